@@ -2,6 +2,7 @@
 """bench.py -- BEV frames/sec of the detector forward on MI355X (BASELINE.json's metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config 2|3|1|5] [--mode infer|train]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one forward of `FlexibleMultiModal3DDetector` over a batch of B synthetic frames
@@ -14,13 +15,18 @@ over ranks as independent replicas (inference has no collective) -
 BEFORE it touches the GPU, forwards their output and exits with their code.  Every rank
 checks that the world it joined has exactly N ranks and fails otherwise.
 
-Rank 0 prints ONE JSON line: the whole-job frames/s of the headline configuration, the live
-roofline of its dominant kernels (wino_f32 + conv_igemm_f32, HIP events on the launch stream
-inside the timed region), the CPU baseline (the oracle on the host cores, N=1 only) and, at
-N=1 under `extra.configs`, short legs of the other BASELINE configs (3: bf16 full fusion,
-5: bf16 bandwidth-stress, 4: the training step), each with its own live roofline.  At N>1
-the line leaves right after the replica headline; the data-parallel training leg (gradient
-all-reduce over RCCL) runs after it and reports on stderr as `[bench extra] {...}`.
+Rank 0 prints ONE JSON line: the whole-job frames/s of the headline configuration and its
+`ms_per_step`.  A plain run does nothing else: set-up, W warm-up steps, exactly K timed steps,
+the outputs of the last timed step if `--dump-outputs DIR` asks for them (DIR/<name>.npy,
+float32 / float64, at most 64 MB in all), the line.
+
+`--full` adds everything beyond the headline: the live roofline of its dominant kernels
+(wino_f32 + conv_igemm_f32, HIP events on the launch stream inside the timed region), the CPU
+baseline (the oracle on the host cores, N=1 only) and, at N=1 under `extra.configs`, short
+legs of the other BASELINE configs (3: bf16 full fusion, 5: bf16 bandwidth-stress, 4: the
+training step), each with its own live roofline, and the front-end kernels.  At N>1 the line
+leaves right after the replica headline; with `--full` the data-parallel training leg
+(gradient all-reduce over RCCL) runs after it and reports on stderr as `[bench extra] {...}`.
 """
 import argparse
 import json
@@ -88,13 +94,23 @@ def parse_args(argv=None):
                          "a few 1e-7 relative from the exact kernel), exact implicit GEMM for the rest; wino_x3 = opt-in: Winograd as "
                          "above and every other layer through the exact three-plane bf16 split of --dtype f32x3 (fp32-level error)")
     ap.add_argument("--graph", action="store_true", help="replay the inference forward as one hipGraph (small batches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (head tensors; losses in train mode) "
+                         "as DIR/<name>.npy, float32 (float64 stays float64), at most 64 MB in all (a fixed, seeded sample of "
+                         "each array beyond that); rank 0's frames")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: live roofline, CPU baseline, extra.configs legs, front-end kernels; "
+                         "--no-cpu-baseline, --no-kernel-timer, --extras and --extra-steps narrow it and do nothing without it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true", help="skip the per-launch HIP-event brackets")
     ap.add_argument("--extras", choices=["auto", "all", "none"], default="auto",
                     help="extra.configs legs after the headline: auto = configs 3 (bf16), 5 (bf16) and 4 (train) at N=1, "
                          "the data-parallel training leg only at N>1 (it is the one with a collective); none = headline only")
     ap.add_argument("--extra-steps", type=int, default=8)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port() -> int:
@@ -286,7 +302,48 @@ def cpu_baseline(cfg, state_dict, budget_s=8.0):
                        f"frame (= value), then one batch of 8 (= value_b8)")
 
 
-def run_leg(config, dtype, mode, batch, steps, warmup, ctx, graph=False, kernel_timer=True, keep_state=False, conv="f32"):
+DUMP_LIMIT_BYTES = 64 * 10**6     # --dump-outputs: all files together, headers included
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, tensors, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each tensor of `tensors` (name -> tensor, any device) as out_dir/<name>.npy -- float64 stays float64,
+    every other dtype becomes float32 (integer outputs float64, exact to 2^53).  If the arrays would pass `limit_bytes`
+    together, each is replaced by a fixed sample of its flattened elements, sized in proportion to the array: sorted indices
+    drawn without replacement by a generator seeded from DUMP_SAMPLE_SEED and the array's size alone, so two runs of the
+    same arguments sample the same elements.  Returns {name: {"shape", "dtype", "sampled"}}."""
+    import re
+
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    header = 256                                             # upper bound of one .npy header
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        keep64 = t.dtype == torch.float64 or not t.is_floating_point()
+        arrays[re.sub(r"[^A-Za-z0-9_.-]", "_", name)] = (t, np.float64 if keep64 else np.float32)
+    total = sum(t.numel() * np.dtype(dt).itemsize + header for t, dt in arrays.values())
+    budget = max(0, limit_bytes - header * len(arrays))
+    data = sum(t.numel() * np.dtype(dt).itemsize for t, dt in arrays.values())
+    manifest = {}
+    for name, (t, dt) in arrays.items():
+        flat = t.reshape(-1)
+        sampled = None
+        if total > limit_bytes:
+            k = min(flat.numel(), int(budget * (flat.numel() * np.dtype(dt).itemsize / data)) // np.dtype(dt).itemsize)
+            idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, flat.numel()]).choice(flat.numel(), size=k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            sampled = k
+        a = flat.float() if dt == np.float32 else flat.double()
+        a = a.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if sampled is not None else a.reshape(tuple(t.shape)))
+        manifest[name] = {"shape": list(t.shape), "dtype": np.dtype(dt).name, "sampled": sampled}
+    return manifest
+
+
+def run_leg(config, dtype, mode, batch, steps, warmup, ctx, graph=False, kernel_timer=True, keep_state=False, conv="f32",
+            dump_dir=None):
     """One timed leg: W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both
     sides, MAX over ranks.  Returns the leg's record (value = whole-job frames/s) and, if asked, the state dict."""
     import torch
@@ -356,6 +413,7 @@ def run_leg(config, dtype, mode, batch, steps, warmup, ctx, graph=False, kernel_
         per_rank_elapsed = replicas.gather_over_ranks(elapsed, dist, dev)
         elapsed = replicas.max_over_ranks(elapsed, dist, dev)
         timer_steps, timer_elapsed = steps, elapsed
+        dumped = dump_outputs(dump_dir, out) if dump_dir is not None and rank == 0 else None
         if timer is not None and not timer_in_region:
             engine.set_timer(timer)
             torch.cuda.synchronize()
@@ -377,6 +435,8 @@ def run_leg(config, dtype, mode, batch, steps, warmup, ctx, graph=False, kernel_
            "mode": "inference forward -> 5 head tensors" if mode == "infer"
            else "training step: fwd (train-mode BN) + targets + loss + bwd + grad all-reduce + clip + AdamW"}
     rec["per_rank_elapsed_s"] = per_rank_elapsed
+    if dumped is not None:
+        print(f"[bench] last timed step's outputs -> {dump_dir}: " + json.dumps(dumped), file=sys.stderr, flush=True)
     if mode == "train" and dist is not None:
         rec["grad_allreduce"] = {"collectives_per_step": reducer.collectives / max(1, warmup + steps + (2 if timer else 0)),
                                  "backend": dist.get_backend(), "ranks": dist.get_world_size()}
@@ -438,6 +498,8 @@ def stub_main(args):
         x = (x @ x).clamp_(max=1.0)
     replicas.barrier(dist)
     elapsed = replicas.max_over_ranks(time.perf_counter() - t0, dist, torch.device("cpu"))
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {"x": x})
     if rank == 0:
         print(json.dumps({"metric": "stub", "value": replicas.aggregate_fps(args.steps, world, elapsed), "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "stub": True,
@@ -478,9 +540,12 @@ def main():
     if args.batch is None:
         args.batch = 2 if args.config == 5 else 8
     ctx = dict(dev=dev, dist=dist, rank=rank, world=world, inputs=InputCache(dev))
+    # a plain run measures the headline and nothing else; --full adds the roofline, the CPU baseline and the extra legs
+    want_cpu_baseline = args.full and world == 1 and not args.no_cpu_baseline and args.mode == "infer"
 
     head, state = run_leg(args.config, args.dtype, args.mode, args.batch, args.steps, args.warmup, ctx,
-                          graph=args.graph, kernel_timer=not args.no_kernel_timer, keep_state=True, conv=args.conv)
+                          graph=args.graph, kernel_timer=args.full and not args.no_kernel_timer, keep_state=want_cpu_baseline,
+                          conv=args.conv, dump_dir=args.dump_outputs)
 
     def emit(extras):
         if rank != 0:
@@ -505,7 +570,7 @@ def main():
         for k in ("roofline", "roofline_bev_pool", "grad_allreduce"):
             if k in head:
                 line[k] = head[k]
-        if world == 1 and not args.no_cpu_baseline and args.mode == "infer":
+        if want_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, state)
             line["gpu_over_cpu"] = line["value"] / line["cpu_baseline"]["value"]
             line["gpu_over_cpu_b8"] = line["value"] / line["cpu_baseline"]["value_b8"]
@@ -519,7 +584,7 @@ def main():
         print(json.dumps(line), flush=True)
 
     plan = []
-    if args.extras != "none" and not args.graph:
+    if args.full and args.extras != "none" and not args.graph:
         # config 1 = the shape the reference itself runs (ref src/fusion.py:1228-1330: camera_only, B=1, 6x448x800), then B=8
         plan = [(3, "bf16", "infer", 8), (5, "bf16", "infer", 2), (1, "fp32", "infer", 1), (1, "fp32", "infer", 8),
                 (4, "fp32", "train", 8)]

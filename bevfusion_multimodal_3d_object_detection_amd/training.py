@@ -757,6 +757,77 @@ class Bilinear:
         return dx
 
 
+class StemBlock:
+    """The camera stem of the training tape: 7x7 / stride-2 conv 3 -> 64 -> train-mode BatchNorm -> ReLU -> 3x3 / stride-2 max-pool
+    with uint8 window indices.  FUSE_POOL_BN_BACKWARD: BatchNorm + ReLU evaluated inside the max-pool, and the pool backward gathered
+    inside the BatchNorm backward."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+
+    def forward(self, x, N: int, H: int, W: int):
+        """x: NCHW fp32 images [N][3][H][W] -> (pooled NHWC [N*H2*W2*64], H2, W2)."""
+        dev = x.device
+        self.cam_geom_in = (N, H, W)
+        self.imgs = x
+        H1, W1 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        w = self.conv.weight.detach()
+        packed = torch.zeros(148, 64, device=dev)
+        packed[:147] = w.reshape(64, 147).t()
+        one, zero = torch.ones(64, device=dev), torch.zeros(64, device=dev)
+        raw = _new(N * H1 * W1 * 64, dev)
+        L.stem_conv7x7(x, packed.view(-1), one, zero, raw, N, H, W, relu=False)
+        H2, W2 = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
+        pooled = _new(N * H2 * W2 * 64, dev)
+        self.pool_idx = torch.empty(N * H2 * W2 * 64, dtype=torch.uint8, device=dev)
+        self.stem_fused = FUSE_POOL_BN_BACKWARD and not bn_is_frozen(self.bn)
+        if self.stem_fused:
+            # statistics only; BatchNorm + ReLU are evaluated inside the max-pool: the normalised stem map (1.1 GB) is never written --
+            # nothing downstream reads it (the backward recomputes the ReLU mask from the raw conv output)
+            _, self.stem_bn = bn_train_forward(raw, self.bn, N * H1 * W1, 64, relu=True, apply=False)
+            s = self.stem_bn
+            g = self.bn.weight.data_ptr() if self.bn.weight is not None else None
+            b = self.bn.bias.data_ptr() if self.bn.bias is not None else None
+            _ck(_lib().bevf_bn_relu_maxpool3x3s2_idx_f32(raw.data_ptr(), s.mean.data_ptr(), s.invstd.data_ptr(), g, b, pooled.data_ptr(),
+                                                         self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
+                "bevf_bn_relu_maxpool3x3s2_idx_f32")
+        else:
+            y, self.stem_bn = bn_train_forward(raw, self.bn, N * H1 * W1, 64, relu=True)
+            _ck(_lib().bevf_maxpool3x3s2_idx_f32(y.data_ptr(), pooled.data_ptr(), self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
+                "bevf_maxpool3x3s2_idx_f32")
+        self.pool_geom = (N, H1, W1)
+        return pooled, H2, W2
+
+    def backward(self, d, sink: GradSink) -> None:
+        """d: gradient of the pooled map (NHWC); adds the conv weight and BatchNorm gradients to `sink`."""
+        N, H1, W1 = self.pool_geom
+        if self.stem_fused:
+            # max-pool backward + BatchNorm/ReLU backward in one pair of passes: the dense dY of the stem map (1.1 GB at 48 images of
+            # 448x800) is gathered from the pooled gradient on the fly, never written (bit-identical to the two-kernel chain below)
+            s = self.stem_bn
+            work = _new(_lib().bevf_bn_work_floats(64), d.device)
+            dgamma, dbeta, draw = _new(64, d.device), _new(64, d.device), _new(N * H1 * W1 * 64, d.device)
+            g = self.bn.weight.data_ptr() if self.bn.weight is not None else None
+            b = self.bn.bias.data_ptr() if self.bn.bias is not None else None
+            _ck(_lib().bevf_pool_bn_backward_f32(d.data_ptr(), self.pool_idx.data_ptr(), s.xraw.data_ptr(), s.mean.data_ptr(),
+                                                 s.invstd.data_ptr(), g, b, work.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                 draw.data_ptr(), N, H1, W1, 64, _st()), "bevf_pool_bn_backward_f32")
+        else:
+            dpool_in = _new(N * H1 * W1 * 64, d.device)
+            _ck(_lib().bevf_maxpool3x3s2_bwd_f32(d.data_ptr(), self.pool_idx.data_ptr(), dpool_in.data_ptr(), N, H1, W1, 64, _st()),
+                "bevf_maxpool3x3s2_bwd_f32")
+            draw, dgamma, dbeta = bn_train_backward(dpool_in, self.stem_bn, self.bn, relu=True)
+        sink.add(self.bn.weight, dgamma)
+        sink.add(self.bn.bias, dbeta)
+        # stem weight gradient: direct MFMA kernel on the image patches (no im2col matrix), dW as [64][160]
+        Ni, H, W = self.cam_geom_in
+        dwbuf = _zeros(64 * 160, d.device)
+        with E._span("conv_wgrad_f32", flops=2.0 * N * H1 * W1 * 64 * 147):
+            _ck(_lib().bevf_stem_wgrad_f32(self.imgs.data_ptr(), draw.data_ptr(), dwbuf.data_ptr(), Ni, H, W, _st()),
+                "bevf_stem_wgrad_f32")
+        sink.add(self.conv.weight, dwbuf[:64 * 160].view(64, 160)[:, :147].reshape(64, 3, 7, 7))
+
+
 # ---- the detector graph --------------------------------------------------------------------------------------------------------
 
 class DetectorTape:
@@ -775,35 +846,8 @@ class DetectorTape:
             B, n = imgs.shape[0], 1
             x = imgs.contiguous().float()
         N, _, H, W = x.shape
-        dev = x.device
-        self.cam_geom_in = (N, H, W)
-        self.imgs = x
-        H1, W1 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        w = enc.conv1.weight.detach()
-        packed = torch.zeros(148, 64, device=dev)
-        packed[:147] = w.reshape(64, 147).t()
-        one, zero = torch.ones(64, device=dev), torch.zeros(64, device=dev)
-        raw = _new(N * H1 * W1 * 64, dev)
-        L.stem_conv7x7(x, packed.view(-1), one, zero, raw, N, H, W, relu=False)
-        H2, W2 = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
-        pooled = _new(N * H2 * W2 * 64, dev)
-        self.pool_idx = torch.empty(N * H2 * W2 * 64, dtype=torch.uint8, device=dev)
-        self.stem_fused = FUSE_POOL_BN_BACKWARD and not bn_is_frozen(enc.bn1)
-        if self.stem_fused:
-            # statistics only; BatchNorm + ReLU are evaluated inside the max-pool: the normalised stem map (1.1 GB) is never written --
-            # nothing downstream reads it (the backward recomputes the ReLU mask from the raw conv output)
-            _, self.stem_bn = bn_train_forward(raw, enc.bn1, N * H1 * W1, 64, relu=True, apply=False)
-            s = self.stem_bn
-            g = enc.bn1.weight.data_ptr() if enc.bn1.weight is not None else None
-            b = enc.bn1.bias.data_ptr() if enc.bn1.bias is not None else None
-            _ck(_lib().bevf_bn_relu_maxpool3x3s2_idx_f32(raw.data_ptr(), s.mean.data_ptr(), s.invstd.data_ptr(), g, b, pooled.data_ptr(),
-                                                         self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_bn_relu_maxpool3x3s2_idx_f32")
-        else:
-            y, self.stem_bn = bn_train_forward(raw, enc.bn1, N * H1 * W1, 64, relu=True)
-            _ck(_lib().bevf_maxpool3x3s2_idx_f32(y.data_ptr(), pooled.data_ptr(), self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_maxpool3x3s2_idx_f32")
-        self.pool_geom = (N, H1, W1)
+        self.stem = StemBlock(enc.conv1, enc.bn1)
+        pooled, H2, W2 = self.stem.forward(x, N, H, W)
         cur, h, wd = pooled, H2, W2
         self.blocks = []
         for layer in (enc.layer1, enc.layer2, enc.layer3):
@@ -822,7 +866,6 @@ class DetectorTape:
         return feat, (B, n, h, wd)
 
     def _camera_backward(self, dfeat, sink):
-        enc = self.m.camera_encoder
         d, _ = self.proj.backward(dfeat, sink)
         rev = list(reversed(self.blocks))
         pre = None                                             # BatchNorm-backward partials that arrive WITH d (or None)
@@ -841,32 +884,7 @@ class DetectorTape:
             d = dx
             if i % 2 == 1:
                 sink.ready()                                   # one ResNet stage done: its gradients can travel
-        N, H1, W1 = self.pool_geom
-        if self.stem_fused:
-            # max-pool backward + BatchNorm/ReLU backward in one pair of passes: the dense dY of the stem map (1.1 GB at 48 images of
-            # 448x800) is gathered from the pooled gradient on the fly, never written (bit-identical to the two-kernel chain below)
-            s = self.stem_bn
-            work = _new(_lib().bevf_bn_work_floats(64), d.device)
-            dgamma, dbeta, draw = _new(64, d.device), _new(64, d.device), _new(N * H1 * W1 * 64, d.device)
-            g = enc.bn1.weight.data_ptr() if enc.bn1.weight is not None else None
-            b = enc.bn1.bias.data_ptr() if enc.bn1.bias is not None else None
-            _ck(_lib().bevf_pool_bn_backward_f32(d.data_ptr(), self.pool_idx.data_ptr(), s.xraw.data_ptr(), s.mean.data_ptr(),
-                                                 s.invstd.data_ptr(), g, b, work.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                 draw.data_ptr(), N, H1, W1, 64, _st()), "bevf_pool_bn_backward_f32")
-        else:
-            dpool_in = _new(N * H1 * W1 * 64, d.device)
-            _ck(_lib().bevf_maxpool3x3s2_bwd_f32(d.data_ptr(), self.pool_idx.data_ptr(), dpool_in.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_maxpool3x3s2_bwd_f32")
-            draw, dgamma, dbeta = bn_train_backward(dpool_in, self.stem_bn, enc.bn1, relu=True)
-        sink.add(enc.bn1.weight, dgamma)
-        sink.add(enc.bn1.bias, dbeta)
-        # stem weight gradient: direct MFMA kernel on the image patches (no im2col matrix), dW as [64][160]
-        Ni, H, W = self.cam_geom_in
-        dwbuf = _zeros(64 * 160, d.device)
-        with E._span("conv_wgrad_f32", flops=2.0 * N * H1 * W1 * 64 * 147):
-            _ck(_lib().bevf_stem_wgrad_f32(self.imgs.data_ptr(), draw.data_ptr(), dwbuf.data_ptr(), Ni, H, W, _st()),
-                "bevf_stem_wgrad_f32")
-        sink.add(enc.conv1.weight, dwbuf[:64 * 160].view(64, 160)[:, :147].reshape(64, 3, 7, 7))
+        self.stem.backward(d, sink)
 
     # -- PointNet ----------------------------------------------------------------------------------------------------------------
     def _lidar_forward(self, pts):

@@ -74,6 +74,11 @@ class VoxelizeDesc(C.Structure):
                [("pc_range", C.c_float * 6), ("voxel_size", C.c_float * 3)]
 
 
+class PillarGeom(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("voxel_features", "voxel_coords", "num_points", "num_voxels")] + \
+               [(n, C.c_int32) for n in ("B", "Nv", "P", "C", "H", "W")] + [(n, C.c_float) for n in ("x0", "y0", "vx", "vy")]
+
+
 class LossDesc(C.Structure):
     _fields_ = [("pred_heatmap", C.c_void_p), ("tgt_heatmap", C.c_void_p), ("pred_reg", C.c_void_p * 4),
                 ("tgt_reg", C.c_void_p * 4), ("ind", C.c_void_p), ("reg_mask", C.c_void_p), ("work", C.c_void_p),
@@ -121,6 +126,11 @@ SIGNATURES = {
     "bevf_voxelize_work_bytes": (C.c_size_t, [C.c_int] * 2),
     "bevf_voxelize_f32": (C.c_int, [C.POINTER(VoxelizeDesc), C.c_void_p]),
     "bevf_scatter_voxels_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "bevf_pillar_work_bytes": (C.c_size_t, [C.c_int]),
+    "bevf_pillar_pfn_f32": (C.c_int, [C.POINTER(PillarGeom)] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 2),
+    "bevf_pillar_moments_f32": (C.c_int, [C.POINTER(PillarGeom)] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_float] +
+                                [C.c_void_p] * 10),
+    "bevf_pillar_pfn_backward_f32": (C.c_int, [C.POINTER(PillarGeom)] + [C.c_void_p] * 10 + [C.c_int] * 2 + [C.c_void_p] * 6),
     # ---- input pipeline ----
     "bevf_resize_normalize_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 +
                                  [C.c_int] + [C.POINTER(C.c_float)] * 2 + [C.c_void_p]),
@@ -644,16 +654,30 @@ def scatter_voxels(features: torch.Tensor, coords: torch.Tensor, grid, num_voxel
     return out
 
 
-def voxelize(points: torch.Tensor, pc_range, voxel_size, max_points: int, max_voxels: int):
+def voxelize_work_bytes(B: int, N: int) -> int:
+    return int(lib().bevf_voxelize_work_bytes(B, N))
+
+
+def voxelize(points: torch.Tensor, pc_range, voxel_size, max_points: int, max_voxels: int, out=None):
+    """out = (feats, coords, npts, nvox, work): caller-owned buffers of at least the sizes allocated below (the engines'
+    grow-only workspaces).  They are NOT zero-filled here: the kernel writes only the kept voxels' rows / entries, so
+    readers of `out` must stop at num_points / num_voxels (the pillar kernels do).  Without `out` the outputs are fresh
+    zero-padded tensors, as before."""
     if points.dim() != 3 or points.shape[2] < 3:
         raise BevfError("voxelize: points must be (B, N, C>=3)")
     B, N, Cc = points.shape
     dev = points.device
-    feats = torch.zeros(B, max_voxels, max_points, Cc, device=dev)
-    coords = torch.zeros(B, max_voxels, 3, dtype=torch.int64, device=dev)
-    npts = torch.zeros(B, max_voxels, dtype=torch.int32, device=dev)
-    nvox = torch.zeros(B, dtype=torch.int32, device=dev)
-    work = torch.empty(lib().bevf_voxelize_work_bytes(B, N), dtype=torch.uint8, device=dev)
+    if out is None:
+        feats = torch.zeros(B, max_voxels, max_points, Cc, device=dev)
+        coords = torch.zeros(B, max_voxels, 3, dtype=torch.int64, device=dev)
+        npts = torch.zeros(B, max_voxels, dtype=torch.int32, device=dev)
+        nvox = torch.zeros(B, dtype=torch.int32, device=dev)
+        work = torch.empty(lib().bevf_voxelize_work_bytes(B, N), dtype=torch.uint8, device=dev)
+    else:
+        feats, coords, npts, nvox, work = out
+        if (feats.numel() < B * max_voxels * max_points * Cc or coords.numel() < B * max_voxels * 3 or npts.numel() < B * max_voxels
+                or nvox.numel() < B or work.numel() < lib().bevf_voxelize_work_bytes(B, N)):
+            raise BevfError("voxelize: out= buffers too small for B, N, C, max_points, max_voxels")
     d = VoxelizeDesc(_pc(points), _p(feats), _p(coords, torch.int64), _p(npts, torch.int32), _p(nvox, torch.int32),
                      _p(work, torch.uint8), B, N, Cc, max_points, max_voxels)
     for i in range(6):
@@ -662,3 +686,52 @@ def voxelize(points: torch.Tensor, pc_range, voxel_size, max_points: int, max_vo
         d.voxel_size[i] = float(voxel_size[i])
     _check(lib().bevf_voxelize_f32(C.byref(d), _stream()), "bevf_voxelize_f32")
     return feats, coords, npts, nvox
+
+
+def pillar_geom(feats, coords, npts, nvox, B: int, Nv: int, P: int, Cc: int, H: int, W: int, x0: float, y0: float,
+                vx: float, vy: float) -> PillarGeom:
+    """Descriptor of voxelize's outputs on a one-pillar-per-cell grid (flat buffers of at least these sizes)."""
+    if feats.numel() < B * Nv * P * Cc or coords.numel() < B * Nv * 3 or npts.numel() < B * Nv or nvox.numel() < B:
+        raise BevfError("pillars: voxel buffers smaller than B, Nv, P, C")
+    return PillarGeom(_p(feats), _p(coords, torch.int64), _p(npts, torch.int32), _p(nvox, torch.int32), B, Nv, P, Cc, H, W,
+                      float(x0), float(y0), float(vx), float(vy))
+
+
+def pillar_work_bytes(Cout: int) -> int:
+    return int(lib().bevf_pillar_work_bytes(Cout))
+
+
+def pillar_pfn(g: PillarGeom, w, scale, shift, Cout: int, canvas, argmax=None) -> None:
+    """Decorate + Linear + scale/shift + ReLU + max over each pillar's rows -> NHWC canvas [B][H][W][Cout] (fp32 or bf16)."""
+    K = g.C + 5
+    if w.numel() != Cout * K or scale.numel() < Cout or shift.numel() < Cout or canvas.numel() < g.B * g.H * g.W * Cout:
+        raise BevfError("pillar_pfn: buffer sizes do not match C, Cout and the canvas")
+    if argmax is not None and argmax.numel() < g.B * g.Nv * Cout:
+        raise BevfError("pillar_pfn: argmax buffer smaller than B * Nv * Cout")
+    bf = canvas.dtype == BF16
+    _check(lib().bevf_pillar_pfn_f32(C.byref(g), _pc(w), _pc(scale), _pc(shift), Cout, _p(canvas, canvas.dtype if bf else torch.float32),
+                                     int(bf), _p(argmax, torch.uint8), _stream()), "bevf_pillar_pfn_f32")
+
+
+def pillar_moments(g: PillarGeom, w, bias, gamma, beta, Cout: int, eps: float, momentum: float, running_mean, running_var, nbt,
+                   moments, mean, invstd, scale, shift, work) -> None:
+    K = g.C + 5
+    if (w.numel() != Cout * K or moments.numel() < 272 or min(mean.numel(), invstd.numel(), scale.numel(), shift.numel()) < Cout
+            or work.numel() < pillar_work_bytes(Cout)):
+        raise BevfError("pillar_moments: buffer sizes do not match C and Cout")
+    _check(lib().bevf_pillar_moments_f32(C.byref(g), _pc(w), _pc(bias), _pc(gamma), _pc(beta), Cout, float(eps), float(momentum),
+                                         _p(running_mean), _p(running_var), _p(nbt, torch.int64), _p(moments, torch.float64),
+                                         _p(mean), _p(invstd), _p(scale), _p(shift), _p(work, torch.uint8), _stream()),
+           "bevf_pillar_moments_f32")
+
+
+def pillar_backward(g: PillarGeom, dcanvas, argmax, w, bias, scale, shift, mean, invstd, gamma, moments, Cout: int, frozen: bool,
+                    dw, db, dgamma, dbeta, work) -> None:
+    K = g.C + 5
+    if (dcanvas.numel() < g.B * g.H * g.W * Cout or argmax.numel() < g.B * g.Nv * Cout or w.numel() != Cout * K
+            or dw.numel() < Cout * K or min(db.numel(), dgamma.numel(), dbeta.numel()) < Cout or work.numel() < pillar_work_bytes(Cout)):
+        raise BevfError("pillar_backward: buffer sizes do not match C, Cout and the canvas")
+    _check(lib().bevf_pillar_pfn_backward_f32(C.byref(g), _pc(dcanvas), _pc(argmax, torch.uint8), _pc(w), _pc(bias), _pc(scale),
+                                              _pc(shift), _pc(mean), _pc(invstd), _pc(gamma), _pc(moments, torch.float64), Cout,
+                                              int(frozen), _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(work, torch.uint8), _stream()),
+           "bevf_pillar_pfn_backward_f32")

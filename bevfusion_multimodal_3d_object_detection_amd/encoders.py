@@ -10,6 +10,7 @@ import warnings
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 import yaml
@@ -349,6 +350,95 @@ class VFELayer(nn.Module):
             return self._engine.run(x.contiguous().float()).view(B, Nv, self.out_channels)
 
 
+PILLAR_TYPES = ("pointpillars", "pillars")
+DEFAULT_PC_RANGE = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)
+
+
+def lidar_encoder_kind(lidar_encoder_type: Optional[str] = None, config: Optional[Dict] = None) -> str:
+    """'pillars' when the keyword -- or, when it is None, `model.lidar_encoder.type` of the config -- names PointPillars
+    (case-insensitive, 'PointPillars' or 'pillars'); 'pointnet' for anything else or nothing (incl. 'PointNet' / 'VoxelNet',
+    the values configs/base.yaml documents but the reference never reads)."""
+    t = lidar_encoder_type
+    if t is None and config is not None:
+        t = (config.get("model", {}).get("lidar_encoder", {}) or {}).get("type")
+    return "pillars" if isinstance(t, str) and t.strip().lower() in PILLAR_TYPES else "pointnet"
+
+
+def pillar_grid(point_cloud_range, bev_h: int, bev_w: int) -> Tuple[float, float, float, float, Tuple[float, float, float]]:
+    """One pillar per BEV cell: (x0, y0, pillar_x, pillar_y, voxel_size) in fp32 -- pillar size (max - min) / cells on x / y,
+    the full z range on z (one pillar per column).  50 x 50 on the base range = 2.048 m, 128^2 = 0.8 m."""
+    r = np.asarray(point_cloud_range, dtype=np.float32)
+    vx = np.float32(r[3] - r[0]) / np.float32(bev_w)
+    vy = np.float32(r[4] - r[1]) / np.float32(bev_h)
+    vz = np.float32(r[5] - r[2])
+    return float(r[0]), float(r[1]), float(vx), float(vy), (float(vx), float(vy), float(vz))
+
+
+class PillarLiDAREncoder(nn.Module):
+    """PointPillars LiDAR front end on the BEV grid (opt-in: `model.lidar_encoder.type: 'PointPillars'`).  Not in the
+    reference, whose voxel path never runs; the semantics are the standard PointPillars ones (include/bevf.h, pillars):
+    points (B,N,C) -> voxelize on one pillar per BEV cell -> decorated points (C + 5 channels) -> pfn = VFELayer(C + 5,
+    pfn_channels) over all P rows of every occupied pillar -> max per pillar -> canvas (B, pfn_channels, bev_h, bev_w),
+    row = y index, column = x index, exactly 0 at empty cells."""
+
+    is_pillars = True
+
+    def __init__(self, input_channels: Optional[int] = None, pfn_channels: Optional[int] = None, bev_h: Optional[int] = None,
+                 bev_w: Optional[int] = None, point_cloud_range=None, max_points_per_pillar: Optional[int] = None,
+                 max_pillars: Optional[int] = None, config: Optional[Dict] = None, config_path: Optional[str] = None):
+        super().__init__()
+        config = _cfg(config, config_path)
+        if config is not None:
+            c, d = config.get("model", {}).get("lidar_encoder", {}) or {}, config.get("dataset", {})
+            input_channels = c.get("input_channels", 5) if input_channels is None else input_channels
+            pfn_channels = c.get("pfn_channels", 64) if pfn_channels is None else pfn_channels
+            max_points_per_pillar = c.get("max_points_per_pillar", 32) if max_points_per_pillar is None else max_points_per_pillar
+            max_pillars = c.get("max_pillars", 12000) if max_pillars is None else max_pillars
+            point_cloud_range = d.get("point_cloud_range", DEFAULT_PC_RANGE) if point_cloud_range is None else point_cloud_range
+            bev_h = d.get("bev_h", 50) if bev_h is None else bev_h
+            bev_w = d.get("bev_w", 50) if bev_w is None else bev_w
+        self.input_channels = 4 if input_channels is None else int(input_channels)
+        self.pfn_channels = 64 if pfn_channels is None else int(pfn_channels)
+        self.max_points = 32 if max_points_per_pillar is None else int(max_points_per_pillar)
+        self.max_pillars = 12000 if max_pillars is None else int(max_pillars)
+        self.pc_range = tuple(float(v) for v in (DEFAULT_PC_RANGE if point_cloud_range is None else point_cloud_range))
+        self.bev_h = 50 if bev_h is None else int(bev_h)
+        self.bev_w = 50 if bev_w is None else int(bev_w)
+        if not 3 <= self.input_channels <= 11:
+            raise L.BevfError(f"PillarLiDAREncoder: input_channels={self.input_channels}: the decorated point (C + 5 channels) "
+                              "must fit 16 channels and carry x, y, z, so 3 <= C <= 11")
+        if self.pfn_channels % 32 or not 0 < self.pfn_channels <= 128:
+            raise L.BevfError(f"PillarLiDAREncoder: pfn_channels={self.pfn_channels} must be a multiple of 32 up to 128")
+        if not 0 < self.max_points <= 255 or self.max_pillars <= 0:
+            raise L.BevfError("PillarLiDAREncoder: need 0 < max_points_per_pillar <= 255 and max_pillars > 0")
+        self.pfn = VFELayer(self.input_channels + 5, self.pfn_channels)
+        self._engine = None
+
+    def grid(self):
+        return pillar_grid(self.pc_range, self.bev_h, self.bev_w)
+
+    def _eng(self) -> E.PillarEngine:
+        if self._engine is None:
+            object.__setattr__(self, "_engine", E.PillarEngine(self))
+        return self._engine
+
+    def forward_nhwc(self, points: torch.Tensor) -> torch.Tensor:
+        """Internal fast path: the canvas as an NHWC view (B, bev_h, bev_w, pfn_channels) in the storage dtype."""
+        E.require_cuda(points)
+        return self._eng().run(points)
+
+    def forward(self, points: torch.Tensor) -> torch.Tensor:
+        if self.training and _training().wants_train_path(self):
+            E.require_cuda(points)
+            return _training().pillar_train_forward(self, points)
+        with torch.no_grad():
+            return self._forward_eval(points)
+
+    def _forward_eval(self, points: torch.Tensor) -> torch.Tensor:
+        c = self.forward_nhwc(points)
+        return E.to_nchw(c, c.shape[0], self.pfn_channels, self.bev_h, self.bev_w)
+
+
 class VoxelNetLiDAREncoder(nn.Module):
     """ref src/encoders.py:308-417.  Dead code in the reference (never imported by fusion.py) and its
     forward raises: vfe2 receives vfe1's 3-D output and cannot unpack 4 dims (ref :395-396 vs :438).
@@ -390,4 +480,5 @@ def print_encoder_specs():
     print("=" * 80)
     print("camera : ResNet-18 conv1..layer3 + 1x1 proj, (B,6,3,H,W) -> (B,6,512,H/16,W/16)")
     print("lidar  : PointNet shared MLP 64-128-256-512-1024 + max, (B,N,C) -> (B,1024)")
+    print("         or (model.lidar_encoder.type: PointPillars) pillars on the BEV grid, decorated points -> PFN -> canvas")
     print("radar  : 5 x shared MLP 32-64-128-256 + max, concat -> Linear(1280,256), -> (B,256)")

@@ -417,6 +417,49 @@ class VFEEngine(_Engine):
         return gmax.view(torch.float32)
 
 
+def pillar_voxelize(enc: nn.Module, pts: torch.Tensor, alloc) -> Tuple[L.PillarGeom, int, Tuple[torch.Tensor, ...]]:
+    """voxelize on the encoder's one-pillar-per-cell grid into buffers from alloc(name, numel, dtype) -> (descriptor, B, buffers).
+    The descriptor holds raw pointers: the caller keeps `buffers` alive as long as it uses it.  The buffers are not
+    zero-filled: the pillar kernels read only rows < num_points of pillars < num_voxels."""
+    if pts.dim() != 3 or pts.shape[2] != enc.input_channels:
+        raise L.BevfError(f"PillarLiDAREncoder: points must be (B, N, {enc.input_channels}), got {tuple(pts.shape)}")
+    pts = pts.float().contiguous()
+    B, N, Cc = pts.shape
+    P, Nv = enc.max_points, enc.max_pillars
+    x0, y0, vx, vy, vsize = enc.grid()
+    feats = alloc("vox_feats", B * Nv * P * Cc, torch.float32)
+    coords = alloc("vox_coords", B * Nv * 3, torch.int64)
+    npts = alloc("vox_npts", B * Nv, torch.int32)
+    nvox = alloc("vox_nvox", B, torch.int32)
+    work = alloc("vox_work", L.voxelize_work_bytes(B, N), torch.uint8)
+    with _span("voxelize"):
+        L.voxelize(pts, enc.pc_range, vsize, P, Nv, out=(feats, coords, npts, nvox, work))
+    return (L.pillar_geom(feats, coords, npts, nvox, B, Nv, P, Cc, enc.bev_h, enc.bev_w, x0, y0, vx, vy), B,
+            (feats, coords, npts, nvox))
+
+
+class PillarEngine(_Engine):
+    """PillarLiDAREncoder, eval mode: voxelize -> bevf_pillar_pfn_f32 (decoration, Linear + folded BN + ReLU, max over the
+    pillar's rows) -> NHWC canvas [B][bev_h][bev_w][pfn_channels] in the storage dtype (the PFN computes in fp32)."""
+
+    def pack(self) -> None:
+        lin, bn = self.module.pfn.linear, self.module.pfn.bn
+        self.cout, self.k = lin.weight.shape
+        self.w = lin.weight.detach().float().contiguous()
+        self.scale, self.shift = _bn_fold(lin.bias, bn, self.cout, lin.weight.device)
+
+    def run(self, pts: torch.Tensor) -> torch.Tensor:
+        self.ensure_packed()
+        m = self.module
+        g, B, _ = pillar_voxelize(m, pts, lambda name, n, dt: self.buf(name, n, dt))        # (buffers: the engine's own)
+        n = B * m.bev_h * m.bev_w * self.cout
+        canvas = self.buf("canvas", n)
+        # algorithmic bytes: the occupied rows are not known on the host; the span carries the canvas write only
+        with _span("pillar_pfn", flops=0.0, nbytes=float(canvas.element_size()) * n):
+            L.pillar_pfn(g, self.w, self.scale, self.shift, self.cout, canvas)
+        return canvas[:n].view(B, m.bev_h, m.bev_w, self.cout)
+
+
 class RadarEngine(_Engine):
     """MultiRadarEncoder: shared RadarEncoder per sweep + concat/max/mean (ref src/encoders.py:628-661)."""
 
@@ -482,7 +525,10 @@ class FusionEngine(_Engine):
         if m.use_camera:
             self.cam1 = pack_conv(m.camera_proj[0], m.camera_proj[1], True)
             self.cam2 = pack_conv(m.camera_proj[3], m.camera_proj[4], True)
-        if m.use_lidar:
+        if m.use_lidar and getattr(m, "lidar_kind", "pointnet") == "pillars":
+            self.lb1 = pack_conv(m.lidar_bev[0], m.lidar_bev[1], True)
+            self.lb2 = pack_conv(m.lidar_bev[3], m.lidar_bev[4], True)
+        elif m.use_lidar:
             l0, l2 = m.lidar_init[0], m.lidar_init[2]
             self.li0 = (l0.weight.detach().contiguous(), l0.bias.detach().float().contiguous())
             self.li2 = (l2.weight.detach().contiguous(), l2.bias.detach().float().contiguous())
@@ -500,8 +546,9 @@ class FusionEngine(_Engine):
 
     def run(self, cam: Optional[torch.Tensor], cam_geom: Optional[Tuple[int, int, int, int]],
             lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int]:
-        """cam: NHWC encoder features [B*ncam][Hc][Wc][C] with cam_geom = (B, ncam, Hc, Wc); lidar (B,1024);
-        radar (B,256).  Returns the fused NHWC map [B][S_h*S_w][bev_channels] and B."""
+        """cam: NHWC encoder features [B*ncam][Hc][Wc][C] with cam_geom = (B, ncam, Hc, Wc); lidar (B,1024), or with a
+        PointPillars branch the NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype; radar (B,256).  Returns the
+        fused NHWC map [B][S_h*S_w][bev_channels] and B."""
         self.ensure_packed()
         m = self.module
         Sh, Sw, bc = m.bev_h, m.bev_w, m.bev_channels
@@ -537,7 +584,16 @@ class FusionEngine(_Engine):
             with _span("bev_pool", nbytes=float(t2.element_size()) * B * bc * (Hc * Wc + Sh * Sw)):
                 L.bilinear_nhwc(t2, concat[slot * bc:], B, Hc, Wc, bc, bc, Sh, Sw, ccs)
             slot += 1
-        if "l" in present:
+        if "l" in present and getattr(m, "lidar_kind", "pointnet") == "pillars":
+            # PointPillars: the canvas is already on the fusion grid -- two conv+BN+ReLU, the second into the concat slice
+            if lidar.dim() != 4 or tuple(lidar.shape[1:]) != (Sh, Sw, self.lb1.cin) or lidar.dtype != self.dtype:
+                raise L.BevfError(f"BEV fusion (PointPillars): expected an NHWC {self.dtype} canvas (B, {Sh}, {Sw}, {self.lb1.cin}), "
+                                  f"got {lidar.dtype} {tuple(lidar.shape)}")
+            t = self.buf("lid_bev1", B * P * self.lb1.cout)
+            _run_conv(self.lb1, lidar, t, B, Sh, Sw)
+            _run_conv(self.lb2, t, concat[slot * bc:], B, Sh, Sw, y_cs=ccs)
+            slot += 1
+        elif "l" in present:
             s0 = m.lidar_start_size
             hid = self.buf("lid_h", B * self.li0[0].shape[0], torch.float32)       # small per-frame vectors stay fp32
             L.linear(lidar.float().contiguous(), self.li0[0], self.li0[1], hid, B, self.li0[0].shape[1], self.li0[0].shape[0], True)

@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from . import engine as E
-from .encoders import (MultiRadarEncoder, PointNetLiDAREncoder, ResNetCameraEncoder, _cfg, load_config)  # noqa: F401
+from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, _cfg,  # noqa: F401
+                       lidar_encoder_kind, load_config)
 
 
 def _cbr(cin: int, cout: int, k: int) -> List[nn.Module]:
@@ -32,6 +33,9 @@ class FlexibleBEVFusion(nn.Module):
     concat [camera, lidar, radar] -> 2 x conv3x3+BN+ReLU.
     Extension: for bev sizes other than 50x50 -- where the reference raises at the
     concat -- the LiDAR map is bilinearly resized like the camera map; the identity at 50x50.
+    Extension (opt-in, lidar_encoder_type / model.lidar_encoder.type 'PointPillars'): the LiDAR input is the pillar
+    canvas (B, pfn_channels, bev_h, bev_w), already on the fusion grid, and the branch is
+    lidar_bev = conv3x3(pfn_channels -> 128)+BN+ReLU -> conv3x3(128 -> bev_channels)+BN+ReLU (no lidar_init / lidar_upsample).
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -39,10 +43,12 @@ class FlexibleBEVFusion(nn.Module):
                  lidar_channels: Optional[int] = None, radar_channels: Optional[int] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, bev_channels: Optional[int] = None,
                  pc_range: Optional[List[float]] = None, config: Optional[Dict] = None,
-                 config_path: Optional[str] = None):
+                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None):
         super().__init__()
         config = _cfg(config, config_path)
         default_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+        self.lidar_kind = lidar_encoder_kind(lidar_encoder_type, config)
+        pillars = self.lidar_kind == "pillars"
         if config is not None:
             mc = config.get("model", {})
             bc, dc = mc.get("bev_fusion", {}), config.get("dataset", {})
@@ -52,7 +58,8 @@ class FlexibleBEVFusion(nn.Module):
             if camera_channels is None:
                 camera_channels = mc.get("camera_encoder", {}).get("output_channels", 512)
             if lidar_channels is None:
-                lidar_channels = mc.get("lidar_encoder", {}).get("feature_dim", 1024)
+                le = mc.get("lidar_encoder", {}) or {}
+                lidar_channels = le.get("pfn_channels", 64) if pillars else le.get("feature_dim", 1024)
             if radar_channels is None:
                 radar_channels = mc.get("radar_encoder", {}).get("feature_dim", 256)
             self.bev_h = bc.get("bev_h", dc.get("bev_h", 200)) if bev_h is None else bev_h
@@ -64,7 +71,7 @@ class FlexibleBEVFusion(nn.Module):
             self.use_lidar = True if use_lidar is None else use_lidar
             self.use_radar = True if use_radar is None else use_radar
             camera_channels = 512 if camera_channels is None else camera_channels
-            lidar_channels = 1024 if lidar_channels is None else lidar_channels
+            lidar_channels = (64 if pillars else 1024) if lidar_channels is None else lidar_channels
             radar_channels = 256 if radar_channels is None else radar_channels
             self.bev_h = 200 if bev_h is None else bev_h
             self.bev_w = 200 if bev_w is None else bev_w
@@ -75,7 +82,9 @@ class FlexibleBEVFusion(nn.Module):
         bevc = self.bev_channels
         if self.use_camera:
             self.camera_proj = nn.Sequential(*_cbr(camera_channels, 512, 3), *_cbr(512, bevc, 1))
-        if self.use_lidar:
+        if self.use_lidar and pillars:
+            self.lidar_bev = nn.Sequential(*_cbr(lidar_channels, 128, 3), *_cbr(128, bevc, 3))
+        elif self.use_lidar:
             hidden, start = 128, 25
             self.lidar_init = nn.Sequential(nn.Linear(lidar_channels, 512), nn.ReLU(inplace=True),
                                             nn.Linear(512, hidden * start * start))
@@ -118,8 +127,11 @@ class FlexibleBEVFusion(nn.Module):
             else:
                 B, Cc, H, W = x.shape
                 cam_nhwc, cam_geom = E.to_nhwc(x).to(self._eng().dtype), (B, 1, H, W)
-        out, B = self.forward_nhwc(cam_nhwc, cam_geom,
-                                   lidar_features.float() if lidar_features is not None else None,
+        lid = lidar_features.float() if lidar_features is not None else None
+        if lid is not None and self.lidar_kind == "pillars" and self.use_lidar:
+            B, Cc, H, W = lid.shape                                       # NCHW canvas -> the engine's NHWC storage
+            lid = E.to_nhwc(lid).to(self._eng().dtype).view(B, H, W, Cc)
+        out, B = self.forward_nhwc(cam_nhwc, cam_geom, lid,
                                    radar_features.float() if radar_features is not None else None)
         return E.to_nchw(out, B, self.bev_channels, self.bev_h, self.bev_w)
 
@@ -132,7 +144,10 @@ class FlexibleBEVFusion(nn.Module):
         out = {}
         if self.use_camera:
             out["camera_proj"] = cnt(self.camera_proj)
-        if self.use_lidar:
+        if self.use_lidar and self.lidar_kind == "pillars":
+            out["lidar_bev"] = cnt(self.lidar_bev)
+            out["lidar_total"] = out["lidar_bev"]
+        elif self.use_lidar:
             out["lidar_init"], out["lidar_upsample"] = cnt(self.lidar_init), cnt(self.lidar_upsample)
             out["lidar_total"] = out["lidar_init"] + out["lidar_upsample"]
         if self.use_radar:
@@ -235,9 +250,12 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  use_radar: Optional[bool] = None, num_classes: Optional[int] = None,
                  fusion_type: Optional[str] = None, detection_head: Optional[str] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
-                 config_path: Optional[str] = None):
+                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None):
         super().__init__()
         config = _cfg(config, config_path)
+        # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
+        # encoder + lidar_bev; anything else -> the reference's PointNet + lidar_init / lidar_upsample
+        self.lidar_encoder_type = "PointPillars" if lidar_encoder_kind(lidar_encoder_type, config) == "pillars" else "PointNet"
         if config is not None:
             mc, dc = config.get("model", {}), config.get("dataset", {})
             self.use_camera = mc.get("use_camera", True) if use_camera is None else use_camera
@@ -261,15 +279,22 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if self.use_camera:
             self.camera_encoder = (ResNetCameraEncoder(config=config) if config is not None
                                    else ResNetCameraEncoder(backbone="resnet18", pretrained=False))
-        if self.use_lidar:
+        pillars = self.lidar_encoder_type == "PointPillars"
+        if self.use_lidar and pillars:
+            self.lidar_encoder = (PillarLiDAREncoder(bev_h=bev_h, bev_w=bev_w, config=config) if config is not None
+                                  else PillarLiDAREncoder(input_channels=4, bev_h=bev_h, bev_w=bev_w))
+        elif self.use_lidar:
             self.lidar_encoder = (PointNetLiDAREncoder(config=config) if config is not None
                                   else PointNetLiDAREncoder(input_channels=4, feat_dim=1024))
         if self.use_radar:
             self.radar_encoder = (MultiRadarEncoder(config=config) if config is not None
                                   else MultiRadarEncoder(input_channels=7, feat_dim=256, num_radars=5))
         if self.fusion_type == "bev":
+            extra = dict(lidar_encoder_type=self.lidar_encoder_type)
+            if self.use_lidar and pillars:
+                extra["lidar_channels"] = self.lidar_encoder.pfn_channels
             self.fusion = FlexibleBEVFusion(use_camera=self.use_camera, use_lidar=self.use_lidar,
-                                            use_radar=self.use_radar, bev_h=bev_h, bev_w=bev_w, config=config)
+                                            use_radar=self.use_radar, bev_h=bev_h, bev_w=bev_w, config=config, **extra)
         elif self.fusion_type == "attention":
             self.fusion = FlexibleAttentionFusion()
         elif self.fusion_type == "late":
@@ -296,7 +321,10 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if self.use_camera and camera_imgs is not None:
             cam, geom = self.camera_encoder.forward_nhwc(camera_imgs)       # stays NHWC: no layout change
         if self.use_lidar and lidar_points is not None:
-            lid = self.lidar_encoder._forward_eval(lidar_points)
+            if getattr(self.lidar_encoder, "is_pillars", False):
+                lid = self.lidar_encoder.forward_nhwc(lidar_points)            # NHWC canvas on the fusion grid
+            else:
+                lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
         fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad)
@@ -350,9 +378,10 @@ class GraphedDetector:
 def create_detector(modality_config: Optional[str] = None, fusion_type: Optional[str] = None,
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
-                    **kwargs) -> FlexibleMultiModal3DDetector:
+                    lidar_encoder_type: Optional[str] = None, **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
-    flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202)."""
+    flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
+    lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type)."""
     config = _cfg(config, config_path)
     if config is not None and modality_config is None:
         modality_config = config.get("model", {}).get("modality_config", "all")
@@ -364,7 +393,8 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
         use_radar = "radar" in m or m == "all"
     return FlexibleMultiModal3DDetector(use_camera=use_camera, use_lidar=use_lidar, use_radar=use_radar,
                                         num_classes=num_classes, fusion_type=fusion_type,
-                                        detection_head=detection_head, config=config, **kwargs)
+                                        detection_head=detection_head, config=config,
+                                        lidar_encoder_type=lidar_encoder_type, **kwargs)
 
 
 def test_all_configurations():

@@ -828,6 +828,68 @@ class StemBlock:
         sink.add(self.conv.weight, dwbuf[:64 * 160].view(64, 160)[:, :147].reshape(64, 3, 7, 7))
 
 
+class PillarPFNLayer:
+    """PillarLiDAREncoder under train-mode BatchNorm: voxelize -> the PFN's batch statistics from the decorated points' moments
+    (bevf_pillar_moments_f32: sum f, sum f f^T over the P rows of every occupied pillar, the empty pillar slots left out; running
+    buffers updated there) -> bevf_pillar_pfn_f32 with those scale / shift, keeping the argmax row of every (pillar, channel) ->
+    fp32 NHWC canvas.  Frozen BatchNorm (bn_is_frozen): the running statistics.  Backward: bevf_pillar_pfn_backward_f32 -- the
+    canvas gradient at the argmax rows gives the weight, bias and BatchNorm gradients in closed form (no per-row pass)."""
+
+    def __init__(self, enc):
+        self.enc = enc
+
+    def forward(self, pts):
+        enc = self.enc
+        lin, bn = enc.pfn.linear, enc.pfn.bn
+        dev = pts.device
+        self.g, self.B, self.vox = E.pillar_voxelize(enc, pts, lambda name, n, dt: _new(n, dev, dt))    # vox: kept for g's pointers
+        self.cout, self.k = lin.weight.shape
+        Cout = self.cout
+        self.w = lin.weight.detach().float().contiguous()
+        self.bias = lin.bias.detach().float().contiguous() if lin.bias is not None else None
+        self.gamma = bn.weight.detach().float().contiguous() if bn.weight is not None else None
+        self.frozen = bn_is_frozen(bn)
+        self.moments = None
+        if self.frozen:                                         # channel-sized torch arithmetic, as bn_train_forward's frozen path
+            self.mean = bn.running_mean.detach().float().contiguous()
+            self.invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps).contiguous()
+            g = self.gamma if self.gamma is not None else torch.ones(Cout, device=dev)
+            b = self.bias if self.bias is not None else torch.zeros(Cout, device=dev)
+            be = bn.bias.detach().float() if bn.bias is not None else torch.zeros(Cout, device=dev)
+            self.scale = (g * self.invstd).contiguous()
+            self.shift = (be + (b - self.mean) * self.scale).contiguous()
+        else:
+            self.moments = torch.empty(272, dtype=torch.float64, device=dev)
+            self.mean, self.invstd, self.scale, self.shift = (_new(Cout, dev) for _ in range(4))
+            work = torch.empty(L.pillar_work_bytes(Cout), dtype=torch.uint8, device=dev)
+            track = bn.track_running_stats and bn.running_mean is not None
+            L.pillar_moments(self.g, self.w, self.bias, self.gamma, bn.bias.detach() if bn.bias is not None else None, Cout,
+                             bn.eps, -1.0 if bn.momentum is None else bn.momentum, bn.running_mean if track else None,
+                             bn.running_var if track else None, bn.num_batches_tracked if track else None, self.moments,
+                             self.mean, self.invstd, self.scale, self.shift, work)
+            if track:
+                for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):   # written through raw pointers
+                    if t is not None:
+                        torch.autograd.graph.increment_version(t)
+        H, W = enc.bev_h, enc.bev_w
+        self.canvas = _new(self.B * H * W * Cout, dev)
+        self.argmax = torch.empty(max(self.g.B * self.g.Nv * Cout, 4), dtype=torch.uint8, device=dev)
+        L.pillar_pfn(self.g, self.w, self.scale, self.shift, Cout, self.canvas, self.argmax)
+        return self.canvas
+
+    def backward(self, dcanvas, sink: GradSink) -> None:
+        lin, bn = self.enc.pfn.linear, self.enc.pfn.bn
+        dev, Cout, K = dcanvas.device, self.cout, self.k
+        dw, db, dgamma, dbeta = _new(Cout * K, dev), _new(Cout, dev), _new(Cout, dev), _new(Cout, dev)
+        work = torch.empty(L.pillar_work_bytes(Cout), dtype=torch.uint8, device=dev)
+        L.pillar_backward(self.g, dcanvas.contiguous(), self.argmax, self.w, self.bias, self.scale, self.shift, self.mean, self.invstd,
+                          self.gamma, self.moments, Cout, self.frozen, dw, db, dgamma, dbeta, work)
+        sink.add(lin.weight, dw[:Cout * K])
+        sink.add(lin.bias, db[:Cout])
+        sink.add(bn.weight, dgamma[:Cout])
+        sink.add(bn.bias, dbeta[:Cout])
+
+
 # ---- the detector graph --------------------------------------------------------------------------------------------------------
 
 class DetectorTape:
@@ -889,6 +951,12 @@ class DetectorTape:
     # -- PointNet ----------------------------------------------------------------------------------------------------------------
     def _lidar_forward(self, pts):
         enc = self.m.lidar_encoder
+        if getattr(enc, "is_pillars", False):                         # PointPillars: NHWC fp32 canvas on the BEV grid
+            _no_input_grad(pts, "the LiDAR points")
+            self.pillar = PillarPFNLayer(enc)
+            canvas = self.pillar.forward(pts)
+            self.pn_geom = (self.pillar.B, pts.shape[1], pts.shape[2])
+            return canvas
         rows = enc._rows(pts)
         B, Np, Cc = rows.shape
         M = B * Np
@@ -912,6 +980,9 @@ class DetectorTape:
         return g
 
     def _lidar_backward(self, dg, sink):
+        if getattr(self, "pillar", None) is not None:                # dg: gradient of the NHWC canvas
+            self.pillar.backward(dg, sink)
+            return
         B, Np, Cc = self.pn_geom
         last = self.pn_layers[-1]
         if self.pn_fused_max:
@@ -1044,7 +1115,17 @@ class DetectorTape:
             self.cam_resize.forward(t2, B, Hc, Wc, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
             self.cam_slot = slot
             slot += 1
-        if self.has_lid:
+        self.lid_pillars = self.has_lid and getattr(fus, "lidar_kind", "pointnet") == "pillars"
+        if self.lid_pillars:
+            # PointPillars: the NHWC canvas is on the fusion grid already -- lidar_bev's two conv+BN+ReLU, then the slice copy
+            self.lb1 = ConvBNLayer(fus.lidar_bev[0], fus.lidar_bev[1], True)
+            self.lb2 = ConvBNLayer(fus.lidar_bev[3], fus.lidar_bev[4], True)
+            t1, _, _ = self.lb1.forward(lid_feat, B, Sh, Sw)
+            t2, _, _ = self.lb2.forward(t1, B, Sh, Sw)
+            concat[:B * P * ccs].view(B * P, ccs)[:, slot * bc:(slot + 1) * bc] = t2[:B * P * bc].view(B * P, bc)
+            self.lid_slot = slot
+            slot += 1
+        elif self.has_lid:
             s0 = fus.lidar_start_size
             self.li0 = LinearLayer(fus.lidar_init[0], True)
             O = fus.lidar_init[2].weight.shape[0]
@@ -1192,7 +1273,14 @@ class DetectorTape:
             drad = self.rp.backward(drv.contiguous(), sink)
             if on_radar is not None:
                 on_radar(drad)
-        if self.has_lid:
+        if self.has_lid and self.lid_pillars:
+            ccs = self.ccs
+            dt2 = dconcat[:B * P * ccs].view(B * P, ccs)[:, self.lid_slot * bc:(self.lid_slot + 1) * bc].contiguous().view(-1)
+            dt1, _ = self.lb2.backward(dt2, sink)
+            dlid, _ = self.lb1.backward(dt1, sink)
+            if on_lidar is not None:
+                on_lidar(dlid)
+        elif self.has_lid:
             dg3 = self.lid_resize.backward(dconcat[self.lid_slot * bc:])
             dg2, _ = self.lu2.backward(dg3, sink)
             dg1 = self.lid_up.backward(dg2)
@@ -1374,6 +1462,24 @@ def pointnet_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def pillar_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
+    """PillarLiDAREncoder.forward under train-mode BatchNorm -> canvas (B, pfn_channels, bev_h, bev_w), gradients for pfn.*."""
+    _no_input_grad(x, "the LiDAR points")
+    Cout, H, W = enc.pfn_channels, enc.bev_h, enc.bev_w
+
+    def fwd():
+        tape = DetectorTape(SimpleNamespace(lidar_encoder=enc))
+        canvas = tape._lidar_forward(x)
+        return tape, (E.to_nchw(canvas, tape.pillar.B, Cout, H, W),)
+
+    def bwd(tape, douts, sink):
+        tape._lidar_backward(_nhwc(douts[0]), sink)
+        return [None]
+
+    (out,) = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in enc.parameters() if p.requires_grad])
+    return out
+
+
 def vfe_train_forward(layer, x: torch.Tensor) -> torch.Tensor:
     """VFELayer.forward under train-mode BatchNorm (ref src/encoders.py:431-455): Linear -> BatchNorm1d over all B*Nv*P rows (padding
     rows included, as the reference) -> ReLU -> max over the P points of a voxel -> (B, Nv, out_channels)."""
@@ -1433,6 +1539,7 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
     if first is None:
         raise ValueError("No modality features provided")
     B, dev = first.shape[0], first.device
+    pillars = getattr(fus, "lidar_kind", "pointnet") == "pillars"
     geom = None
     if cam is not None:
         geom = (B, cam.shape[1], cam.shape[3], cam.shape[4]) if cam.dim() == 5 else (B, 1, cam.shape[2], cam.shape[3])
@@ -1443,7 +1550,10 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
         if cam is not None:
             _, n, h, w = geom
             cam_nhwc = _nhwc(cam.detach().reshape(B * n, -1, h, w))
-        fused = tape._fusion_forward(cam_nhwc, geom, None if lid is None else lid.detach().float().contiguous(),
+        lid_in = None if lid is None else lid.detach().float().contiguous()
+        if lid_in is not None and pillars:                             # NCHW pillar canvas -> NHWC
+            lid_in = _nhwc(lid_in)
+        fused = tape._fusion_forward(cam_nhwc, geom, lid_in,
                                      None if rad is None else rad.detach().float().contiguous(), B, dev)
         return tape, (E.to_nchw(fused, B, fus.bev_channels, fus.bev_h, fus.bev_w),)
 
@@ -1453,7 +1563,9 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
             _, n, h, w = geom
             Cc = tape.cam_pool_geom[3]
             dcam = E.to_nchw(dcam, B * n, Cc, h, w).view(cam.shape)
-        if dlid is not None:
+        if dlid is not None and pillars:
+            dlid = E.to_nchw(dlid, B, lid.shape[1], lid.shape[2], lid.shape[3])
+        elif dlid is not None:
             dlid = dlid.reshape(-1)[:lid.numel()].view(lid.shape)
         if drad is not None:
             drad = drad.reshape(-1)[:rad.numel()].view(rad.shape)

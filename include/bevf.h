@@ -299,6 +299,52 @@ typedef struct {
 size_t bevf_voxelize_work_bytes(int B, int N);
 int bevf_voxelize_f32(const bevf_voxelize_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PointPillars front end (csrc/pillars.hip): the opt-in LiDAR branch `model.lidar_encoder.type: PointPillars`.  The
+ * reference has no line for it (its voxel path never runs): the semantics are the standard PointPillars
+ * ones, held against the fp64 restatement of tests/pillar_ref.py.  Input = bevf_voxelize_f32's outputs on a grid of ONE
+ * pillar per BEV cell; only rows < num_points of pillars < num_voxels are read (those outputs need no zero fill).
+ * Decorated point (K = C + 5 <= 16 channels): [x, y, z, r, extra..., x - x_mean, y - y_mean, z - z_mean, x - x_c, y - y_c],
+ * means over the pillar's kept points, (x_c, y_c) = (x0, y0) + (index + 0.5) * (vx, vy); padding rows are all-zero.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* voxel_features;   /* [B][Nv][P][C] */
+  const int64_t* voxel_coords;   /* [B][Nv][3] (z, y, x): y = canvas row, x = canvas column */
+  const int32_t* num_points;     /* [B][Nv] */
+  const int32_t* num_voxels;     /* [B] */
+  int32_t B, Nv, P, C, H, W;     /* 3 <= C <= 11, 0 < P <= 255 */
+  float x0, y0, vx, vy;          /* grid origin and pillar size */
+} bevf_pillar_geom;
+/* fp64 partials of the two reduction kernels below: bytes for a work buffer (Cout <= 128).                           */
+size_t bevf_pillar_work_bytes(int Cout);
+/* canvas[b][y][x][c] = max over the P rows of pillar (b, v) of relu((f . w[c]) * scale[c] + shift[c]) at the pillar's
+ * cell, exactly 0 at every other cell (stream-ordered memset inside).  w: [Cout][C + 5], Cout % 32 == 0, <= 128.
+ * canvas fp32, or bf16 (round to nearest even) when canvas_bf16.  argmax (optional): [B][Nv][Cout] uint8, the first
+ * row reaching the maximum (padding rows count as one row at index num_points).  No atomics: bit-reproducible.       */
+int bevf_pillar_pfn_f32(const bevf_pillar_geom* g, const float* w, const float* scale, const float* shift, int Cout,
+                        void* canvas, int canvas_bf16, uint8_t* argmax, void* stream);
+/* Train-mode BatchNorm statistics of the pre-BN activations x = f . w[c] + bias[c] over all P rows of every occupied
+ * pillar (P * sum(num_voxels) rows; the empty slots up to Nv stay out): sum f and sum f f^T in fp64 (per-workgroup
+ * partials, one finishing pass), mean_c = w_c . mu + b_c, var_c = w_c^T Cov w_c.  Writes moments [16 + 256] doubles
+ * (mu, then Cov as [16][16]), mean / invstd (biased variance + eps) and the forward's scale = gamma * invstd,
+ * shift = beta + (bias - mean) * scale.  running_mean / running_var (optional) move as torch's do: momentum, unbiased
+ * variance; momentum < 0 = cumulative average over num_batches_tracked, which is incremented.  gamma / beta / bias may
+ * be null (1 / 0 / 0).                                                                                               */
+int bevf_pillar_moments_f32(const bevf_pillar_geom* g, const float* w, const float* bias, const float* gamma, const float* beta,
+                            int Cout, float eps, float momentum, float* running_mean, float* running_var,
+                            int64_t* num_batches_tracked, double* moments, float* mean, float* invstd, float* scale,
+                            float* shift, void* work, void* stream);
+/* Parameter gradients of the PFN from the canvas gradient dcanvas [B][H][W][Cout] (fp32): each (pillar, channel) passes
+ * its cell's gradient to its argmax row through the ReLU, giving sum dy, sum dy x_hat and A = sum dy f; then
+ *   dw[c] = gamma invstd (A - sum(dy) mu - sum(dy x_hat) invstd Cov w[c]),  db = sum of the BatchNorm data gradient,
+ *   dgamma = sum dy x_hat,  dbeta = sum dy
+ * (frozen != 0: mean / invstd are the running statistics, dw = gamma invstd A, db = gamma invstd sum dy, moments unused).
+ * scale / shift / mean / invstd as the forward used them.  Two-stage fp64 partials, no atomics.                       */
+int bevf_pillar_pfn_backward_f32(const bevf_pillar_geom* g, const float* dcanvas, const uint8_t* argmax, const float* w,
+                                 const float* bias, const float* scale, const float* shift, const float* mean,
+                                 const float* invstd, const float* gamma, const double* moments, int Cout, int frozen,
+                                 float* dw, float* db, float* dgamma, float* dbeta, void* work, void* stream);
+
 /* Dense scatter of per-voxel features [B][Nv][C] into out [B][C][D][H][W] at voxel_coords (z,y,x) -- the pillar -> BEV
  * canvas step, ref src/encoders.py:399-410 (`feature_grid[b, :, c0, c1, c2] = features.T`, rows in order: when several
  * rows name one cell the LAST one wins; cells no row names are zero).  num_voxels [B] or NULL: with it only rows

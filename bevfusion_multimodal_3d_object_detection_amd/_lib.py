@@ -1,7 +1,8 @@
 """ctypes binding of libbevf_hip.so (include/bevf.h).  Fails loudly if the library is missing.
 
-Every wrapper takes torch CUDA tensors, checks device / dtype / contiguity on the host,
-passes raw `data_ptr()`s and launches on torch's current HIP stream, so the launches are
+This is the one module that knows the C ABI: every launch in the package goes through a wrapper
+here.  A wrapper takes torch CUDA tensors, checks buffer sizes, device / dtype / contiguity on
+the host, passes raw `data_ptr()`s and launches on torch's current HIP stream, so the launches are
 ordered with (and graph-capturable alongside) everything else torch does on that stream.
 There is no CPU fallback: a CPU tensor raises.
 """
@@ -88,7 +89,7 @@ class LossDesc(C.Structure):
 
 _lib: Optional[C.CDLL] = None
 
-# name -> (restype, argtypes); the not-gpu test checks every one is exported by the .so
+# name -> (restype, argtypes); tests/test_abi_and_host.py holds these, and the Structures above, equal to include/bevf.h
 SIGNATURES = {
     "bevf_version": (C.c_int, []),
     "bevf_last_error": (C.c_char_p, []),
@@ -214,13 +215,15 @@ def lib() -> C.CDLL:
     return _lib
 
 
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise BevfError(f"{what} failed ({rc}): {lib().bevf_last_error().decode()}")
-
-
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _call(name: str, *args) -> None:
+    """Launch entry point `name` on torch's current stream; a nonzero status raises with the library's message."""
+    rc = getattr(lib(), name)(*args, _stream())
+    if rc != 0:
+        raise BevfError(f"{name} failed ({rc}): {lib().bevf_last_error().decode()}")
 
 
 def _p(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
@@ -278,7 +281,7 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, scale, shift, y: Optional[torc
     d = ConvDesc(_p(x, dt), _pc(w, w.dtype), _pc(scale), _pc(shift), _p(res, dt), _p(y, dt), _pc(colmax, torch.int32),
                  N, H, W, Cin, x_cs, Ho, Wo, Cout, y_cs, res_cs, KH, KW, stride, pad, int(relu), rows_per_group, tile)
     fn = "bevf_conv2d_nhwc_f32x3" if split else "bevf_conv2d_nhwc_" + _sfx(x)
-    _check(getattr(lib(), fn)(C.byref(d), _stream()), fn)
+    _call(fn, C.byref(d))
 
 
 def wino_filter_transform(w_ohwi: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
@@ -287,8 +290,13 @@ def wino_filter_transform(w_ohwi: torch.Tensor, Cout: int, Cin: int) -> torch.Te
     if w_ohwi.numel() != Cout * 9 * Cin:
         raise BevfError(f"wino_filter_transform: filter has {w_ohwi.numel()} elements, expected {Cout * 9 * Cin}")
     u = torch.empty(lib().bevf_wino_filter_floats(Cout, Cin), dtype=torch.float32, device=w_ohwi.device)
-    _check(lib().bevf_wino_filter_transform_f32(_pc(w_ohwi), _p(u), Cout, Cin, _stream()), "bevf_wino_filter_transform_f32")
+    _call("bevf_wino_filter_transform_f32", _pc(w_ohwi), _p(u), Cout, Cin)
     return u
+
+
+def wino_stat_rows(N: int, H: int, W: int) -> int:
+    """Rows of conv3x3_wino's BatchNorm partial-sum buffer."""
+    return int(lib().bevf_wino_stat_rows(N, H, W))
 
 
 def conv3x3_wino(x: torch.Tensor, u: torch.Tensor, scale, shift, y: torch.Tensor, *, N: int, H: int, W: int, Cin: int,
@@ -299,7 +307,7 @@ def conv3x3_wino(x: torch.Tensor, u: torch.Tensor, scale, shift, y: torch.Tensor
     tile: 0 = the tiling that covers the batch with the fewest blocks, 1 = 16x16-pixel blocks per image, 2 = 32x8-pixel blocks per image,
     3 / 4 = the same two block shapes over the images' rows stacked into one map (bit-identical results, fewer dead rows).
     `stats` [bevf_wino_stat_rows(N,H,W)][Cout][2]: also leave the BatchNorm partial sums of the output (training)."""
-    if stats is not None and stats.numel() < lib().bevf_wino_stat_rows(N, H, W) * Cout * 2:
+    if stats is not None and stats.numel() < wino_stat_rows(N, H, W) * Cout * 2:
         raise BevfError("conv_wino: stats buffer too small")
     if stats_pivot is not None and stats_pivot.numel() < Cout:
         raise BevfError("conv_wino: stats_pivot shorter than Cout")
@@ -326,7 +334,7 @@ def conv3x3_wino(x: torch.Tensor, u: torch.Tensor, scale, shift, y: torch.Tensor
         d.bnb_x, d.bnb_y = _p(bnb["x"]), _p(bnb.get("y"))
         d.bnb_mean, d.bnb_invstd = _p(bnb["mean"]), _p(bnb["invstd"])
         d.bnb_gamma, d.bnb_beta = _p(bnb.get("gamma")), _p(bnb.get("beta"))
-    _check(lib().bevf_conv3x3_wino_f32(C.byref(d), _stream()), "bevf_conv3x3_wino_f32")
+    _call("bevf_conv3x3_wino_f32", C.byref(d))
 
 
 def conv3x3_pack_bf16(w_ohwi: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
@@ -335,8 +343,7 @@ def conv3x3_pack_bf16(w_ohwi: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor
     if w_ohwi.dtype != torch.bfloat16 or w_ohwi.numel() != Cout * 9 * Cin:
         raise BevfError(f"conv3x3_pack: need a bf16 filter of {Cout * 9 * Cin} elements, got {w_ohwi.dtype} x {w_ohwi.numel()}")
     out = torch.empty(lib().bevf_conv3x3_pack_elems(Cout, Cin), dtype=torch.bfloat16, device=w_ohwi.device)
-    _check(lib().bevf_conv3x3_pack_bf16(_pc(w_ohwi, torch.bfloat16), _p(out, torch.bfloat16), Cout, Cin, _stream()),
-           "bevf_conv3x3_pack_bf16")
+    _call("bevf_conv3x3_pack_bf16", _pc(w_ohwi, torch.bfloat16), _p(out, torch.bfloat16), Cout, Cin)
     return out
 
 
@@ -361,20 +368,20 @@ def conv3x3_bf16(x: torch.Tensor, wp: torch.Tensor, scale, shift, y: torch.Tenso
             raise BevfError("conv3x3_bf16: scale/shift length != Cout")
     d = ConvDesc(_p(x, dt), _pc(wp, dt), _pc(scale), _pc(shift), _p(res, dt), _p(y, dt), None, N, H, W, Cin, x_cs, H, W, Cout,
                  y_cs, res_cs, 3, 3, 1, 1, int(relu), 0, int(tile))
-    _check(lib().bevf_conv3x3_bf16(C.byref(d), _stream()), "bevf_conv3x3_bf16")
+    _call("bevf_conv3x3_bf16", C.byref(d))
 
 
 def split_weights_f32x3(w: torch.Tensor) -> torch.Tensor:
     """fp32 packed filter -> [3][n] bf16 planes (hi, mid, lo) for the f32x3 convolution."""
     w = w.contiguous()
     out = torch.empty(3 * w.numel(), dtype=torch.bfloat16, device=w.device)
-    _check(lib().bevf_split_weights_f32x3(_pc(w), _p(out, torch.bfloat16), w.numel(), _stream()), "bevf_split_weights_f32x3")
+    _call("bevf_split_weights_f32x3", _pc(w), _p(out, torch.bfloat16), w.numel())
     return out
 
 
 def stem_pack_bf16(w_oihw: torch.Tensor) -> torch.Tensor:
     out = torch.empty(64 * 176, dtype=torch.bfloat16, device=w_oihw.device)
-    _check(lib().bevf_stem_pack_bf16(_pc(w_oihw.float().contiguous()), _p(out, torch.bfloat16), _stream()), "bevf_stem_pack_bf16")
+    _call("bevf_stem_pack_bf16", _pc(w_oihw.float().contiguous()), _p(out, torch.bfloat16))
     return out
 
 
@@ -383,8 +390,8 @@ def stem_conv7x7_bf16mma(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, 
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     if x.numel() != N * 3 * H * W or w_packed.numel() != 64 * 176 or y.numel() < N * Ho * Wo * 64:
         raise BevfError("stem bf16: buffer sizes do not match N,H,W")
-    _check(lib().bevf_stem_conv7x7_bf16mma(_pc(x), _pc(w_packed, torch.bfloat16), _pc(scale), _pc(shift), _p(y, torch.bfloat16),
-                                           N, H, W, int(relu), _stream()), "bevf_stem_conv7x7_bf16mma")
+    _call("bevf_stem_conv7x7_bf16mma", _pc(x), _pc(w_packed, torch.bfloat16), _pc(scale), _pc(shift), _p(y, torch.bfloat16),
+          N, H, W, int(relu))
 
 
 def stem_conv7x7(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: torch.Tensor, N: int, H: int, W: int,
@@ -393,7 +400,7 @@ def stem_conv7x7(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: torch
     if x.numel() != N * 3 * H * W or w_packed.numel() != 148 * 64 or y.numel() < N * Ho * Wo * 64:
         raise BevfError("stem: buffer sizes do not match N,H,W")
     fn = "bevf_stem_conv7x7_f32" if y.dtype == torch.float32 else "bevf_stem_conv7x7_bf16out"
-    _check(getattr(lib(), fn)(_pc(x), _pc(w_packed), _pc(scale), _pc(shift), _p(y, y.dtype), N, H, W, int(relu), _stream()), fn)
+    _call(fn, _pc(x), _pc(w_packed), _pc(scale), _pc(shift), _p(y, y.dtype), N, H, W, int(relu))
 
 
 def stem_pool(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: torch.Tensor, N: int, H: int, W: int):
@@ -402,7 +409,7 @@ def stem_pool(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: torch.Te
     Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
     if x.numel() != N * 3 * H * W or w_packed.numel() != 148 * 64 or y.numel() < N * Hp * Wp * 64:
         raise BevfError("stem_pool: buffer sizes do not match N,H,W")
-    _check(lib().bevf_stem_pool_f32(_pc(x), _pc(w_packed), _pc(scale), _pc(shift), _p(y), N, H, W, _stream()), "bevf_stem_pool_f32")
+    _call("bevf_stem_pool_f32", _pc(x), _pc(w_packed), _pc(scale), _pc(shift), _p(y), N, H, W)
 
 
 def stem_pool_bf16mma(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: torch.Tensor, N: int, H: int, W: int):
@@ -411,8 +418,8 @@ def stem_pool_bf16mma(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, y: 
     Hp, Wp = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
     if x.numel() != N * 3 * H * W or w_packed.numel() != 64 * 176 or y.numel() < N * Hp * Wp * 64:
         raise BevfError("stem_pool bf16: buffer sizes do not match N,H,W")
-    _check(lib().bevf_stem_pool_bf16mma(_pc(x), _pc(w_packed, torch.bfloat16), _pc(scale), _pc(shift), _p(y, torch.bfloat16),
-                                        N, H, W, _stream()), "bevf_stem_pool_bf16mma")
+    _call("bevf_stem_pool_bf16mma", _pc(x), _pc(w_packed, torch.bfloat16), _pc(scale), _pc(shift), _p(y, torch.bfloat16),
+          N, H, W)
 
 
 def maxpool3x3s2(x: torch.Tensor, y: torch.Tensor, N: int, H: int, W: int, Cc: int):
@@ -420,14 +427,14 @@ def maxpool3x3s2(x: torch.Tensor, y: torch.Tensor, N: int, H: int, W: int, Cc: i
     if x.numel() < N * H * W * Cc or y.numel() < N * Ho * Wo * Cc:
         raise BevfError("maxpool: buffer too small")
     fn = "bevf_maxpool3x3s2_nhwc_" + _sfx(x)
-    _check(getattr(lib(), fn)(_p(x, x.dtype), _p(y, x.dtype), N, H, W, Cc, _stream()), fn)
+    _call(fn, _p(x, x.dtype), _p(y, x.dtype), N, H, W, Cc)
 
 
 def pointwise_smallk(x, w, scale, shift, y, M: int, K: int, Cout: int, relu: bool):
     if x.numel() < M * K or w.numel() != Cout * K or y.numel() < M * Cout:
         raise BevfError("pointwise: buffer sizes do not match M,K,Cout")
     fn = "bevf_pointwise_smallk_f32" if y.dtype == torch.float32 else "bevf_pointwise_smallk_bf16out"
-    _check(getattr(lib(), fn)(_pc(x), _pc(w), _pc(scale), _pc(shift), _p(y, y.dtype), M, K, Cout, int(relu), _stream()), fn)
+    _call(fn, _pc(x), _pc(w), _pc(scale), _pc(shift), _p(y, y.dtype), M, K, Cout, int(relu))
 
 
 def pointnet_front_pack(w: torch.Tensor) -> torch.Tensor:
@@ -435,7 +442,7 @@ def pointnet_front_pack(w: torch.Tensor) -> torch.Tensor:
     cout, cin = w.shape
     w = w.detach().float().contiguous()
     wf = torch.empty(cout * cin, device=w.device)
-    _check(lib().bevf_pointnet_front_pack_f32(_p(w), _p(wf), cout, cin, _stream()), "bevf_pointnet_front_pack_f32")
+    _call("bevf_pointnet_front_pack_f32", _p(w), _p(wf), cout, cin)
     return wf
 
 
@@ -443,22 +450,21 @@ def pointnet_front(x, w1, s1, b1, w2f, s2, b2, w3f, s3, b3, y, M: int, K: int):
     if x.numel() < M * K or w1.numel() != 64 * K or w2f.numel() != 128 * 64 or w3f.numel() != 256 * 128 or y.numel() < M * 256 \
             or min(s1.numel(), b1.numel()) < 64 or min(s2.numel(), b2.numel()) < 128 or min(s3.numel(), b3.numel()) < 256:
         raise BevfError("pointnet_front: buffer sizes do not match M, K and the 64/128/256 widths")
-    _check(lib().bevf_pointnet_front_f32(_pc(x), M, K, _pc(w1), _pc(s1), _pc(b1), _pc(w2f), _pc(s2), _pc(b2), _pc(w3f), _pc(s3),
-                                         _pc(b3), _p(y), _stream()), "bevf_pointnet_front_f32")
+    _call("bevf_pointnet_front_f32", _pc(x), M, K, _pc(w1), _pc(s1), _pc(b1), _pc(w2f), _pc(s2), _pc(b2), _pc(w3f), _pc(s3),
+          _pc(b3), _p(y))
 
 
 def vfe_smallk_max(x, w, scale, shift, y, G: int, P: int, K: int, Cout: int) -> None:
     """VFELayer for K <= 16 in one pass: pointwise linear + folded BN + ReLU + max over the P rows of each group."""
     if x.numel() < G * P * K or w.numel() != Cout * K or y.numel() < G * Cout:
         raise BevfError("vfe_smallk_max: buffer sizes do not match G, P, K, Cout")
-    _check(lib().bevf_vfe_smallk_max_f32(_pc(x), _pc(w), _pc(scale), _pc(shift), _p(y), G, P, K, Cout, _stream()),
-           "bevf_vfe_smallk_max_f32")
+    _call("bevf_vfe_smallk_max_f32", _pc(x), _pc(w), _pc(scale), _pc(shift), _p(y), G, P, K, Cout)
 
 
 def group_max(x, y, G: int, P: int, Cc: int):
     if x.numel() < G * P * Cc or y.numel() < G * Cc:
         raise BevfError("group_max: buffer too small")
-    _check(lib().bevf_group_max_f32(_p(x), _p(y), G, P, Cc, _stream()), "bevf_group_max_f32")
+    _call("bevf_group_max_f32", _p(x), _p(y), G, P, Cc)
 
 
 def radar_mlp_max(x, ws: Sequence[torch.Tensor], scales, shifts, out, R: int, B: int, P: int, Cin: int,
@@ -474,46 +480,45 @@ def radar_mlp_max(x, ws: Sequence[torch.Tensor], scales, shifts, out, R: int, B:
     d.x, d.out, d.R, d.B, d.P, d.Cin = _pc(x), _p(out), R, B, P, Cin
     for i in range(4):
         d.w[i], d.scale[i], d.shift[i], d.c[i] = _pc(ws[i]), _pc(scales[i]), _pc(shifts[i]), widths[i]
-    _check(lib().bevf_radar_mlp_max_f32(C.byref(d), _stream()), "bevf_radar_mlp_max_f32")
+    _call("bevf_radar_mlp_max_f32", C.byref(d))
 
 
 def linear(x, w, bias, y, B: int, K: int, O: int, relu: bool, perm_inner: int = 0, perm_outer: int = 0):
     if x.numel() < B * K or w.numel() != O * K or y.numel() < B * O or (bias is not None and bias.numel() != O):
         raise BevfError("linear: buffer sizes do not match B,K,O")
     if w.dtype == torch.float32:
-        _check(lib().bevf_linear_f32(_p(x), _pc(w), _pc(bias), _p(y), B, K, O, int(relu), perm_inner, perm_outer,
-                                     _stream()), "bevf_linear_f32")
+        _call("bevf_linear_f32", _p(x), _pc(w), _pc(bias), _p(y), B, K, O, int(relu), perm_inner, perm_outer)
     else:
-        _check(lib().bevf_linear_bf16w(_p(x), _pc(w, BF16), _pc(bias), _p(y, y.dtype), int(y.dtype == BF16), B, K, O,
-                                       int(relu), perm_inner, perm_outer, _stream()), "bevf_linear_bf16w")
+        _call("bevf_linear_bf16w", _p(x), _pc(w, BF16), _pc(bias), _p(y, y.dtype), int(y.dtype == BF16), B, K, O,
+              int(relu), perm_inner, perm_outer)
 
 
 def cam_mean(x, y, B: int, ncam: int, P: int, Cc: int):
     if x.numel() < B * ncam * P * Cc or y.numel() < B * P * Cc:
         raise BevfError("cam_mean: buffer too small")
     fn = "bevf_cam_mean_" + _sfx(x)
-    _check(getattr(lib(), fn)(_p(x, x.dtype), _p(y, x.dtype), B, ncam, P, Cc, _stream()), fn)
+    _call(fn, _p(x, x.dtype), _p(y, x.dtype), B, ncam, P, Cc)
 
 
 def bilinear_nhwc(x, y, B: int, Hi: int, Wi: int, Cc: int, x_cs: int, Ho: int, Wo: int, y_cs: int):
     if x.numel() < (B * Hi * Wi - 1) * x_cs + Cc or y.numel() < (B * Ho * Wo - 1) * y_cs + Cc:
         raise BevfError("bilinear: buffer too small")
     fn = "bevf_bilinear_nhwc_" + _sfx(x)
-    _check(getattr(lib(), fn)(_p(x, x.dtype), _p(y, x.dtype), B, Hi, Wi, Cc, x_cs, Ho, Wo, y_cs, _stream()), fn)
+    _call(fn, _p(x, x.dtype), _p(y, x.dtype), B, Hi, Wi, Cc, x_cs, Ho, Wo, y_cs)
 
 
 def broadcast_nhwc(v, y, B: int, P: int, Cc: int, y_cs: int):
     if v.numel() < B * Cc or y.numel() < (B * P - 1) * y_cs + Cc:
         raise BevfError("broadcast: buffer too small")
     fn = "bevf_broadcast_nhwc_" + _sfx(y)
-    _check(getattr(lib(), fn)(_p(v), _p(y, y.dtype), B, P, Cc, y_cs, _stream()), fn)
+    _call(fn, _p(v), _p(y, y.dtype), B, P, Cc, y_cs)
 
 
 def expand_border_classes(small, y, B: int, Sh: int, Sw: int, Cc: int, y_cs: int):
     if small.numel() < B * 25 * Cc or y.numel() < (B * Sh * Sw - 1) * y_cs + Cc:
         raise BevfError("expand: buffer too small")
     fn = "bevf_expand_border_classes_" + _sfx(small)
-    _check(getattr(lib(), fn)(_p(small, small.dtype), _p(y, small.dtype), B, Sh, Sw, Cc, y_cs, _stream()), fn)
+    _call(fn, _p(small, small.dtype), _p(y, small.dtype), B, Sh, Sw, Cc, y_cs)
 
 
 def head_tail(hid, w, bias, outs: Sequence[torch.Tensor], B: int, P: int, hc: int, cs: Sequence[int], n_sigmoid: int):
@@ -526,23 +531,23 @@ def head_tail(hid, w, bias, outs: Sequence[torch.Tensor], B: int, P: int, hc: in
             raise BevfError("head_tail: output size wrong")
         d.out[k], d.c[k] = _pc(outs[k]), cs[k]
     fn = "bevf_head_tail_" + _sfx(hid)
-    _check(getattr(lib(), fn)(C.byref(d), _stream()), fn)
+    _call(fn, C.byref(d))
 
 
 def nchw_to_nhwc(x, y, N: int, Cc: int, P: int, y_cs: int):
     if x.numel() < N * Cc * P or y.numel() < (N * P - 1) * y_cs + Cc:
         raise BevfError("nchw_to_nhwc: buffer too small")
-    _check(lib().bevf_nchw_to_nhwc_f32(_pc(x), _p(y), N, Cc, P, y_cs, _stream()), "bevf_nchw_to_nhwc_f32")
+    _call("bevf_nchw_to_nhwc_f32", _pc(x), _p(y), N, Cc, P, y_cs)
 
 
 def nhwc_to_nchw(x, y, N: int, Cc: int, P: int, x_cs: int):
     if x.numel() < (N * P - 1) * x_cs + Cc or y.numel() < N * Cc * P:
         raise BevfError("nhwc_to_nchw: buffer too small")
-    _check(lib().bevf_nhwc_to_nchw_f32(_p(x), _pc(y), N, Cc, P, x_cs, _stream()), "bevf_nhwc_to_nchw_f32")
+    _call("bevf_nhwc_to_nchw_f32", _p(x), _pc(y), N, Cc, P, x_cs)
 
 
 def fill(y: torch.Tensor, v: float):
-    _check(lib().bevf_fill_f32(_p(y), float(v), y.numel(), _stream()), "bevf_fill_f32")
+    _call("bevf_fill_f32", _p(y), float(v), y.numel())
 
 
 def centernet_decode(pred: dict, K: int, thresh: float, voxel: float, x_min: float, y_min: float,
@@ -563,14 +568,14 @@ def centernet_decode(pred: dict, K: int, thresh: float, voxel: float, x_min: flo
                    _p(boxes), _p(scores), _p(labels, torch.int64), _p(vels), _p(count, torch.int32),
                    _p(work, torch.uint8), _p(pool_ind, torch.int64), B, Cn, H, W, K, int(true_labels),
                    int(raw_scores), thresh, voxel, x_min, y_min)
-    _check(lib().bevf_centernet_decode_f32(C.byref(d), _stream()), "bevf_centernet_decode_f32")
+    _call("bevf_centernet_decode_f32", C.byref(d))
     return boxes, scores, labels, vels, count
 
 
 def nms_keep(heat: torch.Tensor, out: torch.Tensor, planes: int, H: int, W: int):
     if heat.numel() != planes * H * W or out.numel() != planes * H * W:
         raise BevfError("nms_keep: buffer sizes do not match planes,H,W")
-    _check(lib().bevf_nms_keep_f32(_pc(heat), _pc(out), planes, H, W, _stream()), "bevf_nms_keep_f32")
+    _call("bevf_nms_keep_f32", _pc(heat), _pc(out), planes, H, W)
 
 
 def centernet_targets(boxes, labels, has_vel, out: dict, B: int, nmax: int, H: int, W: int, Cn: int,
@@ -596,18 +601,17 @@ def centernet_targets(boxes, labels, has_vel, out: dict, B: int, nmax: int, H: i
     for i in range(6):
         d.pc_range[i] = float(pc_range[i])
     d.gaussian_overlap = overlap
-    _check(lib().bevf_centernet_targets_f32(C.byref(d), _stream()), "bevf_centernet_targets_f32")
+    _call("bevf_centernet_targets_f32", C.byref(d))
 
 
-def centernet_loss(pred: dict, tgt: dict, weights) -> torch.Tensor:
+def _loss_desc(pred: dict, tgt: dict, weights, keep: list) -> LossDesc:
+    """Descriptor of CenterNetLoss's inputs (work / out left unset); the fp32 copies it makes are appended to `keep`."""
     heat = pred["heatmap"]
     B, Cn, H, W = heat.shape
     K = tgt["ind"].shape[1]
-    dev = heat.device
     if tuple(tgt["heatmap"].shape) != (B, Cn, H, W):
         raise BevfError("loss: target heatmap shape differs from the prediction")
     d = LossDesc()
-    keep = []
 
     def f32(t):
         t = t.float().contiguous()
@@ -622,13 +626,22 @@ def centernet_loss(pred: dict, tgt: dict, weights) -> torch.Tensor:
     rm = tgt["reg_mask"].to(torch.uint8).contiguous()
     if int(ind.numel()) != B * K or rm.numel() != B * K:
         raise BevfError("loss: ind / reg_mask must be (B,K)")
-    work = torch.empty(lib().bevf_centernet_loss_work_floats(), device=dev)
-    out = torch.empty(6, device=dev)
-    d.ind, d.reg_mask, d.work, d.out = _pc(ind, torch.int64), _pc(rm, torch.uint8), _pc(work), _pc(out)
+    keep += [ind, rm]
+    d.ind, d.reg_mask = _pc(ind, torch.int64), _pc(rm, torch.uint8)
     d.B, d.C, d.H, d.W, d.K = B, Cn, H, W, K
     for i in range(5):
         d.weights[i] = float(weights[i])
-    _check(lib().bevf_centernet_loss_f32(C.byref(d), _stream()), "bevf_centernet_loss_f32")
+    return d
+
+
+def centernet_loss(pred: dict, tgt: dict, weights) -> torch.Tensor:
+    keep = []
+    d = _loss_desc(pred, tgt, weights, keep)
+    dev = pred["heatmap"].device
+    work = torch.empty(lib().bevf_centernet_loss_work_floats(), device=dev)
+    out = torch.empty(6, device=dev)
+    d.work, d.out = _pc(work), _pc(out)
+    _call("bevf_centernet_loss_f32", C.byref(d))
     return out
 
 
@@ -649,8 +662,8 @@ def scatter_voxels(features: torch.Tensor, coords: torch.Tensor, grid, num_voxel
     D, H, W = (int(g) for g in grid)
     out = torch.empty(B, Cc, D, H, W, device=features.device)
     owner = torch.empty(B * D * H * W, dtype=torch.int32, device=features.device)
-    _check(lib().bevf_scatter_voxels_f32(_pc(features), _pc(coords, torch.int64), _pc(num_voxels, torch.int32),
-                                         _p(owner, torch.int32), _p(out), B, Nv, Cc, D, H, W, _stream()), "bevf_scatter_voxels_f32")
+    _call("bevf_scatter_voxels_f32", _pc(features), _pc(coords, torch.int64), _pc(num_voxels, torch.int32),
+          _p(owner, torch.int32), _p(out), B, Nv, Cc, D, H, W)
     return out
 
 
@@ -684,7 +697,7 @@ def voxelize(points: torch.Tensor, pc_range, voxel_size, max_points: int, max_vo
         d.pc_range[i] = float(pc_range[i])
     for i in range(3):
         d.voxel_size[i] = float(voxel_size[i])
-    _check(lib().bevf_voxelize_f32(C.byref(d), _stream()), "bevf_voxelize_f32")
+    _call("bevf_voxelize_f32", C.byref(d))
     return feats, coords, npts, nvox
 
 
@@ -709,8 +722,8 @@ def pillar_pfn(g: PillarGeom, w, scale, shift, Cout: int, canvas, argmax=None) -
     if argmax is not None and argmax.numel() < g.B * g.Nv * Cout:
         raise BevfError("pillar_pfn: argmax buffer smaller than B * Nv * Cout")
     bf = canvas.dtype == BF16
-    _check(lib().bevf_pillar_pfn_f32(C.byref(g), _pc(w), _pc(scale), _pc(shift), Cout, _p(canvas, canvas.dtype if bf else torch.float32),
-                                     int(bf), _p(argmax, torch.uint8), _stream()), "bevf_pillar_pfn_f32")
+    _call("bevf_pillar_pfn_f32", C.byref(g), _pc(w), _pc(scale), _pc(shift), Cout, _p(canvas, canvas.dtype if bf else torch.float32),
+          int(bf), _p(argmax, torch.uint8))
 
 
 def pillar_moments(g: PillarGeom, w, bias, gamma, beta, Cout: int, eps: float, momentum: float, running_mean, running_var, nbt,
@@ -719,10 +732,9 @@ def pillar_moments(g: PillarGeom, w, bias, gamma, beta, Cout: int, eps: float, m
     if (w.numel() != Cout * K or moments.numel() < 272 or min(mean.numel(), invstd.numel(), scale.numel(), shift.numel()) < Cout
             or work.numel() < pillar_work_bytes(Cout)):
         raise BevfError("pillar_moments: buffer sizes do not match C and Cout")
-    _check(lib().bevf_pillar_moments_f32(C.byref(g), _pc(w), _pc(bias), _pc(gamma), _pc(beta), Cout, float(eps), float(momentum),
-                                         _p(running_mean), _p(running_var), _p(nbt, torch.int64), _p(moments, torch.float64),
-                                         _p(mean), _p(invstd), _p(scale), _p(shift), _p(work, torch.uint8), _stream()),
-           "bevf_pillar_moments_f32")
+    _call("bevf_pillar_moments_f32", C.byref(g), _pc(w), _pc(bias), _pc(gamma), _pc(beta), Cout, float(eps), float(momentum),
+          _p(running_mean), _p(running_var), _p(nbt, torch.int64), _p(moments, torch.float64),
+          _p(mean), _p(invstd), _p(scale), _p(shift), _p(work, torch.uint8))
 
 
 def pillar_backward(g: PillarGeom, dcanvas, argmax, w, bias, scale, shift, mean, invstd, gamma, moments, Cout: int, frozen: bool,
@@ -731,7 +743,326 @@ def pillar_backward(g: PillarGeom, dcanvas, argmax, w, bias, scale, shift, mean,
     if (dcanvas.numel() < g.B * g.H * g.W * Cout or argmax.numel() < g.B * g.Nv * Cout or w.numel() != Cout * K
             or dw.numel() < Cout * K or min(db.numel(), dgamma.numel(), dbeta.numel()) < Cout or work.numel() < pillar_work_bytes(Cout)):
         raise BevfError("pillar_backward: buffer sizes do not match C, Cout and the canvas")
-    _check(lib().bevf_pillar_pfn_backward_f32(C.byref(g), _pc(dcanvas), _pc(argmax, torch.uint8), _pc(w), _pc(bias), _pc(scale),
-                                              _pc(shift), _pc(mean), _pc(invstd), _pc(gamma), _pc(moments, torch.float64), Cout,
-                                              int(frozen), _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(work, torch.uint8), _stream()),
-           "bevf_pillar_pfn_backward_f32")
+    _call("bevf_pillar_pfn_backward_f32", C.byref(g), _pc(dcanvas), _pc(argmax, torch.uint8), _pc(w), _pc(bias), _pc(scale),
+          _pc(shift), _pc(mean), _pc(invstd), _pc(gamma), _pc(moments, torch.float64), Cout,
+          int(frozen), _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(work, torch.uint8))
+
+
+# ---- training step --------------------------------------------------------------------------------------------------------
+
+def _need(what: str, **bufs) -> None:
+    """Each keyword = (tensor or None, the number of elements the kernel reads or writes through it)."""
+    for name, (t, n) in bufs.items():
+        if t is not None and t.numel() < n:
+            raise BevfError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+
+
+def _strided(M: int, C: int, cs: int) -> int:
+    """Elements covered by M rows of C channels at channel stride cs."""
+    return (M - 1) * cs + C
+
+
+def conv_pixtab_bytes(N: int, H: int, W: int, KH: int, KW: int, stride: int, pad: int) -> int:
+    return int(lib().bevf_conv_pixtab_bytes(N, H, W, KH, KW, stride, pad))
+
+
+def conv_pixtab(tab, N: int, H: int, W: int, KH: int, KW: int, stride: int, pad: int, x_cs: int) -> None:
+    """Tap table of conv2d_wgrad for this shape and x_cs, into int32 `tab`."""
+    _need("conv_pixtab", tab=(tab, -(-conv_pixtab_bytes(N, H, W, KH, KW, stride, pad) // 4)))
+    _call("bevf_conv_pixtab", _pc(tab, torch.int32), N, H, W, KH, KW, stride, pad, x_cs)
+
+
+def wino_wgrad_workspace_floats(N: int, H: int, W: int, Cin: int, Cout: int) -> int:
+    """0 = shape not supported by conv3x3_wgrad_wino."""
+    return int(lib().bevf_wino_wgrad_workspace_floats(N, H, W, Cin, Cout))
+
+
+def wino_wgrad_table_bytes(N: int, H: int, W: int) -> int:
+    return int(lib().bevf_wino_wgrad_table_bytes(N, H, W))
+
+
+def wino_wgrad_table(tab, N: int, H: int, W: int, x_cs: int, dy_cs: int) -> None:
+    _need("wino_wgrad_table", tab=(tab, -(-wino_wgrad_table_bytes(N, H, W) // 4)))
+    _call("bevf_wino_wgrad_table", _pc(tab, torch.int32), N, H, W, x_cs, dy_cs)
+
+
+def conv2d_wgrad(x, dy, dw, pixtab, *, N: int, H: int, W: int, Cin: int, x_cs: int, Cout: int, dy_cs: int, KH: int, KW: int,
+                 stride: int, pad: int) -> None:
+    """dw [Cout][KH][KW][Cin] += the weight gradient (fp32 atomics; dw zero-filled by the caller); pixtab from conv_pixtab."""
+    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    _need("conv2d_wgrad", x=(x, _strided(N * H * W, Cin, x_cs)), dy=(dy, _strided(N * Ho * Wo, Cout, dy_cs)), dw=(dw, Cout * KH * KW * Cin),
+          pixtab=(pixtab, -(-conv_pixtab_bytes(N, H, W, KH, KW, stride, pad) // 4)))
+    d = WgradDesc(_pc(x), _pc(dy), _pc(dw), _pc(pixtab, torch.int32), N, H, W, Cin, x_cs, Cout, dy_cs, KH, KW, stride, pad)
+    _call("bevf_conv2d_wgrad_f32", C.byref(d))
+
+
+def conv3x3_wgrad_wino(x, dy, dw, table, work, *, N: int, H: int, W: int, Cin: int, x_cs: int, Cout: int, dy_cs: int,
+                       accumulate: bool) -> None:
+    """3x3 / stride 1 / pad 1 weight gradient in the Winograd domain (deterministic); table from wino_wgrad_table, work of
+    wino_wgrad_workspace_floats floats.  accumulate: dw += instead of dw =."""
+    M = N * H * W
+    _need("conv3x3_wgrad_wino", x=(x, _strided(M, Cin, x_cs)), dy=(dy, _strided(M, Cout, dy_cs)), dw=(dw, Cout * 9 * Cin),
+          table=(table, -(-wino_wgrad_table_bytes(N, H, W) // 4)), work=(work, wino_wgrad_workspace_floats(N, H, W, Cin, Cout)))
+    d = WgradDesc(_pc(x), _pc(dy), _pc(dw), _pc(table, torch.int32), N, H, W, Cin, x_cs, Cout, dy_cs, 3, 3, 1, 1)
+    _call("bevf_conv3x3_wgrad_wino_f32", C.byref(d), _pc(work), int(accumulate))
+
+
+def zero_stuff_nhwc(dy, out, N: int, Ho: int, Wo: int, Cc: int, H: int, W: int, s: int) -> None:
+    """out [N][H][W][C] = dy [N][Ho][Wo][C] spread to every s-th row and column, zeros in between."""
+    _need("zero_stuff_nhwc", dy=(dy, N * Ho * Wo * Cc), out=(out, N * H * W * Cc))
+    _call("bevf_zero_stuff_nhwc_f32", _pc(dy), _pc(out), N, Ho, Wo, Cc, H, W, s)
+
+
+def interleave2x2_nhwc(cls: Sequence[Optional[torch.Tensor]], hq: Sequence[int], wq: Sequence[int], dx, N: int, H: int, W: int,
+                       Cc: int) -> None:
+    """dx [N][H][W][C] from the four input-parity classes cls[q] [N][hq[q]][wq[q]][C] (None = zeros)."""
+    for q in range(4):
+        _need("interleave2x2_nhwc", **{f"cls[{q}]": (cls[q], N * hq[q] * wq[q] * Cc)})
+    _need("interleave2x2_nhwc", dx=(dx, N * H * W * Cc))
+    ptrs = (C.c_void_p * 4)(*[_pc(c) for c in cls])
+    _call("bevf_interleave2x2_nhwc_f32", ptrs, (C.c_int32 * 4)(*hq), (C.c_int32 * 4)(*wq), _pc(dx), N, H, W, Cc)
+
+
+def stem_wgrad(x, dy, dw, N: int, H: int, W: int) -> None:
+    """dw [64][160] += the 7x7 / stride-2 stem's weight gradient; x planar [N][3][H][W], dy [N][Ho][Wo][64]."""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    _need("stem_wgrad", x=(x, N * 3 * H * W), dy=(dy, N * Ho * Wo * 64), dw=(dw, 64 * 160))
+    _call("bevf_stem_wgrad_f32", _pc(x), _pc(dy), _pc(dw), N, H, W)
+
+
+def smallk_wgrad(dy, x, dw, M: int, K: int, Cout: int) -> None:
+    _need("smallk_wgrad", dy=(dy, M * Cout), x=(x, M * K), dw=(dw, Cout * K))
+    _call("bevf_smallk_wgrad_f32", _pc(dy), _pc(x), _pc(dw), M, K, Cout)
+
+
+def bn_work_floats(Cc: int) -> int:
+    return int(lib().bevf_bn_work_floats(Cc))
+
+
+def bn_stats(x, work, mean, var, invstd, M: int, Cc: int, cs: int, eps: float) -> None:
+    _need("bn_stats", x=(x, _strided(M, Cc, cs)), work=(work, bn_work_floats(Cc)), mean=(mean, Cc), var=(var, Cc), invstd=(invstd, Cc))
+    _call("bevf_bn_stats_f32", _pc(x), _pc(work), _pc(mean), _pc(var), _pc(invstd), M, Cc, cs, float(eps))
+
+
+def bn_stats_from_partials(part, G: int, pivot, mean, var, invstd, M: int, Cc: int, eps: float) -> None:
+    _need("bn_stats_from_partials", part=(part, G * Cc * 2), pivot=(pivot, Cc), mean=(mean, Cc), var=(var, Cc), invstd=(invstd, Cc))
+    _call("bevf_bn_stats_from_partials_f32", _pc(part), G, _pc(pivot), _pc(mean), _pc(var), _pc(invstd), M, Cc, float(eps))
+
+
+def bn_apply(x, mean, invstd, gamma, beta, res, y, M: int, Cc: int, cs: int, relu: bool) -> None:
+    n = _strided(M, Cc, cs)
+    _need("bn_apply", x=(x, n), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc), beta=(beta, Cc), res=(res, n), y=(y, n))
+    _call("bevf_bn_apply_f32", _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(beta), _pc(res), _pc(y), M, Cc, cs, int(relu))
+
+
+def bn_update_running(mean, var, running_mean, running_var, num_batches_tracked, Cc: int, M: int, momentum: float) -> None:
+    """torch's train-mode running-buffer update.  The buffers are written through raw pointers: the caller bumps their versions."""
+    _need("bn_update_running", mean=(mean, Cc), var=(var, Cc), running_mean=(running_mean, Cc), running_var=(running_var, Cc),
+          num_batches_tracked=(num_batches_tracked, 1))
+    _call("bevf_bn_update_running_f32", _pc(mean), _pc(var), _pc(running_mean), _pc(running_var),
+          _pc(num_batches_tracked, torch.int64), Cc, M, float(momentum))
+
+
+def bn_backward(dy, y, x, mean, invstd, gamma, beta, work, dgamma, dbeta, dx, M: int, Cc: int, cs: int, *, relu: bool = False,
+                has_res: bool = False, frozen: bool = False) -> None:
+    """BatchNorm(+ReLU) backward.  relu and has_res: dy is masked with the forward output y in place; relu alone: the mask is
+    recomputed from x (y unused, dy untouched).  frozen: the statistics were the running buffers.  dx None: only the sums
+    (no relu, x / mean / invstd may be None: column sums of dy into dbeta)."""
+    mode = ((1 if has_res else 2) if relu else 0) | (4 if frozen else 0)
+    y = y if mode & 3 == 1 else None
+    n = _strided(M, Cc, cs)
+    _need("bn_backward", dy=(dy, n), y=(y, n), x=(x, n), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc), beta=(beta, Cc),
+          work=(work, bn_work_floats(Cc)), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc), dx=(dx, n))
+    _call("bevf_bn_backward_f32", _pc(dy), _pc(y), _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(beta), _pc(work), _pc(dgamma),
+          _pc(dbeta), _pc(dx), M, Cc, cs, mode)
+
+
+def bn_backward_from_partials(dy, x, mean, invstd, gamma, part, G: int, dgamma, dbeta, dx, M: int, Cc: int, cs: int) -> None:
+    n = _strided(M, Cc, cs)
+    _need("bn_backward_from_partials", dy=(dy, n), x=(x, n), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc),
+          part=(part, G * Cc * 2), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc), dx=(dx, n))
+    _call("bevf_bn_backward_from_partials_f32", _pc(dy), _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(part), G, _pc(dgamma),
+          _pc(dbeta), _pc(dx), M, Cc, cs)
+
+
+def pool_bn_backward(dpool, idx, x, mean, invstd, gamma, beta, work, dgamma, dbeta, dx, N: int, H: int, W: int, Cc: int) -> None:
+    """BatchNorm + ReLU backward whose dY is the 3x3 / stride-2 max-pool's backward of dpool (idx from maxpool3x3s2_idx)."""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    n, npool = N * H * W * Cc, N * Ho * Wo * Cc
+    _need("pool_bn_backward", dpool=(dpool, npool), idx=(idx, npool), x=(x, n), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc),
+          beta=(beta, Cc), work=(work, bn_work_floats(Cc)), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc), dx=(dx, n))
+    _call("bevf_pool_bn_backward_f32", _pc(dpool), _pc(idx, torch.uint8), _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(beta),
+          _pc(work), _pc(dgamma), _pc(dbeta), _pc(dx), N, H, W, Cc)
+
+
+def bn_relu_maxpool3x3s2_idx(x, mean, invstd, gamma, beta, y, idx, N: int, H: int, W: int, Cc: int) -> None:
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    npool = N * Ho * Wo * Cc
+    _need("bn_relu_maxpool3x3s2_idx", x=(x, N * H * W * Cc), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc), beta=(beta, Cc),
+          y=(y, npool), idx=(idx, npool))
+    _call("bevf_bn_relu_maxpool3x3s2_idx_f32", _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(beta), _pc(y), _pc(idx, torch.uint8),
+          N, H, W, Cc)
+
+
+def group_max_idx_work_bytes(G: int, P: int, Cc: int) -> int:
+    return int(lib().bevf_group_max_idx_work_bytes(G, P, Cc))
+
+
+def bn_relu_group_max_idx(x, mean, invstd, gamma, beta, y, idx, work, G: int, P: int, Cc: int) -> None:
+    _need("bn_relu_group_max_idx", x=(x, G * P * Cc), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc), beta=(beta, Cc),
+          y=(y, G * Cc), idx=(idx, G * Cc), work=(work, group_max_idx_work_bytes(G, P, Cc)))
+    _call("bevf_bn_relu_group_max_idx_f32", _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(beta), _pc(y), _pc(idx, torch.int32),
+          _pc(work, torch.uint8), G, P, Cc)
+
+
+def gmax_bn_backward(dg, gmax, idx, x, mean, invstd, gamma, dgm, dgamma, dbeta, dx, B: int, P: int, Cc: int, cs: int) -> None:
+    n = _strided(B * P, Cc, cs)
+    _need("gmax_bn_backward", dg=(dg, B * Cc), gmax=(gmax, B * Cc), idx=(idx, B * Cc), x=(x, n), mean=(mean, Cc), invstd=(invstd, Cc),
+          gamma=(gamma, Cc), dgm=(dgm, B * Cc), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc), dx=(dx, n))
+    _call("bevf_gmax_bn_backward_f32", _pc(dg), _pc(gmax), _pc(idx, torch.int32), _pc(x), _pc(mean), _pc(invstd), _pc(gamma), _pc(dgm),
+          _pc(dgamma), _pc(dbeta), _pc(dx), B, P, Cc, cs)
+
+
+def gmax_bn_sums(dg, gmax, idx, x, mean, invstd, dgm, dgamma, dbeta, B: int, P: int, Cc: int, cs: int) -> None:
+    _need("gmax_bn_sums", dg=(dg, B * Cc), gmax=(gmax, B * Cc), idx=(idx, B * Cc), x=(x, _strided(B * P, Cc, cs)), mean=(mean, Cc),
+          invstd=(invstd, Cc), dgm=(dgm, B * Cc), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc))
+    _call("bevf_gmax_bn_sums_f32", _pc(dg), _pc(gmax), _pc(idx, torch.int32), _pc(x), _pc(mean), _pc(invstd), _pc(dgm), _pc(dgamma),
+          _pc(dbeta), B, P, Cc, cs)
+
+
+def maxpool3x3s2_idx(x, y, idx, N: int, H: int, W: int, Cc: int) -> None:
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    _need("maxpool3x3s2_idx", x=(x, N * H * W * Cc), y=(y, N * Ho * Wo * Cc), idx=(idx, N * Ho * Wo * Cc))
+    _call("bevf_maxpool3x3s2_idx_f32", _pc(x), _pc(y), _pc(idx, torch.uint8), N, H, W, Cc)
+
+
+def maxpool3x3s2_bwd(dy, idx, dx, N: int, H: int, W: int, Cc: int) -> None:
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    _need("maxpool3x3s2_bwd", dy=(dy, N * Ho * Wo * Cc), idx=(idx, N * Ho * Wo * Cc), dx=(dx, N * H * W * Cc))
+    _call("bevf_maxpool3x3s2_bwd_f32", _pc(dy), _pc(idx, torch.uint8), _pc(dx), N, H, W, Cc)
+
+
+def group_max_idx(x, y, idx, work, G: int, P: int, Cc: int) -> None:
+    """y / idx [G][C] = max and first argmax row over the P rows of each group of x [G][P][C]."""
+    _need("group_max_idx", x=(x, G * P * Cc), y=(y, G * Cc), idx=(idx, G * Cc), work=(work, group_max_idx_work_bytes(G, P, Cc)))
+    _call("bevf_group_max_idx_f32", _pc(x), _pc(y), _pc(idx, torch.int32), _pc(work, torch.uint8), G, P, Cc)
+
+
+def group_max_bwd(dy, idx, dx, G: int, P: int, Cc: int) -> None:
+    """dx [G][P][C] (zero-filled by the caller) gets dy [G][C] at the argmax rows."""
+    _need("group_max_bwd", dy=(dy, G * Cc), idx=(idx, G * Cc), dx=(dx, G * P * Cc))
+    _call("bevf_group_max_bwd_f32", _pc(dy), _pc(idx, torch.int32), _pc(dx), G, P, Cc)
+
+
+def sparse_rows_wgrad(S, idx, A, out, G: int, P: int, Cc: int, K: int) -> None:
+    _need("sparse_rows_wgrad", S=(S, G * Cc), idx=(idx, G * Cc), A=(A, G * P * K), out=(out, Cc * K))
+    _call("bevf_sparse_rows_wgrad_f32", _pc(S), _pc(idx, torch.int32), _pc(A), _pc(out), G, P, Cc, K)
+
+
+def sparse_rows_scatter_add(S, idx, Wt, dA, G: int, P: int, Cc: int, K: int) -> None:
+    _need("sparse_rows_scatter_add", S=(S, G * Cc), idx=(idx, G * Cc), W=(Wt, Cc * K), dA=(dA, G * P * K))
+    _call("bevf_sparse_rows_scatter_add_f32", _pc(S), _pc(idx, torch.int32), _pc(Wt), _pc(dA), G, P, Cc, K)
+
+
+def bilinear_bwd_nhwc(dy, dx, B: int, Hi: int, Wi: int, Cc: int, x_cs: int, Ho: int, Wo: int, y_cs: int) -> None:
+    """Backward of bilinear_nhwc; dx zero-filled by the caller."""
+    _need("bilinear_bwd_nhwc", dy=(dy, _strided(B * Ho * Wo, Cc, y_cs)), dx=(dx, _strided(B * Hi * Wi, Cc, x_cs)))
+    _call("bevf_bilinear_bwd_nhwc_f32", _pc(dy), _pc(dx), B, Hi, Wi, Cc, x_cs, Ho, Wo, y_cs)
+
+
+def cam_mean_bwd(dy, dx, B: int, ncam: int, P: int, Cc: int) -> None:
+    _need("cam_mean_bwd", dy=(dy, B * P * Cc), dx=(dx, B * ncam * P * Cc))
+    _call("bevf_cam_mean_bwd_f32", _pc(dy), _pc(dx), B, ncam, P, Cc)
+
+
+def _n4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def relu_mask(dy, y, n: int) -> None:
+    """dy *= (y > 0) over the first n elements; the kernel works in fours, so both buffers must hold n rounded up to 4."""
+    n4 = _n4(n)
+    _need("relu_mask", dy=(dy, n4), y=(y, n4))
+    _call("bevf_relu_mask_f32", _pc(dy), _pc(y), n4)
+
+
+def add_inplace(y, x, n: int) -> None:
+    """y += x over the first n elements; both buffers must hold n rounded up to 4."""
+    n4 = _n4(n)
+    _need("add_inplace", y=(y, n4), x=(x, n4))
+    _call("bevf_add_inplace_f32", _pc(y), _pc(x), n4)
+
+
+def linear_bwd_work_floats(B: int, K: int, O: int) -> int:
+    return int(lib().bevf_linear_bwd_work_floats(B, K, O))
+
+
+def linear_bwd(dy, x, w, dx, dw, db, work, B: int, K: int, O: int, perm_inner: int = 0, perm_outer: int = 0) -> None:
+    """Backward of linear (dy in the forward's stored order); dx None: weight and bias gradients only."""
+    _need("linear_bwd", dy=(dy, B * O), x=(x, B * K), w=(w, O * K), dx=(dx, B * K), dw=(dw, O * K), db=(db, O),
+          work=(work, linear_bwd_work_floats(B, K, O)))
+    _call("bevf_linear_bwd_f32", _pc(dy), _pc(x), _pc(w), _pc(dx), _pc(dw), _pc(db), _pc(work), B, K, O, perm_inner, perm_outer)
+
+
+def head_tail_bwd(hid, w, out0, douts: Sequence[torch.Tensor], dhid, dw, db, B: int, P: int, hc: int, cs: Sequence[int],
+                  n_sigmoid: int) -> None:
+    """Backward of head_tail: douts[k] (B, cs[k], H, W) -> dhid [B*P][5*hc], dw / db (zero-filled by the caller)."""
+    ctot = sum(cs)
+    _need("head_tail_bwd", hid=(hid, B * P * 5 * hc), w=(w, ctot * hc), out0=(out0, B * cs[0] * P), dhid=(dhid, B * P * 5 * hc),
+          dw=(dw, ctot * hc), db=(db, ctot))
+    for k in range(5):
+        _need("head_tail_bwd", **{f"douts[{k}]": (douts[k], B * cs[k] * P)})
+    d = HeadBwdDesc()
+    d.hid, d.w, d.out0 = _pc(hid), _pc(w), _pc(out0)
+    for k in range(5):
+        d.dout[k], d.c[k] = _pc(douts[k]), cs[k]
+    d.dhid, d.dw, d.db, d.B, d.P, d.hc, d.n_sigmoid = _pc(dhid), _pc(dw), _pc(db), B, P, hc, n_sigmoid
+    _call("bevf_head_tail_bwd_f32", C.byref(d))
+
+
+def centernet_loss_bwd(pred: dict, tgt: dict, weights, dpred: Sequence[torch.Tensor], scratch) -> None:
+    """d total_loss / d predictions into dpred (heatmap, offset, size, rot, vel; zero-filled by the caller); scratch: 2 floats."""
+    names = ("heatmap", "offset", "size", "rot", "vel")
+    for k, name in enumerate(names):
+        _need("centernet_loss_bwd", **{f"dpred[{k}]": (dpred[k], pred[name].numel())})
+    _need("centernet_loss_bwd", scratch=(scratch, 2))
+    keep = []
+    d = _loss_desc(pred, tgt, weights, keep)
+    arr = (C.c_void_p * 5)(*[_pc(t) for t in dpred])
+    _call("bevf_centernet_loss_bwd_f32", C.byref(d), arr, _pc(scratch))
+
+
+def grad_norm(g, work, max_norm: float, out) -> None:
+    """out = {L2 norm of g, min(1, max_norm / (norm + 1e-6))}; work: 512 doubles."""
+    _need("grad_norm", work=(work, 512), out=(out, 2))
+    _call("bevf_grad_norm_f32", _pc(g), g.numel(), _pc(work, torch.float64), float(max_norm), _pc(out))
+
+
+def adamw_step(p, g, m, v, clip, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int) -> None:
+    """One AdamW step over the g.numel() leading elements of p / m / v; clip (optional): grad_norm's out, scales g by clip[1]."""
+    n = g.numel()
+    _need("adamw_step", p=(p, n), m=(m, n), v=(v, n), clip=(clip, 2))
+    _call("bevf_adamw_step_f32", _pc(p), _pc(g), _pc(m), _pc(v), _pc(clip), n, float(lr), float(beta1), float(beta2), float(eps),
+          float(weight_decay), int(step))
+
+
+# ---- input pipeline -------------------------------------------------------------------------------------------------------
+
+def resize_normalize_u8(x, out, n: int, H: int, W: int, Ho: int, Wo: int, bounds_h, coef_h, ksize_h: int, bounds_v, coef_v,
+                        ksize_v: int, mean: Sequence[float], std: Sequence[float]) -> None:
+    """uint8 [n][H][W][3] -> fp32 planar [n][3][Ho][Wo] (Pillow-identical resize, then (x/255 - mean) / std); bounds / coef:
+    int32 per-axis tables of preprocess.resample_tables."""
+    _need("resize_normalize_u8", x=(x, n * H * W * 3), out=(out, n * 3 * Ho * Wo), bounds_h=(bounds_h, Wo * 2),
+          coef_h=(coef_h, Wo * ksize_h), bounds_v=(bounds_v, Ho * 2), coef_v=(coef_v, Ho * ksize_v))
+    _call("bevf_resize_normalize_u8", _pc(x, torch.uint8), _pc(out), n, H, W, Ho, Wo, _pc(bounds_h, torch.int32),
+          _pc(coef_h, torch.int32), ksize_h, _pc(bounds_v, torch.int32), _pc(coef_v, torch.int32), ksize_v,
+          (C.c_float * 3)(*mean), (C.c_float * 3)(*std))
+
+
+def lidar_filter_pad(points, out, count, work, choice, N: int, Cc: int, max_points: int, pc_range: Sequence[float]) -> None:
+    """One sweep [N][C] -> the in-range points, in order, zero-padded (or picked by `choice`, max_points int64) to out
+    [max_points][C]; count: 1 int32; work: N*C + ceil(N / 1024) floats."""
+    _need("lidar_filter_pad", points=(points, N * Cc), out=(out, max_points * Cc), count=(count, 1),
+          work=(work, N * Cc + -(-N // 1024)), choice=(choice, max_points))
+    _call("bevf_lidar_filter_pad_f32", _pc(points), _pc(out), _pc(count, torch.int32), _pc(work), _pc(choice, torch.int64), N, Cc,
+          max_points, (C.c_float * 6)(*pc_range))

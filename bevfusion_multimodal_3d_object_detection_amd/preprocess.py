@@ -14,7 +14,6 @@
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence, Tuple
 
@@ -91,11 +90,7 @@ def preprocess_camera_images(imgs: torch.Tensor, size: Tuple[int, int] = (448, 8
     out = torch.empty(n, 3, Ho, Wo, device=x.device)
     bh, kh, ksh = _tables(W, Wo, x.device)
     bv, kv, ksv = _tables(H, Ho, x.device)
-    m = (C.c_float * 3)(*mean)
-    s = (C.c_float * 3)(*std)
-    L._check(L.lib().bevf_resize_normalize_u8(x.data_ptr(), out.data_ptr(), n, H, W, Ho, Wo, bh.data_ptr(), kh.data_ptr(),
-                                              ksh, bv.data_ptr(), kv.data_ptr(), ksv, m, s, L._stream()),
-             "bevf_resize_normalize_u8")
+    L.resize_normalize_u8(x, out, n, H, W, Ho, Wo, bh, kh, ksh, bv, kv, ksv, mean, std)
     return out.reshape(*lead, 3, Ho, Wo)
 
 
@@ -113,13 +108,10 @@ def filter_pad_lidar(points: torch.Tensor, max_points: int = 35000,
     out = torch.empty(max_points, Cc, device=pts.device)
     count = torch.zeros(1, dtype=torch.int32, device=pts.device)
     work = torch.empty(max(N, 1) * Cc + (N + 1023) // 1024 + 64, device=pts.device)
-    r = (C.c_float * 6)(*pc_range)
     ch = None
     if choice is not None:
         if choice.numel() != max_points:
             raise L.BevfError("filter_pad_lidar: `choice` must hold max_points indices")
         ch = choice.to(device=pts.device, dtype=torch.int64).contiguous()
-    L._check(L.lib().bevf_lidar_filter_pad_f32(pts.data_ptr(), out.data_ptr(), count.data_ptr(), work.data_ptr(),
-                                               None if ch is None else ch.data_ptr(), N, Cc, max_points, r, L._stream()),
-             "bevf_lidar_filter_pad_f32")
+    L.lidar_filter_pad(pts, out, count, work, ch, N, Cc, max_points, pc_range)
     return out, count[0]

@@ -10,7 +10,6 @@ allocation and for weight layout permutes; no torch compute op touches an activa
 """
 from __future__ import annotations
 
-import ctypes as C
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
@@ -21,21 +20,9 @@ from . import _lib as L
 from . import engine as E
 
 
-def _lib():
-    return L.lib()
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ck(rc, what):
-    if rc != 0:
-        raise L.BevfError(f"{what} failed ({rc}): {_lib().bevf_last_error().decode()}")
-
-
 def _new(n: int, dev, dtype=torch.float32) -> torch.Tensor:
-    return torch.empty(max(int(n), 4), dtype=dtype, device=dev)
+    """Uninitialised flat buffer of at least n elements, rounded up to a multiple of 4 (the elementwise kernels work in fours)."""
+    return torch.empty(max((int(n) + 3) // 4 * 4, 4), dtype=dtype, device=dev)
 
 
 class _ZeroPool:
@@ -59,7 +46,7 @@ _ZPOOL: Optional[_ZeroPool] = None
 
 
 def _zeros(n: int, dev, dtype=torch.float32) -> torch.Tensor:
-    n = max(int(n), 4)
+    n = max((int(n) + 3) // 4 * 4, 4)                          # rounded up like _new
     if _ZPOOL is not None and dtype == torch.float32 and _ZPOOL.buf.device == torch.device(dev):
         t = _ZPOOL.take(n)
         if t is not None:
@@ -74,8 +61,8 @@ def _pixtab(N, H, W, k, stride, pad, x_cs, dev) -> torch.Tensor:
     key = (N, H, W, k, stride, pad, x_cs, str(dev))
     t = _PIXTAB.get(key)
     if t is None:
-        t = torch.empty(_lib().bevf_conv_pixtab_bytes(N, H, W, k, k, stride, pad) // 4, dtype=torch.int32, device=dev)
-        _ck(_lib().bevf_conv_pixtab(t.data_ptr(), N, H, W, k, k, stride, pad, x_cs, _st()), "bevf_conv_pixtab")
+        t = torch.empty(L.conv_pixtab_bytes(N, H, W, k, k, stride, pad) // 4, dtype=torch.int32, device=dev)
+        L.conv_pixtab(t, N, H, W, k, k, stride, pad, x_cs)
         _PIXTAB[key] = t
     return t
 
@@ -85,8 +72,8 @@ def _wino_wgrad_table(N, H, W, x_cs, dy_cs, dev) -> torch.Tensor:
     key = ("wwtab", N, H, W, x_cs, dy_cs, str(dev))
     t = _PIXTAB.get(key)
     if t is None:
-        t = torch.empty(_lib().bevf_wino_wgrad_table_bytes(N, H, W) // 4, dtype=torch.int32, device=dev)
-        _ck(_lib().bevf_wino_wgrad_table(t.data_ptr(), N, H, W, x_cs, dy_cs, _st()), "bevf_wino_wgrad_table")
+        t = torch.empty(L.wino_wgrad_table_bytes(N, H, W) // 4, dtype=torch.int32, device=dev)
+        L.wino_wgrad_table(t, N, H, W, x_cs, dy_cs)
         _PIXTAB[key] = t
     return t
 
@@ -133,7 +120,7 @@ def conv_raw(x, w_ohwi, bias, N, H, W, cin, cout, k, stride, pad, relu=False, bn
     fuse = bn_pivot is not None and not relu and _wino_ok(cin, k, stride, pad)
     part, rows = None, 0
     if fuse:
-        rows_of = lambda n: _lib().bevf_wino_stat_rows(n, H, W)
+        rows_of = lambda n: L.wino_stat_rows(n, H, W)
         G = sum(rows_of(min(per, N - i0)) for i0 in range(0, N, per))
         part = _new(G * cout * 2, x.device)
     for i0 in range(0, N, per):
@@ -166,24 +153,21 @@ def conv_wgrad(x, dy, N, H, W, cin, cout, k, stride, pad, dw=None) -> torch.Tens
             conv_wgrad(x[i0 * H * W * cin:], dy[i0 * Ho * Wo * cout:], n, H, W, cin, cout, k, stride, pad, dw=dw)
         return dw[:cout * k * k * cin].view(cout, k, k, cin)
     flops = 2.0 * N * Ho * Wo * cout * k * k * cin
-    ws = (_lib().bevf_wino_wgrad_workspace_floats(N, H, W, cin, cout)
+    ws = (L.wino_wgrad_workspace_floats(N, H, W, cin, cout)
           if WINO_WGRAD and E.conv_mode() in ("wino", "wino_x3") and (k, stride, pad) == (3, 1, 1) else 0)
     if ws:
         if fresh:
             dw = _new(cout * 9 * cin, x.device)
-        d = L.WgradDesc(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _wino_wgrad_table(N, H, W, cin, cout, x.device).data_ptr(),
-                        N, H, W, cin, cin, cout, cout, 3, 3, 1, 1)
+        table = _wino_wgrad_table(N, H, W, cin, cout, x.device)
         work = _new(ws, x.device)
         with E._span("conv_wgrad_wino_f32", flops=flops):
-            _ck(_lib().bevf_conv3x3_wgrad_wino_f32(C.byref(d), work.data_ptr(), 0 if fresh else 1, _st()),
-                "bevf_conv3x3_wgrad_wino_f32")
+            L.conv3x3_wgrad_wino(x, dy, dw, table, work, N=N, H=H, W=W, Cin=cin, x_cs=cin, Cout=cout, dy_cs=cout, accumulate=not fresh)
         return dw[:cout * 9 * cin].view(cout, 3, 3, cin)
     if fresh:
         dw = _zeros(cout * k * k * cin, x.device)
-    d = L.WgradDesc(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), _pixtab(N, H, W, k, stride, pad, cin, x.device).data_ptr(),
-                    N, H, W, cin, cin, cout, cout, k, k, stride, pad)
+    pixtab = _pixtab(N, H, W, k, stride, pad, cin, x.device)
     with E._span("conv_wgrad_f32", flops=flops):
-        _ck(_lib().bevf_conv2d_wgrad_f32(C.byref(d), _st()), "bevf_conv2d_wgrad_f32")
+        L.conv2d_wgrad(x, dy, dw, pixtab, N=N, H=H, W=W, Cin=cin, x_cs=cin, Cout=cout, dy_cs=cout, KH=k, KW=k, stride=stride, pad=pad)
     return dw[:cout * k * k * cin].view(cout, k, k, cin)
 
 
@@ -232,8 +216,7 @@ def conv_dgrad(dy, weight_oihw, N, H, W, cin, cout, k, stride, pad, add=None, bn
                 cls, hq, wq = [c00, None, None, None], [h0, 0, 0, 0], [w0, 0, 0, 0]
             else:
                 src = _new(N * (Ho + 1) * (Wo + 1) * cout, dy.device)                      # dy with a zero row / column appended
-                _ck(_lib().bevf_zero_stuff_nhwc_f32(dy.data_ptr(), src.data_ptr(), N, Ho, Wo, cout, Ho + 1, Wo + 1, 1, _st()),
-                    "bevf_zero_stuff_nhwc_f32")
+                L.zero_stuff_nhwc(dy, src, N, Ho, Wo, cout, Ho + 1, Wo + 1, 1)
                 taps = ([1], [2, 0])                                                       # parity 0: kh=1 reads dy[a]; parity 1: kh=2 reads dy[a], kh=0 reads dy[a+1]
                 cls, hq, wq = [], [], []
                 for ph in (0, 1):
@@ -241,16 +224,13 @@ def conv_dgrad(dy, weight_oihw, N, H, W, cin, cout, k, stride, pad, add=None, bn
                         sub = w[:, :, taps[ph]][:, :, :, taps[pw]]
                         c, hc, wc = _dgrad_conv(src, sub, N, Ho + 1, Wo + 1, cin, cout, len(taps[ph]), len(taps[pw]))
                         cls.append(c); hq.append(hc); wq.append(wc)
-            ptrs = (C.c_void_p * 4)(*[None if c is None else c.data_ptr() for c in cls])
-            _ck(_lib().bevf_interleave2x2_nhwc_f32(ptrs, (C.c_int32 * 4)(*hq), (C.c_int32 * 4)(*wq), dx.data_ptr(), N, H, W, cin,
-                                                   _st()), "bevf_interleave2x2_nhwc_f32")
+            L.interleave2x2_nhwc(cls, hq, wq, dx, N, H, W, cin)
         return dx
     wt = w.flip(2, 3).permute(1, 2, 3, 0).contiguous().view(-1)                          # [cin][k][k][cout]
     src, sh, sw = dy, Ho, Wo
     if stride != 1:
         src = _new(N * H * W * cout, dy.device)
-        _ck(_lib().bevf_zero_stuff_nhwc_f32(dy.data_ptr(), src.data_ptr(), N, Ho, Wo, cout, H, W, stride, _st()),
-            "bevf_zero_stuff_nhwc_f32")
+        L.zero_stuff_nhwc(dy, src, N, Ho, Wo, cout, H, W, stride)
         sh, sw = H, W
     else:
         assert (Ho, Wo) == (H, W), "stride-1 convs on this path keep the spatial size"
@@ -260,7 +240,7 @@ def conv_dgrad(dy, weight_oihw, N, H, W, cin, cout, k, stride, pad, add=None, bn
         if wino:
             part = None
             if bnb is not None:
-                G = _lib().bevf_wino_stat_rows(N, sh, sw)
+                G = L.wino_stat_rows(N, sh, sw)
                 part = _new(G * cin * 2, dy.device)
             L.conv3x3_wino(src, L.wino_filter_transform(wt, cin, cout), None, None, dx, N=N, H=sh, W=sw, Cin=cout, x_cs=cout,
                            Cout=cin, y_cs=cin, relu=False, res=add, res_cs=cin if add is not None else 0, stats=part, bnb=bnb)
@@ -316,17 +296,13 @@ def bn_train_forward(xraw, bn: nn.BatchNorm2d, M: int, Cc: int, res=None, relu=T
     dev = xraw.device
     if bn_is_frozen(bn):
         # eval-mode BatchNorm inside a module that trains (mixed mode): the running buffers are the statistics, nothing is updated, and
-        # the backward treats them as constants (bevf_bn_backward_f32, relu | 4).  Channel-sized torch arithmetic only.
+        # the backward treats them as constants (bn_backward(frozen=True)).  Channel-sized torch arithmetic only.
         mean = bn.running_mean.detach().float().contiguous()
         invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps).contiguous()
         y = None
         if apply:
             y = _new(M * Cc, dev)
-            g = bn.weight.data_ptr() if bn.weight is not None else None
-            b = bn.bias.data_ptr() if bn.bias is not None else None
-            _ck(_lib().bevf_bn_apply_f32(xraw.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g, b,
-                                         res.data_ptr() if res is not None else None, y.data_ptr(), M, Cc, Cc, int(relu), _st()),
-                "bevf_bn_apply_f32")
+            L.bn_apply(xraw, mean, invstd, bn.weight, bn.bias, res, y, M, Cc, Cc, relu)
             if relu:
                 _trace_relu(y, M, Cc)
         s = _BNState()
@@ -336,20 +312,14 @@ def bn_train_forward(xraw, bn: nn.BatchNorm2d, M: int, Cc: int, res=None, relu=T
     if partials is not None:
         part, G, pivot = partials
         pivot = pivot.clone()                    # the running mean is updated below, in place
-        _ck(_lib().bevf_bn_stats_from_partials_f32(part.data_ptr(), G, pivot.data_ptr(), mean.data_ptr(), var.data_ptr(),
-                                                   invstd.data_ptr(), M, Cc, float(bn.eps), _st()), "bevf_bn_stats_from_partials_f32")
+        L.bn_stats_from_partials(part, G, pivot, mean, var, invstd, M, Cc, bn.eps)
     else:
-        work = _new(_lib().bevf_bn_work_floats(Cc), dev)
-        _ck(_lib().bevf_bn_stats_f32(xraw.data_ptr(), work.data_ptr(), mean.data_ptr(), var.data_ptr(), invstd.data_ptr(),
-                                     M, Cc, Cc, float(bn.eps), _st()), "bevf_bn_stats_f32")
+        work = _new(L.bn_work_floats(Cc), dev)
+        L.bn_stats(xraw, work, mean, var, invstd, M, Cc, Cc, bn.eps)
     y = None
     if apply:
         y = _new(M * Cc, dev)
-        g = bn.weight.data_ptr() if bn.weight is not None else None
-        b = bn.bias.data_ptr() if bn.bias is not None else None
-        _ck(_lib().bevf_bn_apply_f32(xraw.data_ptr(), mean.data_ptr(), invstd.data_ptr(), g, b,
-                                     res.data_ptr() if res is not None else None, y.data_ptr(), M, Cc, Cc, int(relu), _st()),
-            "bevf_bn_apply_f32")
+        L.bn_apply(xraw, mean, invstd, bn.weight, bn.bias, res, y, M, Cc, Cc, relu)
     if bn.track_running_stats and bn.running_mean is not None:           # torch: momentum 0.1, unbiased running var
         nbt = bn.num_batches_tracked
         if bn.momentum is None:
@@ -358,9 +328,7 @@ def bn_train_forward(xraw, bn: nn.BatchNorm2d, M: int, Cc: int, res=None, relu=T
             mom = 1.0 / (int(nbt.item()) + 1) if nbt is not None else 0.0
         else:
             mom = bn.momentum
-        _ck(_lib().bevf_bn_update_running_f32(mean.data_ptr(), var.data_ptr(), bn.running_mean.data_ptr(),
-                                              bn.running_var.data_ptr(), nbt.data_ptr() if nbt is not None else None, Cc, M,
-                                              float(mom), _st()), "bevf_bn_update_running_f32")
+        L.bn_update_running(mean, var, bn.running_mean, bn.running_var, nbt, Cc, M, mom)
         for t in (bn.running_mean, bn.running_var, nbt):                 # written through raw pointers: bump the versions
             if t is not None:                                             # (the engines' repack signature looks at them)
                 torch.autograd.graph.increment_version(t)
@@ -375,18 +343,12 @@ def bn_train_backward(dy, s: _BNState, bn, relu=True, need_dx=True):
     """Returns (dxraw or None, dgamma, dbeta).  Layers with a skip connection: dy <- dy*(y>0) in place (it is the skip input's
     gradient); layers without one: dy is left untouched (the mask is recomputed from the raw input in both passes)."""
     dev = dy.device
-    work = _new(_lib().bevf_bn_work_floats(s.C), dev)
+    work = _new(L.bn_work_floats(s.C), dev)
     dgamma, dbeta = _new(s.C, dev), _new(s.C, dev)
     dx = _new(s.M * s.C, dev) if need_dx else None
-    g = bn.weight.data_ptr() if bn.weight is not None else None
-    b = bn.bias.data_ptr() if bn.bias is not None else None
     # without a residual the ReLU mask is recomputed from the raw input (same fma as the forward): y is not re-read
-    ymask = s.y.data_ptr() if (relu and s.has_res) else None
-    _ck(_lib().bevf_bn_backward_f32(dy.data_ptr(), ymask, s.xraw.data_ptr(), s.mean.data_ptr(),
-                                    s.invstd.data_ptr(), g, b, work.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                    dx.data_ptr() if dx is not None else None, s.M, s.C, s.C,
-                                    ((1 if s.has_res else 2) if relu else 0) | (4 if s.frozen else 0), _st()),
-        "bevf_bn_backward_f32")
+    L.bn_backward(dy, s.y, s.xraw, s.mean, s.invstd, bn.weight, bn.bias, work, dgamma, dbeta, dx, s.M, s.C, s.C, relu=relu,
+                  has_res=s.has_res, frozen=s.frozen)
     return dx, dgamma[:s.C], dbeta[:s.C]
 
 
@@ -395,16 +357,15 @@ def group_max_with_index(a, G: int, P: int, Cc: int):
     dev = a.device
     g = _new(G * Cc, dev)
     idx = torch.empty(G * Cc, dtype=torch.int32, device=dev)
-    work = torch.empty(_lib().bevf_group_max_idx_work_bytes(G, P, Cc), dtype=torch.uint8, device=dev)
-    _ck(_lib().bevf_group_max_idx_f32(a.data_ptr(), g.data_ptr(), idx.data_ptr(), work.data_ptr(), G, P, Cc, _st()),
-        "bevf_group_max_idx_f32")
+    work = torch.empty(L.group_max_idx_work_bytes(G, P, Cc), dtype=torch.uint8, device=dev)
+    L.group_max_idx(a, g, idx, work, G, P, Cc)
     return g, idx
 
 
 def group_max_scatter(dg, idx, G: int, P: int, Cc: int):
     """Backward of group_max_with_index: a zero [G*P][Cc] gradient with dg at the winning rows."""
     d = _zeros(G * P * Cc, dg.device)
-    _ck(_lib().bevf_group_max_bwd_f32(dg.data_ptr(), idx.data_ptr(), d.data_ptr(), G, P, Cc, _st()), "bevf_group_max_bwd_f32")
+    L.group_max_bwd(dg, idx, d, G, P, Cc)
     return d
 
 
@@ -437,8 +398,7 @@ class PointFirstLayer:
     def backward(self, d, sink) -> None:
         M, Cc, c0 = self.M, self.Cc, self.c0
         if self.bn is None:
-            n4 = (M * c0 + 3) // 4 * 4
-            _ck(_lib().bevf_relu_mask_f32(d.data_ptr(), self.y.data_ptr(), n4, _st()), "bevf_relu_mask_f32")
+            L.relu_mask(d, self.y, M * c0)
             draw = d
         else:
             draw, dgamma, dbeta = bn_train_backward(d, self.bns, self.bn, relu=True)
@@ -447,8 +407,7 @@ class PointFirstLayer:
         if self.conv.bias is not None:
             sink.add(self.conv.bias, colsum(draw, M, c0))
         dw = _zeros(c0 * Cc, d.device)
-        _ck(_lib().bevf_smallk_wgrad_f32(draw.data_ptr(), self.rows.data_ptr(), dw.data_ptr(), M, Cc, c0, _st()),
-            "bevf_smallk_wgrad_f32")
+        L.smallk_wgrad(draw, self.rows, dw, M, Cc, c0)
         sink.add(self.conv.weight, dw[:c0 * Cc])
 
 
@@ -466,25 +425,20 @@ def bn_backward_from_partials(dy, s: _BNState, bn, pre):
     dev = dy.device
     dgamma, dbeta = _new(s.C, dev), _new(s.C, dev)
     dx = _new(s.M * s.C, dev)
-    g = bn.weight.data_ptr() if bn.weight is not None else None
-    _ck(_lib().bevf_bn_backward_from_partials_f32(dy.data_ptr(), s.xraw.data_ptr(), s.mean.data_ptr(), s.invstd.data_ptr(), g,
-                                                  part.data_ptr(), G, dgamma.data_ptr(), dbeta.data_ptr(), dx.data_ptr(),
-                                                  s.M, s.C, s.C, _st()), "bevf_bn_backward_from_partials_f32")
+    L.bn_backward_from_partials(dy, s.xraw, s.mean, s.invstd, bn.weight, part, G, dgamma, dbeta, dx, s.M, s.C, s.C)
     return dx, dgamma[:s.C], dbeta[:s.C]
 
 
 def colsum(dy, M, Cc):
     """sum over rows (bias gradients)."""
-    work = _new(_lib().bevf_bn_work_floats(Cc), dy.device)
+    work = _new(L.bn_work_floats(Cc), dy.device)
     out = _new(Cc, dy.device)
-    _ck(_lib().bevf_bn_backward_f32(dy.data_ptr(), None, None, None, None, None, None, work.data_ptr(), None, out.data_ptr(),
-                                    None, M, Cc, Cc, 0, _st()), "bevf_bn_backward_f32(colsum)")
+    L.bn_backward(dy, None, None, None, None, None, None, work, None, out, None, M, Cc, Cc)
     return out[:Cc]
 
 
 def add_(y, x, n):
-    n4 = (n + 3) // 4 * 4
-    _ck(_lib().bevf_add_inplace_f32(y.data_ptr(), x.data_ptr(), n4, _st()), "bevf_add_inplace_f32")
+    L.add_inplace(y, x, n)
 
 
 class GradSink:
@@ -574,19 +528,12 @@ class ConvBNLayer:
         dev = x.device
         if RELU_TRACE is not None:                               # (tests only: the activation this path never writes)
             yt = _new(M * self.cout, dev)
-            _ck(_lib().bevf_bn_apply_f32(xraw.data_ptr(), self.bns.mean.data_ptr(), self.bns.invstd.data_ptr(),
-                                         self.bn.weight.data_ptr() if self.bn.weight is not None else None,
-                                         self.bn.bias.data_ptr() if self.bn.bias is not None else None, None, yt.data_ptr(), M,
-                                         self.cout, self.cout, 1, _st()), "bevf_bn_apply_f32")
+            L.bn_apply(xraw, self.bns.mean, self.bns.invstd, self.bn.weight, self.bn.bias, None, yt, M, self.cout, self.cout, True)
             _trace_relu(yt, M, self.cout)
         g = _new(B * self.cout, dev)
         idx = torch.empty(B * self.cout, dtype=torch.int32, device=dev)
-        work = torch.empty(_lib().bevf_group_max_idx_work_bytes(B, P, self.cout), dtype=torch.uint8, device=dev)
-        gam = self.bn.weight.data_ptr() if self.bn.weight is not None else None
-        bet = self.bn.bias.data_ptr() if self.bn.bias is not None else None
-        _ck(_lib().bevf_bn_relu_group_max_idx_f32(xraw.data_ptr(), self.bns.mean.data_ptr(), self.bns.invstd.data_ptr(), gam, bet,
-                                                  g.data_ptr(), idx.data_ptr(), work.data_ptr(), B, P, self.cout, _st()),
-            "bevf_bn_relu_group_max_idx_f32")
+        work = torch.empty(L.group_max_idx_work_bytes(B, P, self.cout), dtype=torch.uint8, device=dev)
+        L.bn_relu_group_max_idx(xraw, self.bns.mean, self.bns.invstd, self.bn.weight, self.bn.bias, g, idx, work, B, P, self.cout)
         return g, idx
 
     def bnb_request(self):
@@ -608,8 +555,7 @@ class ConvBNLayer:
         d_res = None
         if self.bn is None:
             if self.relu:
-                n4 = (self.M * self.cout + 3) // 4 * 4
-                _ck(_lib().bevf_relu_mask_f32(dy.data_ptr(), self.y.data_ptr(), n4, _st()), "bevf_relu_mask_f32")
+                L.relu_mask(dy, self.y, self.M * self.cout)
             dxraw = dy
         else:
             if pre is not None:
@@ -628,17 +574,15 @@ class ConvBNLayer:
     def backward_from_groupmax(self, dg, gmax, idx, B: int, P: int, sink: GradSink):
         """Backward when this layer's output went straight into a max over the P rows of each of B groups (PointNet's
         last layer): dg / gmax / idx [B][cout].  The gradient is non-zero in one row per (group, channel), so BatchNorm's
-        sums are gathered from those entries and no dense dY is ever built (bevf_gmax_bn_backward_f32)."""
+        sums are gathered from those entries and no dense dY is ever built (L.gmax_bn_backward)."""
         assert self.bn is not None and self.relu and not self.has_res and B * P == self.M
         st, dev = self.bns, dg.device
         dgm, dgamma, dbeta = _new(B * self.cout, dev), _new(self.cout, dev), _new(self.cout, dev)
         if LOWRANK_GMAX_BACKWARD and self.k == 1 and self.cin % 4 == 0 and self.cout % 4 == 0:
             return self._backward_from_groupmax_lowrank(dg, gmax, idx, B, P, sink, dgm, dgamma, dbeta)
         dxraw = _new(self.M * self.cout, dev)
-        g = self.bn.weight.data_ptr() if self.bn.weight is not None else None
-        _ck(_lib().bevf_gmax_bn_backward_f32(dg.data_ptr(), gmax.data_ptr(), idx.data_ptr(), st.xraw.data_ptr(), st.mean.data_ptr(),
-                                             st.invstd.data_ptr(), g, dgm.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                             dxraw.data_ptr(), B, P, self.cout, self.cout, _st()), "bevf_gmax_bn_backward_f32")
+        L.gmax_bn_backward(dg, gmax, idx, st.xraw, st.mean, st.invstd, self.bn.weight, dgm, dgamma, dbeta, dxraw, B, P, self.cout,
+                           self.cout)
         sink.add(self.bn.weight, dgamma[:self.cout])
         sink.add(self.bn.bias, dbeta[:self.cout])
         return self._conv_backward(dxraw, sink, True, None)
@@ -654,9 +598,7 @@ class ConvBNLayer:
             db = colsum(S) + M beta' + kappa (W colsum(A)).
         (C = 1024, K = 512: 294 instead of 586 GFLOP, and no 1.15 GB tensor written and read twice.)"""
         st, dev, M, K, Cc = self.bns, dg.device, self.M, self.cin, self.cout
-        _ck(_lib().bevf_gmax_bn_sums_f32(dg.data_ptr(), gmax.data_ptr(), idx.data_ptr(), st.xraw.data_ptr(), st.mean.data_ptr(),
-                                         st.invstd.data_ptr(), dgm.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, P, Cc, Cc, _st()),
-            "bevf_gmax_bn_sums_f32")
+        L.gmax_bn_sums(dg, gmax, idx, st.xraw, st.mean, st.invstd, dgm, dgamma, dbeta, B, P, Cc, Cc)
         dgamma, dbeta = dgamma[:Cc], dbeta[:Cc]
         sink.add(self.bn.weight, dgamma)
         sink.add(self.bn.bias, dbeta)
@@ -675,8 +617,7 @@ class ConvBNLayer:
         gram = conv_wgrad(self.x, self.x, M, 1, 1, K, K, 1, 1, 0).reshape(K, K)
         wg, _, _ = conv_raw(W2.contiguous().view(-1), gram.contiguous().view(-1), None, Cc, 1, 1, K, K, 1, 1, 0)
         sa = _new(Cc * K, dev)                                                            # S^T A over the B*C argmax rows, frames in order
-        _ck(_lib().bevf_sparse_rows_wgrad_f32(S.data_ptr(), idx.data_ptr(), self.x.data_ptr(), sa.data_ptr(), B, P, Cc, K, _st()),
-            "bevf_sparse_rows_wgrad_f32")
+        L.sparse_rows_wgrad(S, idx, self.x, sa, B, P, Cc, K)
         dW = sa[:Cc * K].view(Cc, K) + beta_p.unsqueeze(1) * cs_a.unsqueeze(0) + kap.unsqueeze(1) * wg[:Cc * K].view(Cc, K)
         sink.add(w, dW.reshape(w.shape))
         # data gradient: A (W^T diag(kappa) W) + the row-constant term in ONE 1x1-conv launch, then the B*C sparse rows
@@ -685,8 +626,7 @@ class ConvBNLayer:
         v = (beta_p.unsqueeze(1) * W2).sum(0).contiguous()
         dA, _, _ = conv_raw(self.x, gw.contiguous().view(-1), v, M, 1, 1, K, K, 1, 1, 0)
         # + S W at the argmax rows: channels sharing a row are added by the row's first channel, in order (no atomics: reproducible)
-        _ck(_lib().bevf_sparse_rows_scatter_add_f32(S.data_ptr(), idx.data_ptr(), W2.contiguous().data_ptr(), dA.data_ptr(), B, P, Cc, K,
-                                                    _st()), "bevf_sparse_rows_scatter_add_f32")
+        L.sparse_rows_scatter_add(S, idx, W2.contiguous(), dA, B, P, Cc, K)
         return dA
 
     def _conv_backward(self, dxraw, sink: GradSink, need_dx=True, add=None, fuse_next=None):
@@ -728,14 +668,11 @@ class LinearLayer:
         O, K = w.shape
         dev = dy.device
         if self.relu:
-            n4 = (self.B * O + 3) // 4 * 4
-            _ck(_lib().bevf_relu_mask_f32(dy.data_ptr(), self.y.data_ptr(), n4, _st()), "bevf_relu_mask_f32")
+            L.relu_mask(dy, self.y, self.B * O)
         dx = _new(self.B * K, dev) if need_dx else None
         dw, db = _new(O * K, dev), _new(O, dev)
-        work = _new(_lib().bevf_linear_bwd_work_floats(self.B, K, O), dev)
-        _ck(_lib().bevf_linear_bwd_f32(dy.data_ptr(), self.x.data_ptr(), w.data_ptr(),
-                                       dx.data_ptr() if dx is not None else None, dw.data_ptr(), db.data_ptr(),
-                                       work.data_ptr(), self.B, K, O, self.perm[0], self.perm[1], _st()), "bevf_linear_bwd_f32")
+        work = _new(L.linear_bwd_work_floats(self.B, K, O), dev)
+        L.linear_bwd(dy, self.x, w, dx, dw, db, work, self.B, K, O, *self.perm)
         sink.add(self.lin.weight, dw[:O * K])
         sink.add(self.lin.bias, db[:O])
         return dx
@@ -752,8 +689,7 @@ class Bilinear:
     def backward(self, dy):
         B, Hi, Wi, Cc, Ho, Wo, y_cs = self.geom
         dx = _zeros(B * Hi * Wi * Cc, dy.device)
-        _ck(_lib().bevf_bilinear_bwd_nhwc_f32(dy.data_ptr(), dx.data_ptr(), B, Hi, Wi, Cc, Cc, Ho, Wo, y_cs, _st()),
-            "bevf_bilinear_bwd_nhwc_f32")
+        L.bilinear_bwd_nhwc(dy, dx, B, Hi, Wi, Cc, Cc, Ho, Wo, y_cs)
         return dx
 
 
@@ -786,15 +722,10 @@ class StemBlock:
             # nothing downstream reads it (the backward recomputes the ReLU mask from the raw conv output)
             _, self.stem_bn = bn_train_forward(raw, self.bn, N * H1 * W1, 64, relu=True, apply=False)
             s = self.stem_bn
-            g = self.bn.weight.data_ptr() if self.bn.weight is not None else None
-            b = self.bn.bias.data_ptr() if self.bn.bias is not None else None
-            _ck(_lib().bevf_bn_relu_maxpool3x3s2_idx_f32(raw.data_ptr(), s.mean.data_ptr(), s.invstd.data_ptr(), g, b, pooled.data_ptr(),
-                                                         self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_bn_relu_maxpool3x3s2_idx_f32")
+            L.bn_relu_maxpool3x3s2_idx(raw, s.mean, s.invstd, self.bn.weight, self.bn.bias, pooled, self.pool_idx, N, H1, W1, 64)
         else:
             y, self.stem_bn = bn_train_forward(raw, self.bn, N * H1 * W1, 64, relu=True)
-            _ck(_lib().bevf_maxpool3x3s2_idx_f32(y.data_ptr(), pooled.data_ptr(), self.pool_idx.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_maxpool3x3s2_idx_f32")
+            L.maxpool3x3s2_idx(y, pooled, self.pool_idx, N, H1, W1, 64)
         self.pool_geom = (N, H1, W1)
         return pooled, H2, W2
 
@@ -805,17 +736,13 @@ class StemBlock:
             # max-pool backward + BatchNorm/ReLU backward in one pair of passes: the dense dY of the stem map (1.1 GB at 48 images of
             # 448x800) is gathered from the pooled gradient on the fly, never written (bit-identical to the two-kernel chain below)
             s = self.stem_bn
-            work = _new(_lib().bevf_bn_work_floats(64), d.device)
+            work = _new(L.bn_work_floats(64), d.device)
             dgamma, dbeta, draw = _new(64, d.device), _new(64, d.device), _new(N * H1 * W1 * 64, d.device)
-            g = self.bn.weight.data_ptr() if self.bn.weight is not None else None
-            b = self.bn.bias.data_ptr() if self.bn.bias is not None else None
-            _ck(_lib().bevf_pool_bn_backward_f32(d.data_ptr(), self.pool_idx.data_ptr(), s.xraw.data_ptr(), s.mean.data_ptr(),
-                                                 s.invstd.data_ptr(), g, b, work.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                 draw.data_ptr(), N, H1, W1, 64, _st()), "bevf_pool_bn_backward_f32")
+            L.pool_bn_backward(d, self.pool_idx, s.xraw, s.mean, s.invstd, self.bn.weight, self.bn.bias, work, dgamma, dbeta, draw,
+                               N, H1, W1, 64)
         else:
             dpool_in = _new(N * H1 * W1 * 64, d.device)
-            _ck(_lib().bevf_maxpool3x3s2_bwd_f32(d.data_ptr(), self.pool_idx.data_ptr(), dpool_in.data_ptr(), N, H1, W1, 64, _st()),
-                "bevf_maxpool3x3s2_bwd_f32")
+            L.maxpool3x3s2_bwd(d, self.pool_idx, dpool_in, N, H1, W1, 64)
             draw, dgamma, dbeta = bn_train_backward(dpool_in, self.stem_bn, self.bn, relu=True)
         sink.add(self.bn.weight, dgamma)
         sink.add(self.bn.bias, dbeta)
@@ -823,16 +750,15 @@ class StemBlock:
         Ni, H, W = self.cam_geom_in
         dwbuf = _zeros(64 * 160, d.device)
         with E._span("conv_wgrad_f32", flops=2.0 * N * H1 * W1 * 64 * 147):
-            _ck(_lib().bevf_stem_wgrad_f32(self.imgs.data_ptr(), draw.data_ptr(), dwbuf.data_ptr(), Ni, H, W, _st()),
-                "bevf_stem_wgrad_f32")
+            L.stem_wgrad(self.imgs, draw, dwbuf, Ni, H, W)
         sink.add(self.conv.weight, dwbuf[:64 * 160].view(64, 160)[:, :147].reshape(64, 3, 7, 7))
 
 
 class PillarPFNLayer:
     """PillarLiDAREncoder under train-mode BatchNorm: voxelize -> the PFN's batch statistics from the decorated points' moments
-    (bevf_pillar_moments_f32: sum f, sum f f^T over the P rows of every occupied pillar, the empty pillar slots left out; running
-    buffers updated there) -> bevf_pillar_pfn_f32 with those scale / shift, keeping the argmax row of every (pillar, channel) ->
-    fp32 NHWC canvas.  Frozen BatchNorm (bn_is_frozen): the running statistics.  Backward: bevf_pillar_pfn_backward_f32 -- the
+    (L.pillar_moments: sum f, sum f f^T over the P rows of every occupied pillar, the empty pillar slots left out; running
+    buffers updated there) -> L.pillar_pfn with those scale / shift, keeping the argmax row of every (pillar, channel) ->
+    fp32 NHWC canvas.  Frozen BatchNorm (bn_is_frozen): the running statistics.  Backward: L.pillar_backward -- the
     canvas gradient at the argmax rows gives the weight, bias and BatchNorm gradients in closed form (no per-row pass)."""
 
     def __init__(self, enc):
@@ -1023,9 +949,8 @@ class DetectorTape:
         if renc.fusion_method == "max":                                   # ref src/encoders.py:654-655
             out = _new(B * feat, per.device)
             self.rad_fuse_idx = torch.empty(B * feat, dtype=torch.int32, device=per.device)
-            gwork = torch.empty(_lib().bevf_group_max_idx_work_bytes(B, R, feat), dtype=torch.uint8, device=per.device)
-            _ck(_lib().bevf_group_max_idx_f32(per.data_ptr(), out.data_ptr(), self.rad_fuse_idx.data_ptr(), gwork.data_ptr(),
-                                              B, R, feat, _st()), "bevf_group_max_idx_f32")
+            gwork = torch.empty(L.group_max_idx_work_bytes(B, R, feat), dtype=torch.uint8, device=per.device)
+            L.group_max_idx(per, out, self.rad_fuse_idx, gwork, B, R, feat)
             return out, B
         if renc.fusion_method == "mean":                                  # ref src/encoders.py:656-657
             out = _new(B * feat, per.device)
@@ -1043,11 +968,10 @@ class DetectorTape:
         B, R, feat = self.rad_geom
         if renc.fusion_method == "max":            # the gradient goes to the sweep that held the maximum (first one on ties)
             dper = _zeros(B * R * feat, dfeat.device)
-            _ck(_lib().bevf_group_max_bwd_f32(dfeat.data_ptr(), self.rad_fuse_idx.data_ptr(), dper.data_ptr(), B, R, feat, _st()),
-                "bevf_group_max_bwd_f32")
+            L.group_max_bwd(dfeat, self.rad_fuse_idx, dper, B, R, feat)
         elif renc.fusion_method == "mean":         # every sweep receives dfeat / R
             dper = _new(B * R * feat, dfeat.device)
-            _ck(_lib().bevf_cam_mean_bwd_f32(dfeat.data_ptr(), dper.data_ptr(), B, R, 1, feat, _st()), "bevf_cam_mean_bwd_f32")
+            L.cam_mean_bwd(dfeat, dper, B, R, 1, feat)
         else:
             dper = self.rad_fc.backward(dfeat, sink)                        # [B][R][feat]
         for r in reversed(range(R)):
@@ -1220,16 +1144,8 @@ class DetectorTape:
         ctot = sum(self.cs)
         dhid = _new(B * P * 5 * self.hc, dev)
         dw1, db1 = _zeros(ctot * self.hc, dev), _zeros(ctot, dev)
-        d = L.HeadBwdDesc()
-        d.hid, d.w, d.out0 = self.head_hid.data_ptr(), self.w1.data_ptr(), self.outs[0].data_ptr()
-        keep = []
-        for k in range(5):
-            g = douts[k]
-            g = torch.zeros_like(self.outs[k]) if g is None else g.contiguous().float()
-            keep.append(g)
-            d.dout[k], d.c[k] = g.data_ptr(), self.cs[k]
-        d.dhid, d.dw, d.db, d.B, d.P, d.hc, d.n_sigmoid = dhid.data_ptr(), dw1.data_ptr(), db1.data_ptr(), B, P, self.hc, self.cs[0]
-        _ck(_lib().bevf_head_tail_bwd_f32(C.byref(d), _st()), "bevf_head_tail_bwd_f32")
+        gouts = [torch.zeros_like(o) if g is None else g.contiguous().float() for g, o in zip(douts, self.outs)]
+        L.head_tail_bwd(self.head_hid, self.w1, self.outs[0], gouts, dhid, dw1, db1, B, P, self.hc, self.cs, self.cs[0])
         o = 0
         for k, c1 in enumerate(convs1):
             n = self.cs[k]
@@ -1238,8 +1154,7 @@ class DetectorTape:
             o += n
         # fused 3x3 head conv: ReLU mask, bias / weight / data gradients, split back per branch
         c5 = 5 * self.hc
-        n4 = (B * P * c5 + 3) // 4 * 4
-        _ck(_lib().bevf_relu_mask_f32(dhid.data_ptr(), self.head_hid.data_ptr(), n4, _st()), "bevf_relu_mask_f32")
+        L.relu_mask(dhid, self.head_hid, B * P * c5)
         db3 = colsum(dhid, B * P, c5)
         cin = self.head_w3.shape[1]
         dw3 = conv_wgrad(self.head_in, dhid, B, Sh, Sw, cin, c5, 3, 1, 1).permute(0, 3, 1, 2)
@@ -1297,8 +1212,7 @@ class DetectorTape:
             dfeat = dpooled
             if ncam > 1:
                 dfeat = _new(Bc * ncam * Pc * Cc, dev)
-                _ck(_lib().bevf_cam_mean_bwd_f32(dpooled.data_ptr(), dfeat.data_ptr(), Bc, ncam, Pc, Cc, _st()),
-                    "bevf_cam_mean_bwd_f32")
+                L.cam_mean_bwd(dpooled, dfeat, Bc, ncam, Pc, Cc)
             if on_camera is not None:
                 on_camera(dfeat)
         return drad, dlid, dfeat
@@ -1609,31 +1523,11 @@ class _LossFn(torch.autograd.Function):
         for g in g_rest:
             if g is not None and bool((g != 0).any()):
                 raise NotImplementedError("backward through the individual loss terms is not built; use total_loss")
-        preds, tgt, w = ctx.preds, ctx.tgt, ctx.weights
-        heat = preds["heatmap"]
-        B, Cn, H, W = heat.shape
-        K = tgt["ind"].shape[1]
-        dev = heat.device
-        d = L.LossDesc()
-        keep = []
-
-        def f32(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        d.pred_heatmap, d.tgt_heatmap = f32(heat), f32(tgt["heatmap"])
-        for q, name in enumerate(("offset", "size", "rot", "vel")):
-            d.pred_reg[q], d.tgt_reg[q] = f32(preds[name]), f32(tgt["target_" + name])
-        ind = tgt["ind"].to(torch.int64).contiguous()
-        rm = tgt["reg_mask"].to(torch.uint8).contiguous()
-        d.ind, d.reg_mask = ind.data_ptr(), rm.data_ptr()
-        d.B, d.C, d.H, d.W, d.K = B, Cn, H, W, K
-        for i in range(5):
-            d.weights[i] = float(w[i])
+        preds = ctx.preds
+        dev = preds["heatmap"].device
         dp = [torch.zeros_like(preds[n], dtype=torch.float32) for n in E.HEAD_BRANCHES]
-        arr = (C.c_void_p * 5)(*[t.data_ptr() for t in dp])
         scratch = torch.empty(4, device=dev)
-        _ck(_lib().bevf_centernet_loss_bwd_f32(C.byref(d), arr, scratch.data_ptr(), _st()), "bevf_centernet_loss_bwd_f32")
+        L.centernet_loss_bwd(preds, ctx.tgt, ctx.weights, dp, scratch)
         gt = g_total if g_total is not None else torch.zeros((), device=dev)
         return (None, None, *[t * gt for t in dp], *([None] * len(ctx.tgt)))
 
@@ -1654,15 +1548,14 @@ def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
     flat = torch.cat([p.grad.detach().reshape(-1).float() for p in params])
     work = torch.empty(512, dtype=torch.float64, device=dev)
     out = torch.empty(2, device=dev)
-    _ck(_lib().bevf_grad_norm_f32(flat.data_ptr(), flat.numel(), work.data_ptr(), float(max_norm), out.data_ptr(), _st()),
-        "bevf_grad_norm_f32")
+    L.grad_norm(flat, work, max_norm, out)
     for p in params:
         p.grad.mul_(out[1])
     return out[0]
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics (ref src/train_detect.py:725-741: lr 1e-4, weight_decay 0.01) on bevf_adamw_step_f32.
+    """torch.optim.AdamW semantics (ref src/train_detect.py:725-741: lr 1e-4, weight_decay 0.01) on L.adamw_step.
 
     The parameters that receive gradients are moved into ONE flat fp32 arena on the first step (each Parameter becomes
     a view of it, so state_dict / load_state_dict keep working); a step is then one gradient gather, optionally the
@@ -1714,15 +1607,12 @@ class FusedAdamW(torch.optim.Optimizer):
             g = torch.cat([p.grad.reshape(-1) for p in with_grad])
             clip = None
             if self.max_grad_norm is not None:
-                _ck(_lib().bevf_grad_norm_f32(g.data_ptr(), g.numel(), ar["work"].data_ptr(), float(self.max_grad_norm),
-                                              ar["clip"].data_ptr(), _st()), "bevf_grad_norm_f32")
-                clip = ar["clip"].data_ptr()
+                L.grad_norm(g, ar["work"], self.max_grad_norm, ar["clip"])
+                clip = ar["clip"]
                 self.last_grad_norm = ar["clip"][0]
             ar["step"] += 1
             b1, b2 = group["betas"]
-            _ck(_lib().bevf_adamw_step_f32(ar["flat"].data_ptr(), g.data_ptr(), ar["m"].data_ptr(), ar["v"].data_ptr(), clip,
-                                           g.numel(), group["lr"], b1, b2, group["eps"], group["weight_decay"], ar["step"],
-                                           _st()), "bevf_adamw_step_f32")
+            L.adamw_step(ar["flat"], g, ar["m"], ar["v"], clip, group["lr"], b1, b2, group["eps"], group["weight_decay"], ar["step"])
             for p in with_grad:                      # the kernel wrote through raw pointers: tell torch (and the
                 torch.autograd.graph.increment_version(p)   # engines' repack signature) that the values changed
 

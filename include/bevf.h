@@ -494,6 +494,8 @@ int bevf_pool_bn_backward_f32(const float* dpool, const uint8_t* idx, const floa
 int bevf_bn_relu_maxpool3x3s2_idx_f32(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                       float* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
 
+/* Elementwise over n floats; both require n % 4 == 0 and 16-byte aligned buffers (callers round n up and size both
+ * buffers for the rounded count).                                                                                    */
 int bevf_add_inplace_f32(float* y, const float* x, size_t n, void* stream);            /* y += x            */
 int bevf_relu_mask_f32(float* dy, const float* y, size_t n, void* stream);             /* dy *= (y > 0)     */
 int bevf_maxpool3x3s2_idx_f32(const float* x, float* y, uint8_t* idx, int N, int H, int W, int C, void* stream);

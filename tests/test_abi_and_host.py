@@ -31,6 +31,173 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().bevf_version() >= 100
 
 
+_STRUCTS = {"bevf_conv_desc": _lib.ConvDesc, "bevf_radar_desc": _lib.RadarDesc, "bevf_head_desc": _lib.HeadDesc,
+            "bevf_decode_desc": _lib.DecodeDesc, "bevf_targets_desc": _lib.TargetsDesc, "bevf_loss_desc": _lib.LossDesc,
+            "bevf_voxelize_desc": _lib.VoxelizeDesc, "bevf_pillar_geom": _lib.PillarGeom, "bevf_wgrad_desc": _lib.WgradDesc,
+            "bevf_head_bwd_desc": _lib.HeadBwdDesc}
+_SCALARS = {"int": "int", "int32_t": "int", "size_t": "size_t", "float": "float", "double": "double"}
+
+
+def _c_kind(decl: str) -> str:
+    """Kind of a C declaration with its name removed: 'ptr', 'struct:<name>' (pointer to a bevf struct) or a scalar kind."""
+    base = re.sub(r"\bconst\b", "", decl).strip()
+    if "*" in base:
+        pointee = base.replace("*", " ").split()
+        return f"struct:{pointee[0]}" if base.count("*") == 1 and pointee[0] in _STRUCTS else "ptr"
+    return _SCALARS.get(base, base)
+
+
+def _c_decl(decl: str):
+    """'const float* w[4]' -> (name, kind); arrays are '<kind>[n]'."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[(\d+)\])?", decl.strip(), re.S)
+    kind = _c_kind(m.group(1))
+    return m.group(2), kind + (f"[{m.group(3)}]" if m.group(3) else "")
+
+
+def _ct_kind(t) -> str:
+    if isinstance(t, type) and issubclass(t, ctypes.Array):
+        return f"{_ct_kind(t._type_)}[{t._length_}]"
+    if isinstance(t, type) and issubclass(t, ctypes._Pointer):
+        names = [k for k, v in _STRUCTS.items() if v is t._type_]
+        return f"struct:{names[0]}" if names else "ptr"
+    kinds = {ctypes.c_void_p: "ptr", ctypes.c_char_p: "ptr", ctypes.c_int: "int", ctypes.c_size_t: "size_t",
+             ctypes.c_float: "float", ctypes.c_double: "double"}
+    return kinds.get(t, repr(t))
+
+
+def _parse_header():
+    """include/bevf.h -> ({function: (return kind, [argument kinds])}, {struct: [(field, kind)]})."""
+    src = open(os.path.join(ROOT, "include", "bevf.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        fields = []
+        for decl in filter(str.strip, body.split(";")):
+            first, *more = decl.split(",")
+            fname, kind = _c_decl(first)
+            fields.append((fname, kind))
+            fields += [(d.strip(), kind) for d in more]                    # 'int32_t N, H, W': the rest share the first's kind
+        structs[name] = fields
+    src = re.sub(r"typedef\s+(?:struct|enum)\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
+    funcs = {}
+    for stmt in src.split(";"):
+        m = re.fullmatch(r"\s*([^(]*?)\b(bevf_\w+)\s*\(([^()]*)\)\s*", re.split(r"[{}]", stmt)[-1])
+        if m:
+            ret, name, args = m.groups()
+            funcs[name] = (_c_kind(ret), [] if args.strip() == "void" else [_c_decl(a)[1] for a in args.split(",")])
+    return funcs, structs
+
+
+def test_bindings_match_header_types():
+    """Every prototype's return and argument kinds, and every struct's field names, order, kinds and array lengths, as
+    include/bevf.h declares them: SIGNATURES and the ctypes Structures must say the same."""
+    funcs, structs = _parse_header()
+    assert sorted(funcs) == sorted(_lib.SIGNATURES) and len(funcs) >= 100
+    for name, (ret, args) in funcs.items():
+        res, argtypes = _lib.SIGNATURES[name]
+        assert (_ct_kind(res), [_ct_kind(a) for a in argtypes]) == (ret, args), f"{name}: binding differs from include/bevf.h"
+    assert sorted(structs) == sorted(_STRUCTS)
+    for name, fields in structs.items():
+        assert [(f, _ct_kind(t)) for f, t in _STRUCTS[name]._fields_] == fields, f"{name}: ctypes fields differ from include/bevf.h"
+
+
+class _LaunchRecorder:
+    """Stands in for the loaded library: size queries answer from the real one, every other entry point is recorded."""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    def __getattr__(self, name):
+        if re.search(r"_(bytes|floats|rows)$", name) or name == "bevf_last_error":
+            return getattr(self.real, name)
+        return lambda *args: self.calls.append(name) or 0
+
+
+def _wrapper_case(name: str, s: int):
+    """(wrapper, args, kwargs) with CPU buffers of exactly the sizes the kernel needs; s = 1 makes one of them an element short."""
+    def z(n, dt=torch.float32):
+        return torch.zeros(n, dtype=dt)
+    I32, U8, I64, F64 = torch.int32, torch.uint8, torch.int64, torch.float64
+    L = _lib
+    wtab = -(-L.wino_wgrad_table_bytes(1, 8, 8) // 4)
+    ptab = -(-L.conv_pixtab_bytes(1, 4, 4, 3, 3, 1, 1) // 4)
+    bw, gw = L.bn_work_floats(4), L.group_max_idx_work_bytes(2, 4, 4)
+    geo = dict(N=1, H=4, W=4, Cin=4, x_cs=4, Cout=4, dy_cs=4)
+    pred = {k: z((1, c, 4, 4)) for k, c in (("heatmap", 2), ("offset", 2), ("size", 3), ("rot", 2), ("vel", 2))}
+    tgt = dict(heatmap=z((1, 2, 4, 4)), ind=z((1, 3), I64), reg_mask=z((1, 3), U8), target_offset=z((1, 3, 2)),
+               target_size=z((1, 3, 3)), target_rot=z((1, 3, 2)), target_vel=z((1, 3, 2)))
+    cases = {
+        "conv_pixtab": (L.conv_pixtab, (z(ptab - s, I32), 1, 4, 4, 3, 3, 1, 1, 4), {}),
+        "wino_wgrad_table": (L.wino_wgrad_table, (z(wtab - s, I32), 1, 8, 8, 64, 64), {}),
+        "conv2d_wgrad": (L.conv2d_wgrad, (z(64), z(64), z(144 - s), z(ptab, I32)), dict(geo, KH=3, KW=3, stride=1, pad=1)),
+        "conv3x3_wgrad_wino": (L.conv3x3_wgrad_wino, (z(4096), z(4096), z(36864), z(wtab, I32),
+                                                      z(L.wino_wgrad_workspace_floats(1, 8, 8, 64, 64) - s)),
+                               dict(N=1, H=8, W=8, Cin=64, x_cs=64, Cout=64, dy_cs=64, accumulate=False)),
+        "zero_stuff_nhwc": (L.zero_stuff_nhwc, (z(16), z(64 - s), 1, 2, 2, 4, 4, 4, 2), {}),
+        "interleave2x2_nhwc": (L.interleave2x2_nhwc, ([z(16 - s), z(16), None, z(16)], [2] * 4, [2] * 4, z(64), 1, 4, 4, 4), {}),
+        "stem_wgrad": (L.stem_wgrad, (z(192), z(1024 - s), z(10240), 1, 8, 8), {}),
+        "smallk_wgrad": (L.smallk_wgrad, (z(512), z(32 - s), z(256), 8, 4, 64), {}),
+        "bn_stats": (L.bn_stats, (z(32), z(bw - s), z(4), z(4), z(4), 8, 4, 4, 1e-5), {}),
+        "bn_stats_from_partials": (L.bn_stats_from_partials, (z(16 - s), 2, z(4), z(4), z(4), z(4), 8, 4, 1e-5), {}),
+        "bn_apply": (L.bn_apply, (z(32), z(4), z(4), z(4), z(4), z(32 - s), z(32), 8, 4, 4, True), {}),
+        "bn_update_running": (L.bn_update_running, (z(4), z(4), z(4), z(4), z(1 - s, I64), 4, 8, 0.1), {}),
+        "bn_backward": (L.bn_backward, (z(32), z(32 - s), z(32), z(4), z(4), z(4), z(4), z(bw), z(4), z(4), z(32), 8, 4, 4),
+                        dict(relu=True, has_res=True)),
+        "bn_backward_from_partials": (L.bn_backward_from_partials, (z(32), z(32), z(4), z(4), z(4), z(16), 2, z(4), z(4),
+                                                                    z(32 - s), 8, 4, 4), {}),
+        "pool_bn_backward": (L.pool_bn_backward, (z(16), z(16 - s, U8), z(64), z(4), z(4), z(4), z(4), z(bw), z(4), z(4), z(64),
+                                                  1, 4, 4, 4), {}),
+        "bn_relu_maxpool3x3s2_idx": (L.bn_relu_maxpool3x3s2_idx, (z(64), z(4), z(4), z(4), z(4), z(16), z(16 - s, U8), 1, 4, 4, 4), {}),
+        "bn_relu_group_max_idx": (L.bn_relu_group_max_idx, (z(32), z(4), z(4), z(4), z(4), z(8), z(8, I32), z(gw - s, U8), 2, 4, 4), {}),
+        "gmax_bn_backward": (L.gmax_bn_backward, (z(8), z(8), z(8, I32), z(32 - s), z(4), z(4), z(4), z(8), z(4), z(4), z(32),
+                                                  2, 4, 4, 4), {}),
+        "gmax_bn_sums": (L.gmax_bn_sums, (z(8), z(8), z(8, I32), z(32), z(4), z(4), z(8 - s), z(4), z(4), 2, 4, 4, 4), {}),
+        "maxpool3x3s2_idx": (L.maxpool3x3s2_idx, (z(64), z(16 - s), z(16, U8), 1, 4, 4, 4), {}),
+        "maxpool3x3s2_bwd": (L.maxpool3x3s2_bwd, (z(16), z(16, U8), z(64 - s), 1, 4, 4, 4), {}),
+        "group_max_idx": (L.group_max_idx, (z(32 - s), z(8), z(8, I32), z(gw, U8), 2, 4, 4), {}),
+        "group_max_bwd": (L.group_max_bwd, (z(8), z(8 - s, I32), z(32), 2, 4, 4), {}),
+        "sparse_rows_wgrad": (L.sparse_rows_wgrad, (z(8), z(8, I32), z(32), z(16 - s), 2, 4, 4, 4), {}),
+        "sparse_rows_scatter_add": (L.sparse_rows_scatter_add, (z(8), z(8, I32), z(16 - s), z(32), 2, 4, 4, 4), {}),
+        "bilinear_bwd_nhwc": (L.bilinear_bwd_nhwc, (z(64 - s), z(16), 1, 2, 2, 4, 4, 4, 4, 4), {}),
+        "cam_mean_bwd": (L.cam_mean_bwd, (z(16), z(32 - s), 1, 2, 4, 4), {}),
+        "relu_mask": (L.relu_mask, (z(8 - s), z(8), 6), {}),             # n = 6 reaches the kernel as 8
+        "add_inplace": (L.add_inplace, (z(8), z(8 - s), 6), {}),
+        "linear_bwd": (L.linear_bwd, (z(8), z(8), z(16), z(8), z(16), z(4 - s), z(L.linear_bwd_work_floats(2, 4, 4)), 2, 4, 4), {}),
+        "head_tail_bwd": (L.head_tail_bwd, (z(80), z(44), z(8), [z(8), z(8), z(12 - s), z(8), z(8)], z(80), z(44), z(11),
+                                            1, 4, 4, (2, 2, 3, 2, 2), 2), {}),
+        "centernet_loss_bwd": (L.centernet_loss_bwd, (pred, tgt, [1.0] * 5, [z(32 - s), z(32), z(48), z(32), z(32)], z(2)), {}),
+        "grad_norm": (L.grad_norm, (z(8), z(512 - s, F64), 10.0, z(2)), {}),
+        "adamw_step": (L.adamw_step, (z(8), z(8), z(8 - s), z(8), z(2), 1e-4, 0.9, 0.999, 1e-8, 0.01, 1), {}),
+        "resize_normalize_u8": (L.resize_normalize_u8, (z(48, U8), z(12), 1, 4, 4, 2, 2, z(4, I32), z(6 - s, I32), 3, z(4, I32),
+                                                        z(6, I32), 3, (0.5,) * 3, (0.25,) * 3), {}),
+        "lidar_filter_pad": (L.lidar_filter_pad, (z(32), z(16), z(1, I32), z(33 - s), z(4, I64), 8, 4, 4, (-1.0,) * 3 + (1.0,) * 3), {}),
+    }
+    return cases[name]
+
+
+_WRAPPERS = ["conv_pixtab", "wino_wgrad_table", "conv2d_wgrad", "conv3x3_wgrad_wino", "zero_stuff_nhwc", "interleave2x2_nhwc",
+             "stem_wgrad", "smallk_wgrad", "bn_stats", "bn_stats_from_partials", "bn_apply", "bn_update_running", "bn_backward",
+             "bn_backward_from_partials", "pool_bn_backward", "bn_relu_maxpool3x3s2_idx", "bn_relu_group_max_idx", "gmax_bn_backward",
+             "gmax_bn_sums", "maxpool3x3s2_idx", "maxpool3x3s2_bwd", "group_max_idx", "group_max_bwd", "sparse_rows_wgrad",
+             "sparse_rows_scatter_add", "bilinear_bwd_nhwc", "cam_mean_bwd", "relu_mask", "add_inplace", "linear_bwd", "head_tail_bwd",
+             "centernet_loss_bwd", "grad_norm", "adamw_step", "resize_normalize_u8", "lidar_filter_pad"]
+
+
+@pytest.mark.parametrize("name", _WRAPPERS)
+def test_training_and_input_wrappers_check_before_launching(name, monkeypatch):
+    """A buffer one element short raises before anything is launched; right-sized CPU tensors are refused, not computed."""
+    rec = _LaunchRecorder(_lib.lib())
+    monkeypatch.setattr(_lib, "_lib", rec)
+    fn, args, kwargs = _wrapper_case(name, 1)
+    with pytest.raises(_lib.BevfError, match="needs"):
+        fn(*args, **kwargs)
+    fn, args, kwargs = _wrapper_case(name, 0)
+    with pytest.raises(_lib.BevfError, match="no CPU fallback"):
+        fn(*args, **kwargs)
+    assert rec.calls == []
+
+
 def test_cpu_tensors_are_refused_not_silently_computed():
     m = fusion.create_detector("camera_only", "bev", "centernet", bev_h=8, bev_w=8).eval()
     with pytest.raises(_lib.BevfError, match="no CPU fallback"):

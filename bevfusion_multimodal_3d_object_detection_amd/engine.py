@@ -5,9 +5,10 @@ An engine packs its module's parameters once per weight version (BatchNorm folde
 conv weights re-laid OIHW -> OHWI, the lidar_init rows left in place and permuted on store),
 keeps grow-only device workspaces, and issues the C-ABI calls on torch's current stream.
 Internally every activation is fp32 NHWC; NCHW exists only at the reference's API surface.
-These engines are the eval-mode path (BatchNorm folded from its running statistics).  Training runs through
-training.DetectorTape (train-mode BatchNorm + hand-written backward): the whole detector, and each camera / PointNet /
-radar encoder, the BEV fusion and the head used on their own, dispatch there from their `forward` while in train mode.
+These engines are the eval-mode path (BatchNorm folded from its running statistics).  Training runs through the tapes
+of training.py (train-mode BatchNorm + hand-written backward), one per module kind: training.DetectorTape composes them
+for the whole detector, and each camera / PointNet / radar / pillar encoder, the BEV fusion and the head used on their
+own dispatch to their own tape from their `forward` while in train mode.
 An engine asked to fold a BatchNorm that is still in train mode (e.g. VFELayer, which has no tape) raises (_check_eval).
 """
 from __future__ import annotations
@@ -111,8 +112,9 @@ def _check_eval(module: nn.Module) -> None:
             raise L.BevfError(
                 f"{type(module).__name__} has a BatchNorm in train mode but was asked for the eval-mode kernels (BatchNorm "
                 "folded from running statistics) -- call .eval() first.  Train-mode BatchNorm, backward and optimiser run "
-                "through training.DetectorTape: the detector, ResNetCameraEncoder, PointNetLiDAREncoder, RadarEncoder / "
-                "MultiRadarEncoder, VFELayer, FlexibleBEVFusion and CenterNetHead reach it from forward() in train mode.")
+                "through the training tapes (training.DetectorTape and its per-module tapes): the detector, ResNetCameraEncoder, "
+                "PointNetLiDAREncoder, PillarLiDAREncoder, RadarEncoder / MultiRadarEncoder, VFELayer, FlexibleBEVFusion and "
+                "CenterNetHead reach them from forward() in train mode.")
 
 
 class _Engine:
@@ -646,19 +648,39 @@ class FusionEngine(_Engine):
 HEAD_BRANCHES = ("heatmap", "offset", "size", "rot", "vel")
 
 
+@dataclass
+class HeadWeights:
+    """CenterNetHead's five branches (HEAD_BRANCHES order) concatenated for two launches: w3 [5*hc][Cin][3][3] / b3 the 3x3 convs
+    along Cout, w1 [sum cs][hc] / b1 the 1x1 tails; convs3 / convs1 the branch modules the gradients belong to."""
+    convs3: List[nn.Module]
+    convs1: List[nn.Module]
+    hc: int
+    cs: List[int]
+    w3: torch.Tensor
+    b3: torch.Tensor
+    w1: torch.Tensor
+    b1: torch.Tensor
+
+
+def head_weights(head: nn.Module) -> HeadWeights:
+    """The head's weights as HeadWeights, in the module's dtype (HeadEngine.pack and training.HeadTape)."""
+    convs3 = [getattr(head, f"{n}_head")[0] for n in HEAD_BRANCHES]
+    convs1 = [getattr(head, f"{n}_head")[2] for n in HEAD_BRANCHES]
+    hc = convs3[0].weight.shape[0]
+    return HeadWeights(convs3, convs1, hc, [c.weight.shape[0] for c in convs1],
+                       torch.cat([c.weight.detach() for c in convs3], 0), torch.cat([c.bias.detach() for c in convs3], 0),
+                       torch.cat([c.weight.detach().reshape(c.weight.shape[0], hc) for c in convs1], 0),
+                       torch.cat([c.bias.detach() for c in convs1], 0))
+
+
 class HeadEngine(_Engine):
     def pack(self) -> None:
-        m = self.module
-        convs3 = [getattr(m, f"{n}_head")[0] for n in HEAD_BRANCHES]
-        convs1 = [getattr(m, f"{n}_head")[2] for n in HEAD_BRANCHES]
-        w3 = torch.cat([c.weight.detach() for c in convs3], dim=0)                 # (5*hc, Cin, 3, 3)
-        b3 = torch.cat([c.bias.detach() for c in convs3], dim=0)
-        self.hc = convs3[0].weight.shape[0]
-        self.conv = _finish_pack(w3.permute(0, 2, 3, 1).contiguous().view(-1), None, b3.float().contiguous(),
-                                 w3.shape[1], w3.shape[0], 3, 1, 1, True)
-        self.cs = [c.weight.shape[0] for c in convs1]
-        self.w1 = torch.cat([c.weight.detach().reshape(c.weight.shape[0], self.hc) for c in convs1], 0).float().contiguous()
-        self.b1 = torch.cat([c.bias.detach() for c in convs1], 0).float().contiguous()
+        hw = head_weights(self.module)
+        self.hc, self.cs = hw.hc, hw.cs
+        self.conv = _finish_pack(hw.w3.permute(0, 2, 3, 1).contiguous().view(-1), None, hw.b3.float().contiguous(),
+                                 hw.w3.shape[1], hw.w3.shape[0], 3, 1, 1, True)
+        self.w1 = hw.w1.float().contiguous()
+        self.b1 = hw.b1.float().contiguous()
 
     def run(self, bev_nhwc: torch.Tensor, B: int, H: int, W: int) -> Dict[str, torch.Tensor]:
         self.ensure_packed()

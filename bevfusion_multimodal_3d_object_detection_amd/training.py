@@ -1,16 +1,16 @@
 """Training step on the HIP path (ref src/train_detect.py:401-434).
 
-`model.train()` routes `FlexibleMultiModal3DDetector.forward` through `_DetectorTrainFn`, one
-`torch.autograd.Function` for the whole detector: the forward runs the same NHWC kernels as inference but
-with train-mode BatchNorm (batch statistics, running-stat update) and keeps a tape; the backward walks the
-tape with hand-written gradient kernels (MFMA weight / data gradients, BN, pooling, resample, dense layers,
-head) and returns the parameter gradients to autograd, so the reference's training loop --
-`loss.backward(); clip_grad_norm_(...); optimizer.step()` -- works unchanged.  torch is used for tensor
+`model.train()` routes `FlexibleMultiModal3DDetector.forward` through `DetectorTape` under `_TapeFn`, the one
+`torch.autograd.Function` of every tape path: the forward runs the same NHWC kernels as inference but with train-mode
+BatchNorm (batch statistics, running-stat update) and keeps a tape; the backward walks the tape with hand-written gradient
+kernels (MFMA weight / data gradients, BN, pooling, resample, dense layers, head) and returns the parameter gradients to
+autograd, so the reference's training loop -- `loss.backward(); clip_grad_norm_(...); optimizer.step()` -- works unchanged.
+`DetectorTape` composes one tape per module kind (CameraTape, PointMLPTape, RadarTape, PillarPFNLayer, FusionTape,
+HeadTape), each built from the real module; the same tapes serve those modules used on their own.  torch is used for tensor
 allocation and for weight layout permutes; no torch compute op touches an activation.
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -816,27 +816,30 @@ class PillarPFNLayer:
         sink.add(bn.bias, dbeta[:Cout])
 
 
-# ---- the detector graph --------------------------------------------------------------------------------------------------------
+# ---- module tapes ---------------------------------------------------------------------------------------------------------------
+# One tape per module kind, built from the real nn.Module.  forward() runs the module under train-mode BatchNorm, keeps what the
+# backward needs and exposes the geometry its callers need (B: batch size, cout: output channels, H / W: spatial size);
+# backward(d, sink) adds the parameter gradients to `sink` and returns the input gradient (None where there is none).
+# PillarPFNLayer above is the PointPillars tape.
 
-class DetectorTape:
-    """Train-mode forward of FlexibleMultiModal3DDetector (bev + centernet) with everything backward needs."""
+class CameraTape:
+    """ResNetCameraEncoder (ref src/encoders.py:133-172): stem, ResNet blocks, channel_proj -> NHWC features [B*n*H*W*cout]
+    (n cameras per frame)."""
 
-    def __init__(self, model):
-        self.m = model
+    def __init__(self, enc):
+        self.enc = enc
 
-    # -- camera encoder ---------------------------------------------------------------------------------------------------------
-    def _camera_forward(self, imgs):
-        enc = self.m.camera_encoder
+    def forward(self, imgs):
+        enc = self.enc
         if imgs.dim() == 5:
-            B, n = imgs.shape[:2]
-            x = imgs.reshape(B * n, *imgs.shape[2:]).contiguous().float()
+            self.B, self.n = imgs.shape[:2]
+            x = imgs.reshape(self.B * self.n, *imgs.shape[2:]).contiguous().float()
         else:
-            B, n = imgs.shape[0], 1
+            self.B, self.n = imgs.shape[0], 1
             x = imgs.contiguous().float()
         N, _, H, W = x.shape
         self.stem = StemBlock(enc.conv1, enc.bn1)
-        pooled, H2, W2 = self.stem.forward(x, N, H, W)
-        cur, h, wd = pooled, H2, W2
+        cur, h, wd = self.stem.forward(x, N, H, W)
         self.blocks = []
         for layer in (enc.layer1, enc.layer2, enc.layer3):
             for blk in layer:
@@ -846,14 +849,15 @@ class DetectorTape:
                 idt = cur
                 if down is not None:
                     idt, _, _ = down.forward(cur, N, h, wd)
-                out, _, _ = c2.forward(t, N, ho, wo, res=idt)
+                cur, _, _ = c2.forward(t, N, ho, wo, res=idt)
                 self.blocks.append((c1, c2, down))
-                cur, h, wd = out, ho, wo
+                h, wd = ho, wo
         self.proj = ConvBNLayer(enc.channel_proj[0], enc.channel_proj[1], True)
         feat, _, _ = self.proj.forward(cur, N, h, wd)
-        return feat, (B, n, h, wd)
+        self.cout, self.H, self.W = self.proj.cout, h, wd
+        return feat
 
-    def _camera_backward(self, dfeat, sink):
+    def backward(self, dfeat, sink: GradSink) -> None:
         d, _ = self.proj.backward(dfeat, sink)
         rev = list(reversed(self.blocks))
         pre = None                                             # BatchNorm-backward partials that arrive WITH d (or None)
@@ -874,155 +878,123 @@ class DetectorTape:
                 sink.ready()                                   # one ResNet stage done: its gradients can travel
         self.stem.backward(d, sink)
 
-    # -- PointNet ----------------------------------------------------------------------------------------------------------------
-    def _lidar_forward(self, pts):
-        enc = self.m.lidar_encoder
-        if getattr(enc, "is_pillars", False):                         # PointPillars: NHWC fp32 canvas on the BEV grid
-            _no_input_grad(pts, "the LiDAR points")
-            self.pillar = PillarPFNLayer(enc)
-            canvas = self.pillar.forward(pts)
-            self.pn_geom = (self.pillar.B, pts.shape[1], pts.shape[2])
-            return canvas
+
+class PointMLPTape:
+    """A shared point MLP (encoders._PointMLP: conv1..conv{depth}, each with BatchNorm1d or Identity, ReLU) and the max over each
+    frame's points -> (B, cout) as a flat buffer.  fuse_max (PointNet): while the last BatchNorm is in train mode, its BatchNorm +
+    ReLU + max run as one pass (ConvBNLayer.forward_groupmax); otherwise (radar, use_bn=False, frozen statistics) the activation is
+    written, then group_max_with_index."""
+
+    def __init__(self, enc, depth: int, fuse_max: bool):
+        self.enc, self.depth, self.fuse_max = enc, depth, fuse_max
+
+    def forward(self, pts):
+        enc = self.enc
         rows = enc._rows(pts)
-        B, Np, Cc = rows.shape
-        M = B * Np
-        self.pn_geom = (B, Np, Cc)
-        self.pn_first = PointFirstLayer(enc.conv1, enc.bn1)          # bn*: BatchNorm1d, or Identity under use_bn=False
-        a = self.pn_first.forward(rows, M, Cc)
-        self.pn_layers = []
-        for i in range(2, 5):
-            lyr = ConvBNLayer(getattr(enc, f"conv{i}"), _bn_or_none(getattr(enc, f"bn{i}")), True)
+        self.B, self.Np, Cc = rows.shape
+        M = self.B * self.Np
+        self.first = PointFirstLayer(enc.conv1, enc.bn1)               # bn*: BatchNorm1d, or Identity under use_bn=False
+        a = self.first.forward(rows, M, Cc)
+        self.layers = [ConvBNLayer(getattr(enc, f"conv{i}"), _bn_or_none(getattr(enc, f"bn{i}")), True)
+                       for i in range(2, self.depth + 1)]
+        *mid, last = self.layers
+        for lyr in mid:
             a, _, _ = lyr.forward(a, M, 1, 1)
-            self.pn_layers.append(lyr)
-        lyr = ConvBNLayer(enc.conv5, _bn_or_none(enc.bn5), True)
-        self.pn_layers.append(lyr)
-        self.pn_fused_max = lyr.bn is not None and not bn_is_frozen(lyr.bn)
-        if self.pn_fused_max:                                        # last layer: BN + ReLU + max over points, fused
-            g, self.pn_idx = lyr.forward_groupmax(a, B, Np)
-        else:                                                        # use_bn=False / frozen statistics: the activation is written, then max + argmax
-            a, _, _ = lyr.forward(a, M, 1, 1)
-            g, self.pn_idx = group_max_with_index(a, B, Np, lyr.cout)
-        self.pn_g = g
-        return g
-
-    def _lidar_backward(self, dg, sink):
-        if getattr(self, "pillar", None) is not None:                # dg: gradient of the NHWC canvas
-            self.pillar.backward(dg, sink)
-            return
-        B, Np, Cc = self.pn_geom
-        last = self.pn_layers[-1]
-        if self.pn_fused_max:
-            d = last.backward_from_groupmax(dg.contiguous(), self.pn_g, self.pn_idx, B, Np, sink)
+        self.cout = last.cout
+        self.fused = self.fuse_max and last.bn is not None and not bn_is_frozen(last.bn)
+        if self.fused:
+            self.g, self.idx = last.forward_groupmax(a, self.B, self.Np)
         else:
-            d = group_max_scatter(dg.contiguous(), self.pn_idx, B, Np, last.cout)
-            d, _ = last.backward(d, sink)
-        for lyr in reversed(self.pn_layers[:-1]):
+            a, _, _ = last.forward(a, M, 1, 1)
+            self.g, self.idx = group_max_with_index(a, self.B, self.Np, self.cout)
+        return self.g
+
+    def backward(self, dg, sink: GradSink) -> None:
+        last = self.layers[-1]
+        if self.fused:
+            d = last.backward_from_groupmax(dg.contiguous(), self.g, self.idx, self.B, self.Np, sink)
+        else:
+            d, _ = last.backward(group_max_scatter(dg.contiguous(), self.idx, self.B, self.Np, self.cout), sink)
+        for lyr in reversed(self.layers[:-1]):
             d, _ = lyr.backward(d, sink)
-        self.pn_first.backward(d, sink)
+        self.first.backward(d, sink)
 
-    # -- radar: shared per-sweep MLP + max, concat -> Linear (ref src/encoders.py:628-661) --------------------------------------
-    def _radar_forward(self, radars):
-        renc = self.m.radar_encoder
-        if renc.fusion_method not in ("concat", "max", "mean"):
-            raise ValueError(f"Unknown fusion method: {renc.fusion_method}")
-        enc = renc.radar_encoder
-        self.rad_sweeps = []
-        feats = []
+
+class RadarTape:
+    """MultiRadarEncoder (ref src/encoders.py:628-661): the shared RadarEncoder over every sweep (conv1..conv4, then the max over
+    the sweep's points), then concat -> fusion_fc, max or mean over the sweeps -> (B, cout) as a flat buffer.  One RadarEncoder
+    alone is fusion_method "max" over its single sweep, the identity."""
+
+    def __init__(self, enc, fusion_method: str, fusion_fc=None):
+        self.enc, self.method, self.fc = enc, fusion_method, fusion_fc
+
+    def forward(self, radars):
+        if self.method not in ("concat", "max", "mean"):
+            raise ValueError(f"Unknown fusion method: {self.method}")
+        self.sweeps, feats = [], []
         for pts in radars:
-            rows = enc._rows(pts)
-            B, Np, Cc = rows.shape
-            M = B * Np
-            first = PointFirstLayer(enc.conv1, enc.bn1)               # bn*: BatchNorm1d, or Identity under use_bn=False
-            a = first.forward(rows, M, Cc)
-            layers = []
-            for i in range(2, 5):
-                lyr = ConvBNLayer(getattr(enc, f"conv{i}"), _bn_or_none(getattr(enc, f"bn{i}")), True)
-                a, _, _ = lyr.forward(a, M, 1, 1)
-                layers.append(lyr)
-            feat = layers[-1].cout
-            g, idx = group_max_with_index(a, B, Np, feat)
-            feats.append(g[:B * feat].view(B, feat))
-            self.rad_sweeps.append((first, layers, idx, (B, Np, feat)))
+            sweep = PointMLPTape(self.enc, 4, fuse_max=False)
+            g = sweep.forward(pts)
+            feats.append(g[:sweep.B * sweep.cout].view(sweep.B, sweep.cout))
+            self.sweeps.append(sweep)
         per = torch.stack(feats, dim=1).contiguous()                      # (B, R, feat) -- layout copy only
-        B, R, feat = per.shape
-        self.rad_geom = (B, R, feat)
-        if renc.fusion_method == "max":                                   # ref src/encoders.py:654-655
-            out = _new(B * feat, per.device)
-            self.rad_fuse_idx = torch.empty(B * feat, dtype=torch.int32, device=per.device)
+        self.B, self.R, self.feat = B, R, feat = per.shape
+        if self.method == "concat":
+            if R * feat != self.fc.weight.shape[1]:
+                raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({B}x{R * feat} and "
+                                   f"{self.fc.weight.shape[1]}x{self.fc.weight.shape[0]})")
+            self.fc_layer = LinearLayer(self.fc, False)
+            self.cout = self.fc.weight.shape[0]
+            return self.fc_layer.forward(per.view(-1), B)
+        self.cout = feat
+        out = _new(B * feat, per.device)
+        if self.method == "max":                                          # ref src/encoders.py:654-655
+            self.fuse_idx = torch.empty(B * feat, dtype=torch.int32, device=per.device)
             gwork = torch.empty(L.group_max_idx_work_bytes(B, R, feat), dtype=torch.uint8, device=per.device)
-            L.group_max_idx(per, out, self.rad_fuse_idx, gwork, B, R, feat)
-            return out, B
-        if renc.fusion_method == "mean":                                  # ref src/encoders.py:656-657
-            out = _new(B * feat, per.device)
+            L.group_max_idx(per, out, self.fuse_idx, gwork, B, R, feat)
+        else:                                                             # mean, ref src/encoders.py:656-657
             L.cam_mean(per.view(-1), out, B, R, 1, feat)
-            return out, B
-        if R * feat != renc.fusion_fc.weight.shape[1]:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied ({B}x{R * feat} and "
-                               f"{renc.fusion_fc.weight.shape[1]}x{renc.fusion_fc.weight.shape[0]})")
-        self.rad_fc = LinearLayer(renc.fusion_fc, False)
-        return self.rad_fc.forward(per.view(-1), B), B
+        return out
 
-    def _radar_backward(self, dfeat, sink):
-        renc = self.m.radar_encoder
-        enc = renc.radar_encoder
-        B, R, feat = self.rad_geom
-        if renc.fusion_method == "max":            # the gradient goes to the sweep that held the maximum (first one on ties)
+    def backward(self, dfeat, sink: GradSink) -> None:
+        B, R, feat = self.B, self.R, self.feat
+        if self.method == "max":                   # the gradient goes to the sweep that held the maximum (first one on ties)
             dper = _zeros(B * R * feat, dfeat.device)
-            L.group_max_bwd(dfeat, self.rad_fuse_idx, dper, B, R, feat)
-        elif renc.fusion_method == "mean":         # every sweep receives dfeat / R
+            L.group_max_bwd(dfeat, self.fuse_idx, dper, B, R, feat)
+        elif self.method == "mean":                # every sweep receives dfeat / R
             dper = _new(B * R * feat, dfeat.device)
             L.cam_mean_bwd(dfeat, dper, B, R, 1, feat)
         else:
-            dper = self.rad_fc.backward(dfeat, sink)                        # [B][R][feat]
+            dper = self.fc_layer.backward(dfeat, sink)                      # [B][R][feat]
         for r in reversed(range(R)):
-            first, layers, idx, (B, Np, feat) = self.rad_sweeps[r]
-            dg = dper[:B * R * feat].view(B, R, feat)[:, r].contiguous().view(-1)
-            d = group_max_scatter(dg, idx, B, Np, feat)
-            for lyr in reversed(layers):
-                d, _ = lyr.backward(d, sink)
-            first.backward(d, sink)
+            self.sweeps[r].backward(dper[:B * R * feat].view(B, R, feat)[:, r].contiguous().view(-1), sink)
 
-    # -- fusion + head -----------------------------------------------------------------------------------------------------------
-    def forward(self, imgs, pts, radars):
-        m = self.m
-        fus = m.fusion
-        Sh, Sw, bc = fus.bev_h, fus.bev_w, fus.bev_channels
-        P = Sh * Sw
-        self.has_cam = m.use_camera and imgs is not None
-        self.has_lid = m.use_lidar and pts is not None
-        self.has_rad = m.use_radar and radars is not None
-        nmod = int(self.has_cam) + int(self.has_lid) + int(self.has_rad)
-        if nmod == 0:
-            raise ValueError("No modality features provided")
-        dev = imgs.device if self.has_cam else (pts.device if self.has_lid else radars[0].device)
-        cam_feat = lid_feat = rad_feat = None
-        if self.has_rad:
-            rad_feat, B = self._radar_forward(radars)
-        if self.has_cam:
-            cam_feat, (B, ncam, Hc, Wc) = self._camera_forward(imgs)
-        if self.has_lid:
-            lid_feat = self._lidar_forward(pts)
-            B = self.pn_geom[0]
-        fused = self._fusion_forward(cam_feat, (B, ncam, Hc, Wc) if self.has_cam else None, lid_feat, rad_feat, B, dev)
-        return self._head_forward(fused, B, Sh, Sw)
 
-    def _fusion_forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, dev):
-        """FlexibleBEVFusion under train-mode BatchNorm (ref src/fusion.py:209-297): NHWC camera features [B*ncam*Hc*Wc*C] with
-        cam_geom = (B, ncam, Hc, Wc), LiDAR (B, C_l) and radar (B, C_r) vectors -> fused NHWC map [B*Sh*Sw*bev_channels]."""
-        fus = self.m.fusion
-        Sh, Sw, bc = fus.bev_h, fus.bev_w, fus.bev_channels
+class FusionTape:
+    """FlexibleBEVFusion (ref src/fusion.py:209-297): NHWC camera features [B*ncam*Hc*Wc*C] with cam_geom = (B, ncam, Hc, Wc),
+    LiDAR (B, C_l) vectors or the PointPillars NHWC canvas on the fusion grid, radar (B, C_r) vectors -> fused NHWC map
+    [B*H*W*cout].  Each modality present fills one bev_channels slot of the concatenated map, in the order camera, LiDAR, radar."""
+
+    def __init__(self, fus):
+        self.fus = fus
+
+    def _slot(self, buf, slot):
+        """The [B*H*W][bev_channels] columns of `slot` in a concatenated NHWC map."""
+        bc, rows = self.fus.bev_channels, self.B * self.H * self.W
+        return buf[:rows * self.ccs].view(rows, self.ccs)[:, slot * bc:(slot + 1) * bc]
+
+    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B):
+        fus = self.fus
+        self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
+        Sh, Sw, bc = self.H, self.W, self.cout
         P = Sh * Sw
-        self.has_cam, self.has_lid, self.has_rad = cam_feat is not None, lid_feat is not None, rad_feat is not None
-        nmod = int(self.has_cam) + int(self.has_lid) + int(self.has_rad)
-        if nmod == 0:
-            raise ValueError("No modality features provided")
-        ccs = bc * nmod
+        self.has_cam, self.has_lid, self.has_rad = (f is not None for f in (cam_feat, lid_feat, rad_feat))
+        self.ccs = ccs = bc * (int(self.has_cam) + int(self.has_lid) + int(self.has_rad))
         if ccs != fus.bev_fusion[0].weight.shape[1]:
             raise RuntimeError(f"expected input to have {fus.bev_fusion[0].weight.shape[1]} channels, but got {ccs} channels instead")
+        dev = next(f for f in (cam_feat, lid_feat, rad_feat) if f is not None).device
         concat = _new(B * P * ccs, dev)
         slot = 0
-        self.B, self.ccs = B, ccs
-        self.S = (Sh, Sw)
         if self.has_cam:
             _, ncam, Hc, Wc = cam_geom
             Cc = fus.camera_proj[0].weight.shape[1]
@@ -1039,22 +1011,21 @@ class DetectorTape:
             self.cam_resize.forward(t2, B, Hc, Wc, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
             self.cam_slot = slot
             slot += 1
-        self.lid_pillars = self.has_lid and getattr(fus, "lidar_kind", "pointnet") == "pillars"
+        self.lid_pillars = self.has_lid and fus.lidar_kind == "pillars"
         if self.lid_pillars:
             # PointPillars: the NHWC canvas is on the fusion grid already -- lidar_bev's two conv+BN+ReLU, then the slice copy
             self.lb1 = ConvBNLayer(fus.lidar_bev[0], fus.lidar_bev[1], True)
             self.lb2 = ConvBNLayer(fus.lidar_bev[3], fus.lidar_bev[4], True)
             t1, _, _ = self.lb1.forward(lid_feat, B, Sh, Sw)
             t2, _, _ = self.lb2.forward(t1, B, Sh, Sw)
-            concat[:B * P * ccs].view(B * P, ccs)[:, slot * bc:(slot + 1) * bc] = t2[:B * P * bc].view(B * P, bc)
+            self._slot(concat, slot)[:] = t2[:B * P * bc].view(B * P, bc)
             self.lid_slot = slot
             slot += 1
         elif self.has_lid:
             s0 = fus.lidar_start_size
             self.li0 = LinearLayer(fus.lidar_init[0], True)
             O = fus.lidar_init[2].weight.shape[0]
-            ch = O // (s0 * s0)
-            self.li2 = LinearLayer(fus.lidar_init[2], False, (s0 * s0, ch))
+            self.li2 = LinearLayer(fus.lidar_init[2], False, (s0 * s0, O // (s0 * s0)))
             hid = self.li0.forward(lid_feat, B)
             grid0 = self.li2.forward(hid, B)
             self.lu1 = ConvBNLayer(fus.lidar_upsample[0], fus.lidar_upsample[1], True)
@@ -1064,15 +1035,8 @@ class DetectorTape:
             s1 = 2 * s0
             g2 = self.lid_up.forward(g1, B, s0, s0, self.lu1.cout, s1, s1)
             g3, _, _ = self.lu2.forward(g2, B, s1, s1)
-            self.lid_s1 = s1
-            self.lid_resize = None
-            if (s1, s1) == (Sh, Sw):
-                # copy into the concat slice (bilinear at identical size is the identity map)
-                self.lid_resize = Bilinear()
-                self.lid_resize.forward(g3, B, s1, s1, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
-            else:
-                self.lid_resize = Bilinear()
-                self.lid_resize.forward(g3, B, s1, s1, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
+            self.lid_resize = Bilinear()                                   # (the identity map when s1 == Sh == Sw)
+            self.lid_resize.forward(g3, B, s1, s1, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
             self.lid_slot = slot
             slot += 1
         if self.has_rad:
@@ -1084,138 +1048,151 @@ class DetectorTape:
             self.rr2 = ConvBNLayer(fus.radar_refine[3], fus.radar_refine[4], True)
             r1, _, _ = self.rr1.forward(r0, B, Sh, Sw)
             r2, _, _ = self.rr2.forward(r1, B, Sh, Sw)
-            concat[:B * P * ccs].view(B * P, ccs)[:, slot * bc:(slot + 1) * bc] = r2[:B * P * bc].view(B * P, bc)   # slice copy
+            self._slot(concat, slot)[:] = r2[:B * P * bc].view(B * P, bc)
             self.rad_slot = slot
             slot += 1
         self.f1 = ConvBNLayer(fus.bev_fusion[0], fus.bev_fusion[1], True)
-        self.f2 = ConvBNLayer(fus.bev_fusion[3], fus.bev_fusion[4], True)
+        self.f2 = ConvBNLayer(fus.bev_fusion[3], fus.bev_fusion[4], True)          # (the producer of the head's input)
         a1, _, _ = self.f1.forward(concat, B, Sh, Sw)
         fused, _, _ = self.f2.forward(a1, B, Sh, Sw)
         return fused
 
-    def _head_forward(self, fused, B, Sh, Sw):
-        """CenterNetHead (ref src/fusion.py:869-884): the five 3x3 branches as one conv (weights concatenated along Cout), then
-        the tail kernel."""
-        head = self.m.det_head
-        dev = fused.device
-        P = Sh * Sw
-        self.B = B
-        convs3 = [getattr(head, f"{n}_head")[0] for n in E.HEAD_BRANCHES]
-        convs1 = [getattr(head, f"{n}_head")[2] for n in E.HEAD_BRANCHES]
-        self.hc = convs3[0].weight.shape[0]
-        w3 = torch.cat([c.weight.detach() for c in convs3], 0)
-        b3 = torch.cat([c.bias.detach() for c in convs3], 0).contiguous()
-        self.head_w3 = w3
-        hid, _, _ = conv_raw(fused, w3.permute(0, 2, 3, 1).contiguous().view(-1), b3, B, Sh, Sw, w3.shape[1], w3.shape[0],
-                             3, 1, 1, relu=True)
-        self.head_in, self.head_hid = fused, hid
-        _trace_relu(hid, B * P, w3.shape[0])
-        self.cs = [c.weight.shape[0] for c in convs1]
-        self.w1 = torch.cat([c.weight.detach().reshape(c.weight.shape[0], self.hc) for c in convs1], 0).contiguous()
-        b1 = torch.cat([c.bias.detach() for c in convs1], 0).contiguous()
-        outs = [torch.empty(B, c, Sh, Sw, device=dev) for c in self.cs]
-        L.head_tail(hid, self.w1, b1, outs, B, P, self.hc, self.cs, self.cs[0])
-        self.outs = outs
-        self.S = (Sh, Sw)
-        return outs
-
-    def backward(self, douts: List[torch.Tensor], reducer=None) -> GradSink:
-        sink = GradSink(reducer)
-        dfused, pre_f2 = self._head_backward(douts, sink, self.f2)
-
-        def camera(dfeat):
-            sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
-            self._camera_backward(dfeat, sink)
-
-        self._fusion_backward(dfused, pre_f2, sink, on_radar=lambda d: self._radar_backward(d, sink),
-                              on_lidar=lambda d: self._lidar_backward(d, sink), on_camera=camera)
-        sink.finish()
-        return sink
-
-    def _head_backward(self, douts: List[torch.Tensor], sink: GradSink, f2=None):
-        """-> (gradient of the fused NHWC map, BatchNorm-backward partials for `f2` or None)."""
-        m = self.m
-        B, (Sh, Sw) = self.B, self.S
-        P = Sh * Sw
-        dev = self.outs[0].device
-        head = m.det_head
-        convs3 = [getattr(head, f"{n}_head")[0] for n in E.HEAD_BRANCHES]
-        convs1 = [getattr(head, f"{n}_head")[2] for n in E.HEAD_BRANCHES]
-        ctot = sum(self.cs)
-        dhid = _new(B * P * 5 * self.hc, dev)
-        dw1, db1 = _zeros(ctot * self.hc, dev), _zeros(ctot, dev)
-        gouts = [torch.zeros_like(o) if g is None else g.contiguous().float() for g, o in zip(douts, self.outs)]
-        L.head_tail_bwd(self.head_hid, self.w1, self.outs[0], gouts, dhid, dw1, db1, B, P, self.hc, self.cs, self.cs[0])
-        o = 0
-        for k, c1 in enumerate(convs1):
-            n = self.cs[k]
-            sink.add(c1.weight, dw1[o * self.hc:(o + n) * self.hc])
-            sink.add(c1.bias, db1[o:o + n])
-            o += n
-        # fused 3x3 head conv: ReLU mask, bias / weight / data gradients, split back per branch
-        c5 = 5 * self.hc
-        L.relu_mask(dhid, self.head_hid, B * P * c5)
-        db3 = colsum(dhid, B * P, c5)
-        cin = self.head_w3.shape[1]
-        dw3 = conv_wgrad(self.head_in, dhid, B, Sh, Sw, cin, c5, 3, 1, 1).permute(0, 3, 1, 2)
-        for k, c3 in enumerate(convs3):
-            sink.add(c3.weight, dw3[k * self.hc:(k + 1) * self.hc])
-            sink.add(c3.bias, db3[k * self.hc:(k + 1) * self.hc])
-        pre_f2 = None
-        if FUSE_BN_BACKWARD and f2 is not None and f2.can_take_fused_dy() and dgrad_can_fuse_bn(B, Sh, Sw, cin, c5, 3, 1, 1):
-            dfused, pre_f2 = conv_dgrad(dhid, self.head_w3, B, Sh, Sw, cin, c5, 3, 1, 1, bnb=f2.bnb_request())
-        else:
-            dfused = conv_dgrad(dhid, self.head_w3, B, Sh, Sw, cin, c5, 3, 1, 1)
-        return dfused, pre_f2
-
-    def _fusion_backward(self, dfused, pre_f2, sink: GradSink, on_radar=None, on_lidar=None, on_camera=None):
-        """Backward of `_fusion_forward`.  Each modality's input gradient (radar (B*C_r), LiDAR (B*C_l), camera NHWC) goes to its
-        callback as soon as it exists -- the detector continues into that encoder there -- and is returned as well."""
-        m = self.m
-        B, (Sh, Sw) = self.B, self.S
-        P = Sh * Sw
-        dev = dfused.device
-        drad = dlid = dfeat = None
-        da1, _, pre_f1 = self.f2.backward(dfused, sink, fuse_next=self.f1, pre=pre_f2)
+    def backward(self, dfused, sink: GradSink, pre=None, on_radar=None, on_lidar=None, on_camera=None):
+        """pre: BatchNorm-backward partials for f2 that arrive with dfused (or None).  Each modality's input gradient (radar (B*C_r),
+        LiDAR (B*C_l) or the pillar canvas, camera NHWC) goes to its callback as soon as it exists -- the detector continues into
+        that encoder there -- and is returned as well: (drad, dlid, dcam)."""
+        B, P, bc = self.B, self.H * self.W, self.cout
+        drad = dlid = dcam = None
+        da1, _, pre_f1 = self.f2.backward(dfused, sink, fuse_next=self.f1, pre=pre)
         dconcat, _ = self.f1.backward(da1, sink, pre=pre_f1)
-        bc = m.fusion.bev_channels
         if self.has_rad:
-            ccs = self.ccs
-            dr2 = dconcat[:B * P * ccs].view(B * P, ccs)[:, self.rad_slot * bc:(self.rad_slot + 1) * bc].contiguous().view(-1)
-            dr1, _ = self.rr2.backward(dr2, sink)
+            dr1, _ = self.rr2.backward(self._slot(dconcat, self.rad_slot).contiguous().view(-1), sink)
             dr0, _ = self.rr1.backward(dr1, sink)
             drv = torch.cat([colsum(dr0[b * P * bc:], P, bc) for b in range(B)])      # d(broadcast) = sum over cells
             drad = self.rp.backward(drv.contiguous(), sink)
             if on_radar is not None:
                 on_radar(drad)
-        if self.has_lid and self.lid_pillars:
-            ccs = self.ccs
-            dt2 = dconcat[:B * P * ccs].view(B * P, ccs)[:, self.lid_slot * bc:(self.lid_slot + 1) * bc].contiguous().view(-1)
-            dt1, _ = self.lb2.backward(dt2, sink)
+        if self.lid_pillars:
+            dt1, _ = self.lb2.backward(self._slot(dconcat, self.lid_slot).contiguous().view(-1), sink)
             dlid, _ = self.lb1.backward(dt1, sink)
-            if on_lidar is not None:
-                on_lidar(dlid)
         elif self.has_lid:
-            dg3 = self.lid_resize.backward(dconcat[self.lid_slot * bc:])
-            dg2, _ = self.lu2.backward(dg3, sink)
-            dg1 = self.lid_up.backward(dg2)
-            dgrid0, _ = self.lu1.backward(dg1, sink)
-            dhid_l = self.li2.backward(dgrid0, sink)
-            dlid = self.li0.backward(dhid_l, sink)
-            if on_lidar is not None:
-                on_lidar(dlid)
+            dg2, _ = self.lu2.backward(self.lid_resize.backward(dconcat[self.lid_slot * bc:]), sink)
+            dgrid0, _ = self.lu1.backward(self.lid_up.backward(dg2), sink)
+            dlid = self.li0.backward(self.li2.backward(dgrid0, sink), sink)
+        if dlid is not None and on_lidar is not None:
+            on_lidar(dlid)
         if self.has_cam:
-            dt2 = self.cam_resize.backward(dconcat[self.cam_slot * bc:])
-            dt1, _ = self.cp2.backward(dt2, sink)
-            dpooled, _ = self.cp1.backward(dt1, sink)
+            dt1, _ = self.cp2.backward(self.cam_resize.backward(dconcat[self.cam_slot * bc:]), sink)
+            dcam, _ = self.cp1.backward(dt1, sink)
             Bc, ncam, Pc, Cc = self.cam_pool_geom
-            dfeat = dpooled
             if ncam > 1:
-                dfeat = _new(Bc * ncam * Pc * Cc, dev)
-                L.cam_mean_bwd(dpooled, dfeat, Bc, ncam, Pc, Cc)
+                dpooled, dcam = dcam, _new(Bc * ncam * Pc * Cc, dfused.device)
+                L.cam_mean_bwd(dpooled, dcam, Bc, ncam, Pc, Cc)
             if on_camera is not None:
-                on_camera(dfeat)
-        return drad, dlid, dfeat
+                on_camera(dcam)
+        return drad, dlid, dcam
+
+
+class HeadTape:
+    """CenterNetHead (ref src/fusion.py:869-884) on an NHWC map [B*H*W*Cin]: the five 3x3 branches as one conv (engine.head_weights,
+    rebuilt every step because the weights change), then the tail kernel -> five NCHW outputs."""
+
+    def __init__(self, head):
+        self.head = head
+
+    def forward(self, x, B, H, W):
+        hw = self.weights = E.head_weights(self.head)
+        self.x, self.B, self.H, self.W, self.hc = x, B, H, W, hw.hc
+        P = H * W
+        hid, _, _ = conv_raw(x, hw.w3.permute(0, 2, 3, 1).contiguous().view(-1), hw.b3, B, H, W, hw.w3.shape[1], hw.w3.shape[0],
+                             3, 1, 1, relu=True)
+        self.hid = hid
+        _trace_relu(hid, B * P, hw.w3.shape[0])
+        self.outs = [torch.empty(B, c, H, W, device=x.device) for c in hw.cs]
+        L.head_tail(hid, hw.w1, hw.b1, self.outs, B, P, hw.hc, hw.cs, hw.cs[0])
+        return self.outs
+
+    def backward(self, douts: List[torch.Tensor], sink: GradSink, fuse_next: Optional[ConvBNLayer] = None):
+        """-> (gradient of the input NHWC map, BatchNorm-backward partials for `fuse_next`, the layer that produced the input, or
+        None)."""
+        hw, B, H, W, hc = self.weights, self.B, self.H, self.W, self.hc
+        P = H * W
+        dev = self.outs[0].device
+        c5, cin = hw.w3.shape[0], hw.w3.shape[1]
+        ctot = sum(hw.cs)
+        dhid = _new(B * P * c5, dev)
+        dw1, db1 = _zeros(ctot * hc, dev), _zeros(ctot, dev)
+        gouts = [torch.zeros_like(o) if g is None else g.contiguous().float() for g, o in zip(douts, self.outs)]
+        L.head_tail_bwd(self.hid, hw.w1, self.outs[0], gouts, dhid, dw1, db1, B, P, hc, hw.cs, hw.cs[0])
+        o = 0
+        for c1, n in zip(hw.convs1, hw.cs):
+            sink.add(c1.weight, dw1[o * hc:(o + n) * hc])
+            sink.add(c1.bias, db1[o:o + n])
+            o += n
+        # fused 3x3 head conv: ReLU mask, bias / weight / data gradients, split back per branch
+        L.relu_mask(dhid, self.hid, B * P * c5)
+        db3 = colsum(dhid, B * P, c5)
+        dw3 = conv_wgrad(self.x, dhid, B, H, W, cin, c5, 3, 1, 1).permute(0, 3, 1, 2)
+        for k, c3 in enumerate(hw.convs3):
+            sink.add(c3.weight, dw3[k * hc:(k + 1) * hc])
+            sink.add(c3.bias, db3[k * hc:(k + 1) * hc])
+        if FUSE_BN_BACKWARD and fuse_next is not None and fuse_next.can_take_fused_dy() and dgrad_can_fuse_bn(B, H, W, cin, c5, 3, 1, 1):
+            return conv_dgrad(dhid, hw.w3, B, H, W, cin, c5, 3, 1, 1, bnb=fuse_next.bnb_request())
+        return conv_dgrad(dhid, hw.w3, B, H, W, cin, c5, 3, 1, 1), None
+
+
+# ---- the detector ------------------------------------------------------------------------------------------------------------------
+
+class DetectorTape:
+    """FlexibleMultiModal3DDetector (bev + centernet) as a composition of module tapes: the encoders of the modalities present, in
+    the order radar, camera, LiDAR (RELU_TRACE follows it), then fusion and head.  The backward walks them in reverse and marks
+    where gradients become final for the data-parallel all-reduce (sink.ready())."""
+
+    def __init__(self, model):
+        self.m = model
+
+    def forward(self, imgs, pts, radars):
+        m = self.m
+        has_cam = m.use_camera and imgs is not None
+        has_lid = m.use_lidar and pts is not None
+        has_rad = m.use_radar and radars is not None
+        if not (has_cam or has_lid or has_rad):
+            raise ValueError("No modality features provided")
+        self.radar = self.camera = self.lidar = None
+        cam_feat = cam_geom = lid_feat = rad_feat = None
+        if has_rad:
+            renc = m.radar_encoder
+            self.radar = RadarTape(renc.radar_encoder, renc.fusion_method, getattr(renc, "fusion_fc", None))
+            rad_feat = self.radar.forward(radars)
+            B = self.radar.B
+        if has_cam:
+            self.camera = CameraTape(m.camera_encoder)
+            cam_feat = self.camera.forward(imgs)
+            B = self.camera.B
+            cam_geom = (B, self.camera.n, self.camera.H, self.camera.W)
+        if has_lid:
+            if getattr(m.lidar_encoder, "is_pillars", False):              # PointPillars: NHWC fp32 canvas on the BEV grid
+                _no_input_grad(pts, "the LiDAR points")
+                self.lidar = PillarPFNLayer(m.lidar_encoder)
+            else:
+                self.lidar = PointMLPTape(m.lidar_encoder, 5, fuse_max=True)
+            lid_feat = self.lidar.forward(pts)
+            B = self.lidar.B
+        self.fusion = FusionTape(m.fusion)
+        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B)
+        self.head = HeadTape(m.det_head)
+        return self.head.forward(fused, B, self.fusion.H, self.fusion.W)
+
+    def backward(self, douts: List[torch.Tensor], sink: GradSink) -> list:
+        dfused, pre_f2 = self.head.backward(douts, sink, fuse_next=self.fusion.f2)
+
+        def camera(dfeat):
+            sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
+            self.camera.backward(dfeat, sink)
+
+        self.fusion.backward(dfused, sink, pre_f2, on_radar=lambda d: self.radar.backward(d, sink),
+                             on_lidar=lambda d: self.lidar.backward(d, sink), on_camera=camera)
+        return [None, None, None]
 
 
 _GRAD_REDUCER = None
@@ -1228,31 +1205,38 @@ def set_grad_reducer(reducer) -> None:
     _GRAD_REDUCER = reducer
 
 
-class _DetectorTrainFn(torch.autograd.Function):
+class _TapeFn(torch.autograd.Function):
+    """The autograd node of every tape path: the detector, or one module used on its own.  `fwd(*inputs)` runs the tape's forward
+    and returns its outputs; `bwd(douts, sink)` runs its backward and returns one gradient per input (None where there is none).
+    `reducer`: the GradReducer the sink hands final gradients to (the detector's), or None.  `what` names the module in errors."""
+
     @staticmethod
-    def forward(ctx, model, imgs, pts, radars, *params):
-        tape = DetectorTape(model)
+    def forward(ctx, what, fwd, bwd, reducer, n_in, *tensors):
         with torch.no_grad():
-            outs = tape.forward(imgs, pts, radars)
-        ctx.tape, ctx.params = tape, params
+            outs = fwd(*tensors[:n_in])
+        ctx.what, ctx.bwd, ctx.reducer, ctx.n_in, ctx.params = what, bwd, reducer, n_in, tensors[n_in:]
         # The tape keeps its own tensors; autograd gets fresh aliases.  Returning the tape's objects would close a
-        # reference cycle through C++ (output -> grad_fn -> ctx.tape -> output) that the garbage collector cannot
+        # reference cycle through C++ (output -> grad_fn -> ctx -> tape -> output) that the garbage collector cannot
         # see: every step's activations (~11 GiB at config 4) would stay allocated for ever.
         return tuple(o.detach() for o in outs)
 
     @staticmethod
     def backward(ctx, *douts):
-        if ctx.tape is None:
-            raise RuntimeError("Trying to backward through the detector a second time: its saved activations were freed")
+        if ctx.bwd is None:
+            raise RuntimeError(f"Trying to backward through the {ctx.what} a second time: its saved activations were freed")
         global _ZPOOL
         with torch.no_grad():
             pool = _ZPOOL = _ZeroPool(next(g for g in douts if g is not None).device)
             try:
-                sink = ctx.tape.backward(list(douts), _GRAD_REDUCER)
+                sink = GradSink(ctx.reducer)
+                dins = ctx.bwd(list(douts), sink)
+                sink.finish()
             finally:
                 _ZPOOL = None
-        ctx.tape = None                                   # activations are dead now: hand them back to the allocator
-        return (None, None, None, None, *_param_grads(sink, ctx.params, pool))
+        ctx.bwd = None                                    # the tape's activations are dead now: hand them back to the allocator
+        need = ctx.needs_input_grad[5:5 + ctx.n_in]
+        dins = [_owned(d, pool) if (n and d is not None) else None for d, n in zip(dins, need)]
+        return (None,) * 5 + (*dins, *_param_grads(sink, ctx.params, pool))
 
 
 def _owned(g, pool):
@@ -1272,6 +1256,10 @@ def _param_grads(sink: GradSink, params, pool) -> list:
     return grads
 
 
+def _trainable(module: nn.Module) -> list:
+    return [p for p in module.parameters() if p.requires_grad]
+
+
 def any_bn_training(module: nn.Module) -> bool:
     return any(isinstance(m, nn.modules.batchnorm._BatchNorm) and m.training for m in module.modules())
 
@@ -1284,42 +1272,13 @@ def wants_train_path(module: nn.Module) -> bool:
 
 
 def detector_train_forward(model, imgs, pts, radars) -> Dict[str, torch.Tensor]:
-    params = [p for p in model.parameters() if p.requires_grad]
-    outs = _DetectorTrainFn.apply(model, imgs, pts, radars, *params)
+    tape = DetectorTape(model)
+    outs = _TapeFn.apply("detector", tape.forward, tape.backward, _GRAD_REDUCER, 3, imgs, pts, radars, *_trainable(model))
     return dict(zip(E.HEAD_BRANCHES, outs))
 
 
 # ---- stand-alone modules under train-mode BatchNorm (ref src/encoders.py:792-846 calls freshly built encoders, i.e. in train mode) ----
-
-class _ModuleTrainFn(torch.autograd.Function):
-    """One encoder / fusion / head module used outside the detector: the matching part of DetectorTape.
-    `run_fwd()` -> (tape, outputs); `run_bwd(tape, douts, sink)` -> one gradient per tensor input (None where there is none)."""
-
-    @staticmethod
-    def forward(ctx, run_fwd, run_bwd, n_in, *tensors):
-        with torch.no_grad():
-            tape, outs = run_fwd()
-        ctx.tape, ctx.run_bwd, ctx.n_in, ctx.params = tape, run_bwd, n_in, tensors[n_in:]
-        return tuple(o.detach() for o in outs)                    # fresh aliases: see _DetectorTrainFn.forward
-
-    @staticmethod
-    def backward(ctx, *douts):
-        if ctx.tape is None:
-            raise RuntimeError("Trying to backward through the module a second time: its saved activations were freed")
-        global _ZPOOL
-        with torch.no_grad():
-            pool = _ZPOOL = _ZeroPool(next(g for g in douts if g is not None).device)
-            try:
-                sink = GradSink(None)
-                dins = ctx.run_bwd(ctx.tape, list(douts), sink)
-                sink.finish()
-            finally:
-                _ZPOOL = None
-        ctx.tape = None
-        need = ctx.needs_input_grad[3:3 + ctx.n_in]
-        dins = [_owned(d, pool) if (n and d is not None) else None for d, n in zip(dins, need)]
-        return (None, None, None, *dins, *_param_grads(sink, ctx.params, pool))
-
+# Each checks its inputs, builds its tape and converts between the reference's layouts and the tape's flat NHWC buffers.
 
 def _no_input_grad(x, what: str) -> None:
     if isinstance(x, torch.Tensor) and x.requires_grad:
@@ -1332,27 +1291,26 @@ def _nhwc(x: torch.Tensor) -> torch.Tensor:
     return E.to_nhwc(x.float().contiguous()).float().reshape(-1)
 
 
+def _flat(x: torch.Tensor) -> torch.Tensor:
+    return x.contiguous().float().reshape(-1)
+
+
 def camera_encoder_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
     """ResNetCameraEncoder.forward under train-mode BatchNorm (ref src/encoders.py:133-172): batch statistics, running buffers
     updated, gradients for every trainable parameter."""
     _no_input_grad(x, "the camera images")
-    five_d = x.dim() == 5
-    geom = {}
+    tape = CameraTape(enc)
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(camera_encoder=enc))
-        feat, (B, n, h, w) = tape._camera_forward(x)
-        geom["g"] = (B, n, h, w)
-        return tape, (E.to_nchw(feat, B * n, tape.proj.cout, h, w),)
+    def fwd(x):
+        feat = tape.forward(x)
+        return (E.to_nchw(feat, tape.B * tape.n, tape.cout, tape.H, tape.W),)
 
-    def bwd(tape, douts, sink):
-        B, n, h, w = geom["g"]
-        tape._camera_backward(_nhwc(douts[0].reshape(B * n, tape.proj.cout, h, w)), sink)
+    def bwd(douts, sink):
+        tape.backward(_nhwc(douts[0].reshape(tape.B * tape.n, tape.cout, tape.H, tape.W)), sink)
         return [None]
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in enc.parameters() if p.requires_grad])
-    B, n, h, w = geom["g"]
-    return out.view(B, n, out.shape[1], h, w) if five_d else out
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(enc))
+    return out.view(tape.B, tape.n, tape.cout, tape.H, tape.W) if x.dim() == 5 else out
 
 
 def pointnet_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
@@ -1361,36 +1319,32 @@ def pointnet_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
     if getattr(enc, "return_point_features", False):
         raise L.BevfError("training: PointNetLiDAREncoder(return_point_features=True) has no train-mode path on the device "
                           "(the detector uses the global feature, ref src/fusion.py:1105-1108); call .eval() for per-point features")
+    tape = PointMLPTape(enc, 5, fuse_max=True)
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(lidar_encoder=enc))
-        g = tape._lidar_forward(x)
-        B, feat = tape.pn_geom[0], tape.pn_layers[-1].cout
-        return tape, (g.reshape(-1)[:B * feat].view(B, feat),)
+    def fwd(x):
+        return (tape.forward(x)[:tape.B * tape.cout].view(tape.B, tape.cout),)
 
-    def bwd(tape, douts, sink):
-        tape._lidar_backward(douts[0].contiguous().float().reshape(-1), sink)
+    def bwd(douts, sink):
+        tape.backward(_flat(douts[0]), sink)
         return [None]
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in enc.parameters() if p.requires_grad])
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(enc))
     return out
 
 
 def pillar_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
     """PillarLiDAREncoder.forward under train-mode BatchNorm -> canvas (B, pfn_channels, bev_h, bev_w), gradients for pfn.*."""
     _no_input_grad(x, "the LiDAR points")
-    Cout, H, W = enc.pfn_channels, enc.bev_h, enc.bev_w
+    tape = PillarPFNLayer(enc)
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(lidar_encoder=enc))
-        canvas = tape._lidar_forward(x)
-        return tape, (E.to_nchw(canvas, tape.pillar.B, Cout, H, W),)
+    def fwd(x):
+        return (E.to_nchw(tape.forward(x), tape.B, enc.pfn_channels, enc.bev_h, enc.bev_w),)
 
-    def bwd(tape, douts, sink):
-        tape._lidar_backward(_nhwc(douts[0]), sink)
+    def bwd(douts, sink):
+        tape.backward(_nhwc(douts[0]), sink)
         return [None]
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in enc.parameters() if p.requires_grad])
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(enc))
     return out
 
 
@@ -1402,20 +1356,20 @@ def vfe_train_forward(layer, x: torch.Tensor) -> torch.Tensor:
     if Cc > 16:
         raise L.BevfError(f"training: VFELayer(in_channels={Cc}) has a train-mode path for point features of <= 16 channels only")
     G, M = B * Nv, B * Nv * P
-    lin = SimpleNamespace(weight=layer.linear.weight, bias=layer.linear.bias)      # same Parameters: gradients land on them
+    first = PointFirstLayer(layer.linear, layer.bn)               # reads only .weight / .bias of the Linear
+    idx = None
 
-    def fwd():
-        first = PointFirstLayer(lin, layer.bn)
+    def fwd(x):
+        nonlocal idx
         a = first.forward(x.detach().float().contiguous().view(M, Cc), M, Cc)
         g, idx = group_max_with_index(a, G, P, first.c0)
-        return (first, idx), (g[:G * first.c0].view(B, Nv, first.c0),)
+        return (g[:G * first.c0].view(B, Nv, first.c0),)
 
-    def bwd(tape, douts, sink):
-        first, idx = tape
-        first.backward(group_max_scatter(douts[0].contiguous().float().reshape(-1), idx, G, P, first.c0), sink)
+    def bwd(douts, sink):
+        first.backward(group_max_scatter(_flat(douts[0]), idx, G, P, first.c0), sink)
         return [None]
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in layer.parameters() if p.requires_grad])
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(layer))
     return out
 
 
@@ -1426,20 +1380,17 @@ def radar_train_forward(enc, radar_list) -> torch.Tensor:
     sweeps = [radar_list] if single else list(radar_list)
     for r in sweeps:
         _no_input_grad(r, "the radar points")
-    # one encoder alone = the shared encoder over one sweep, "max" over that single sweep being the identity
-    renc = SimpleNamespace(radar_encoder=enc, fusion_method="max") if single else enc
+    tape = (RadarTape(enc, "max") if single
+            else RadarTape(enc.radar_encoder, enc.fusion_method, getattr(enc, "fusion_fc", None)))
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(radar_encoder=renc))
-        out, B = tape._radar_forward(sweeps)
-        feat = tape.rad_geom[2] if renc.fusion_method != "concat" else renc.fusion_fc.weight.shape[0]
-        return tape, (out.reshape(-1)[:B * feat].view(B, feat),)
+    def fwd(*pts):
+        return (tape.forward(pts).reshape(-1)[:tape.B * tape.cout].view(tape.B, tape.cout),)
 
-    def bwd(tape, douts, sink):
-        tape._radar_backward(douts[0].contiguous().float().reshape(-1), sink)
+    def bwd(douts, sink):
+        tape.backward(_flat(douts[0]), sink)
         return [None] * len(sweeps)
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, len(sweeps), *sweeps, *[p for p in enc.parameters() if p.requires_grad])
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, len(sweeps), *sweeps, *_trainable(enc))
     return out
 
 
@@ -1452,14 +1403,14 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
     first = next((t for t in (cam, lid, rad) if t is not None), None)
     if first is None:
         raise ValueError("No modality features provided")
-    B, dev = first.shape[0], first.device
-    pillars = getattr(fus, "lidar_kind", "pointnet") == "pillars"
+    B = first.shape[0]
+    pillars = fus.lidar_kind == "pillars"
     geom = None
     if cam is not None:
         geom = (B, cam.shape[1], cam.shape[3], cam.shape[4]) if cam.dim() == 5 else (B, 1, cam.shape[2], cam.shape[3])
+    tape = FusionTape(fus)
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(fusion=fus))
+    def fwd(cam, lid, rad):
         cam_nhwc = None
         if cam is not None:
             _, n, h, w = geom
@@ -1467,16 +1418,14 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
         lid_in = None if lid is None else lid.detach().float().contiguous()
         if lid_in is not None and pillars:                             # NCHW pillar canvas -> NHWC
             lid_in = _nhwc(lid_in)
-        fused = tape._fusion_forward(cam_nhwc, geom, lid_in,
-                                     None if rad is None else rad.detach().float().contiguous(), B, dev)
-        return tape, (E.to_nchw(fused, B, fus.bev_channels, fus.bev_h, fus.bev_w),)
+        fused = tape.forward(cam_nhwc, geom, lid_in, None if rad is None else rad.detach().float().contiguous(), B)
+        return (E.to_nchw(fused, B, tape.cout, tape.H, tape.W),)
 
-    def bwd(tape, douts, sink):
-        drad, dlid, dcam = tape._fusion_backward(_nhwc(douts[0]), None, sink)
+    def bwd(douts, sink):
+        drad, dlid, dcam = tape.backward(_nhwc(douts[0]), sink)
         if dcam is not None:
             _, n, h, w = geom
-            Cc = tape.cam_pool_geom[3]
-            dcam = E.to_nchw(dcam, B * n, Cc, h, w).view(cam.shape)
+            dcam = E.to_nchw(dcam, B * n, fus.camera_proj[0].weight.shape[1], h, w).view(cam.shape)
         if dlid is not None and pillars:
             dlid = E.to_nchw(dlid, B, lid.shape[1], lid.shape[2], lid.shape[3])
         elif dlid is not None:
@@ -1485,26 +1434,27 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
             drad = drad.reshape(-1)[:rad.numel()].view(rad.shape)
         return [dcam, dlid, drad]
 
-    (out,) = _ModuleTrainFn.apply(fwd, bwd, 3, cam, lid, rad, *[p for p in fus.parameters() if p.requires_grad])
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 3, cam, lid, rad, *_trainable(fus))
     return out
 
 
 def head_train_forward(head, x: torch.Tensor) -> Dict[str, torch.Tensor]:
     """CenterNetHead.forward with a gradient path (ref src/fusion.py:869-884; the head has no BatchNorm, so train and eval mode
     compute the same values): gradients for its parameters and for the BEV map `x` (B, C, H, W)."""
-    B, _, Sh, Sw = x.shape
+    B, Cin, H, W = x.shape
+    tape = HeadTape(head)
 
-    def fwd():
-        tape = DetectorTape(SimpleNamespace(det_head=head))
-        tape.S = (Sh, Sw)
-        return tape, tuple(tape._head_forward(_nhwc(x.detach()), B, Sh, Sw))
+    def fwd(x):
+        return tuple(tape.forward(_nhwc(x.detach()), B, H, W))
 
-    def bwd(tape, douts, sink):
-        dfused, _ = tape._head_backward(douts, sink, None)
-        return [E.to_nchw(dfused, B, x.shape[1], Sh, Sw)]
+    def bwd(douts, sink):
+        dx, _ = tape.backward(douts, sink)
+        return [E.to_nchw(dx, B, Cin, H, W)]
 
-    outs = _ModuleTrainFn.apply(fwd, bwd, 1, x, *[p for p in head.parameters() if p.requires_grad])
+    outs = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
     return dict(zip(E.HEAD_BRANCHES, outs))
+
+
 
 
 # ---- loss with gradient ------------------------------------------------------------------------------------------------------------

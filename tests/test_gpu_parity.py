@@ -302,7 +302,7 @@ def test_lidar_resize_extension_128(gpu):
 
 
 def test_modules_without_a_train_mode_path_refuse_it(gpu):
-    """Train-mode BatchNorm runs through training.DetectorTape for the detector and its module kinds
+    """Train-mode BatchNorm runs through training.DetectorTape for the detector and the module tapes for its module kinds
     (tests/test_gpu_standalone_train.py, mixed-mode BatchNorm included); a VFELayer wider than the small-K point kernel refuses loudly."""
     v = encoders.VFELayer(32, 32).cuda().train()
     with pytest.raises(RuntimeError, match="<= 16 channels"):

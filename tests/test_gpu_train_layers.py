@@ -1,8 +1,8 @@
 """Every layer of the training tape at its BASELINE config-4 shape (per-GPU batch 8, 6 x 448x800 images, 35 000 points,
 BEV 50^2) against a float64 reference of the same operation.
 
-The layers are the product's own classes (training.StemBlock, ConvBNLayer, PointFirstLayer, LinearLayer, Bilinear, the
-head of DetectorTape, CenterNetLoss) on the real submodules of the config-4 detector.  The reference is torch's own
+The layers are the product's own classes (training.StemBlock, ConvBNLayer, PointFirstLayer, LinearLayer, Bilinear,
+HeadTape, CenterNetLoss) on the real submodules of the config-4 detector.  The reference is torch's own
 float64 operators on the GPU (F.conv2d / F.batch_norm / F.linear / F.interpolate and autograd; MIOpen has no float64
 path, so torch runs im2col + BLAS there) -- pinned against the CPU by test_float64_reference_on_the_gpu_matches_the_cpu.
 
@@ -783,21 +783,21 @@ def test_camera_mean(gpu, product_flags):
 
 # ---- head and loss --------------------------------------------------------------------------------------------------------------
 
-def test_head_forward_backward(gpu, product_flags):
+def test_head_tape_forward_backward(gpu, product_flags):
     """The fused 3x3 head conv (256 -> 5 x 64, bias, ReLU) and the five 1x1 tails with the heatmap sigmoid (head_tail), forward and
     backward, at B = 8 on the 50^2 grid."""
     m = fresh_bn()
     head = m.det_head
     Cin, P = 256, BEV * BEV
     x = snormal((B, Cin, BEV, BEV), 101).clamp_min(0)
-    tape = training.DetectorTape(SimpleNamespace(det_head=head))
-    outs = [o.clone() for o in tape._head_forward(nhwc(x), B, BEV, BEV)]
+    tape = training.HeadTape(head)
+    outs = [o.clone() for o in tape.forward(nhwc(x), B, BEV, BEV)]
     douts = [snormal(tuple(o.shape), 102 + k) for k, o in enumerate(outs)]
     c5 = 5 * tape.hc
     torch.cuda.synchronize()
-    hid_dev = from_nhwc(tape.head_hid, B, c5, BEV, BEV)
+    hid_dev = from_nhwc(tape.hid, B, c5, BEV, BEV)
     sink = training.GradSink()
-    dfused, pre = tape._head_backward(douts, sink, None)
+    dfused, pre = tape.backward(douts, sink)
     assert pre is None
     torch.cuda.synchronize()
 

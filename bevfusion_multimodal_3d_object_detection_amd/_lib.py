@@ -198,6 +198,10 @@ SIGNATURES = {
     "bevf_smallk_wgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_grad_norm_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "bevf_adamw_step_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
+    "bevf_csr_gather_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+                            + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_csr_gather_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+                             + [C.c_int] * 3 + [C.c_void_p]),
 }
 
 
@@ -1066,3 +1070,21 @@ def lidar_filter_pad(points, out, count, work, choice, N: int, Cc: int, max_poin
           work=(work, N * Cc + -(-N // 1024)), choice=(choice, max_points))
     _call("bevf_lidar_filter_pad_f32", _pc(points), _pc(out), _pc(count, torch.int32), _pc(work), _pc(choice, torch.int64), N, Cc,
           max_points, (C.c_float * 6)(*pc_range))
+
+
+def csr_gather(row_ptr, col, w, nrows: int, ncols: int, x, x_bs: int, x_cs: int, y, y_bs: int, y_cs: int, B: int, C: int) -> None:
+    """y[b][r][0:C] = sum_e w[e] * x[b][col[e]][0:C] over CSR row r (bevf_csr_gather): the camera -> BEV projection and, on the
+    transposed table, its backward.  x / y in the same storage dtype (fp32 or bf16), batch strides x_bs / y_bs and row strides
+    x_cs / y_cs in elements; ncols = the table's column count (every col < ncols, checked when the table is built)."""
+    if row_ptr.numel() != nrows + 1:
+        raise BevfError(f"csr_gather: row_ptr holds {row_ptr.numel()} elements, needs nrows + 1 = {nrows + 1}")
+    nnz = col.numel()
+    if w.numel() != nnz:
+        raise BevfError(f"csr_gather: {nnz} columns but {w.numel()} weights")
+    _need("csr_gather", x=(x, (B - 1) * x_bs + _strided(ncols, C, x_cs)), y=(y, (B - 1) * y_bs + _strided(nrows, C, y_cs)))
+    if y.dtype != x.dtype:
+        raise BevfError(f"csr_gather: x is {x.dtype}, y is {y.dtype}")
+    if x.is_cuda and y.is_cuda and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("csr_gather: x and y share storage")
+    _call("bevf_csr_gather_" + _sfx(x), _pc(row_ptr, torch.int32), _pc(col, torch.int32) if nnz else None,
+          _pc(w) if nnz else None, nrows, _p(x, x.dtype), x_bs, x_cs, _p(y, y.dtype), y_bs, y_cs, B, C)

@@ -1,0 +1,280 @@
+"""Camera calibration and the camera -> BEV projection table of the opt-in `camera_view_transform: 'project'` branch.
+
+Parameter-free projection in the style of Simple-BEV (Harley et al. 2022): every BEV cell of the fusion grid takes
+`num_heights` points above its centre, projects each into every camera with a fixed calibration, samples the camera feature
+map bilinearly there and averages over the samples that hit an image.  With a static rig the whole lift is a sparse matrix
+over (BEV cell) x (camera feature pixel), built here once on the host in fp64 and applied on the device by
+bevf_csr_gather (csrc/camera_bev.hip) -- the forward on the cell table, the backward on its exact transpose.
+
+One rig per module: calibration that changes from frame to frame is not supported (the table would have to be rebuilt per
+frame).  DESIGN.md 3.2d.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+# the reference's camera order (ref src/train_detect.py:134-135): the order of the camera axis of the image input
+CAM_ORDER = ("CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_FRONT_LEFT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_BACK_RIGHT")
+VIEW_TRANSFORMS = ("mean", "project")
+DEFAULT_NUM_HEIGHTS = 8
+DEFAULT_MIN_DEPTH = 0.1
+
+
+def quat_to_matrix(q: Sequence[float]) -> np.ndarray:
+    """Unit quaternion (w, x, y, z) -- the nuScenes / pyquaternion convention -> 3x3 rotation (fp64, normalised first)."""
+    w, x, y, z = (float(v) for v in q)
+    n = math.sqrt(w * w + x * x + y * y + z * z)
+    if n == 0.0:
+        raise ValueError("camera rig: zero quaternion")
+    w, x, y, z = w / n, x / n, y / n, z / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], dtype=np.float64)
+
+
+def sensor_to_frame(calibrated_sensor: Dict) -> np.ndarray:
+    """{'translation': [3], 'rotation': [w, x, y, z]} (sensor -> ego) -> 4x4 fp64."""
+    T = np.eye(4, dtype=np.float64)
+    T[:3, :3] = quat_to_matrix(calibrated_sensor["rotation"])
+    T[:3, 3] = np.asarray(calibrated_sensor["translation"], dtype=np.float64)
+    return T
+
+
+@dataclass(frozen=True)
+class CameraRig:
+    """A fixed multi-camera calibration.
+
+    image_size: (H, W) of the images the intrinsics refer to (the feature map of any resolution covers the same field of view);
+    names: camera names in the order of the input's camera axis; K: (ncam, 3, 3) intrinsics; cam_to_bev: (ncam, 4, 4) from the
+    camera frame (OpenCV: x right, y down, z forward) to the frame of the LiDAR points, the boxes and point_cloud_range."""
+    image_size: Tuple[int, int]
+    names: Tuple[str, ...]
+    K: np.ndarray
+    cam_to_bev: np.ndarray
+
+    def __post_init__(self):
+        K = np.asarray(self.K, dtype=np.float64).reshape(-1, 3, 3)
+        T = np.asarray(self.cam_to_bev, dtype=np.float64).reshape(-1, 4, 4)
+        if K.shape[0] != len(self.names) or T.shape[0] != len(self.names) or not self.names:
+            raise ValueError(f"camera rig: {len(self.names)} names, {K.shape[0]} intrinsics, {T.shape[0]} extrinsics")
+        H, W = (int(v) for v in self.image_size)
+        if H <= 0 or W <= 0:
+            raise ValueError(f"camera rig: bad image_size {self.image_size}")
+        object.__setattr__(self, "K", K)
+        object.__setattr__(self, "cam_to_bev", T)
+        object.__setattr__(self, "image_size", (H, W))
+        object.__setattr__(self, "names", tuple(self.names))
+
+    @property
+    def num_cameras(self) -> int:
+        return len(self.names)
+
+    def key(self) -> Tuple:
+        """Hashable identity of the calibration (table cache key)."""
+        return (self.image_size, self.names, self.K.tobytes(), self.cam_to_bev.tobytes())
+
+    @classmethod
+    def from_info(cls, info: Dict, cam_order: Sequence[str] = CAM_ORDER, image_size: Tuple[int, int] = (900, 1600)) -> "CameraRig":
+        """From one converted-data info dict (ref src/data_converter.py:100-151): cams[name]['calibrated_sensor'] is camera -> ego
+        ({translation, rotation (w, x, y, z), camera_intrinsic}), lidar_calibrated_sensor is LiDAR -> ego; the boxes and points are in
+        the LiDAR frame, so cam_to_bev = (lidar -> ego)^-1 . (camera -> ego).  image_size: the size the intrinsics refer to (nuScenes:
+        900 x 1600)."""
+        lidar_to_ego = sensor_to_frame(info["lidar_calibrated_sensor"])
+        ego_to_lidar = np.linalg.inv(lidar_to_ego)
+        Ks, Ts = [], []
+        for name in cam_order:
+            cs = info["cams"][name]["calibrated_sensor"]
+            Ks.append(np.asarray(cs["camera_intrinsic"], dtype=np.float64).reshape(3, 3))
+            Ts.append(ego_to_lidar @ sensor_to_frame(cs))
+        return cls(tuple(image_size), tuple(cam_order), np.stack(Ks), np.stack(Ts))
+
+    @classmethod
+    def from_dict(cls, d: Dict) -> "CameraRig":
+        """The config form: {image_size: [H, W], cameras: [{name, K: 3x3, cam_to_bev: 4x4}, ...]} (to_dict's output)."""
+        cams = d["cameras"]
+        return cls(tuple(d["image_size"]), tuple(c["name"] for c in cams), np.stack([np.asarray(c["K"], dtype=np.float64) for c in cams]),
+                   np.stack([np.asarray(c["cam_to_bev"], dtype=np.float64) for c in cams]))
+
+    def to_dict(self) -> Dict:
+        return {"image_size": list(self.image_size),
+                "cameras": [{"name": n, "K": k.tolist(), "cam_to_bev": t.tolist()} for n, k, t in zip(self.names, self.K, self.cam_to_bev)]}
+
+    def subset(self, n: int) -> "CameraRig":
+        """The first n cameras."""
+        return CameraRig(self.image_size, self.names[:n], self.K[:n], self.cam_to_bev[:n])
+
+
+# (name, yaw in degrees counter-clockwise from +y, mount x, mount y, focal length in pixels)
+_DEFAULT_MOUNTS = (("CAM_FRONT", 0.0, 0.0, 0.8, 1260.0), ("CAM_FRONT_RIGHT", -55.0, 0.5, 0.6, 1260.0),
+                   ("CAM_FRONT_LEFT", 55.0, -0.5, 0.6, 1260.0), ("CAM_BACK", 180.0, 0.0, -1.0, 800.0),
+                   ("CAM_BACK_LEFT", 110.0, -0.5, -0.4, 1260.0), ("CAM_BACK_RIGHT", -110.0, 0.5, -0.4, 1260.0))
+
+
+def default_rig() -> CameraRig:
+    """A fixed nuScenes-LIKE six-camera rig at 900 x 1600 -- an approximation of the dataset's layout so that configs and tests
+    work without data, NOT a calibration: pass CameraRig.from_info(info) for real frames.
+
+    Intrinsics fx = fy = 1260, cx = 800, cy = 450 (about 65 degrees horizontal field of view) for the five forward / side cameras,
+    fx = fy = 800 for CAM_BACK (about 90 degrees).  Optical axes horizontal; in the LiDAR frame (x right, y forward, z up) a camera of
+    yaw psi (counter-clockwise from +y) has x_cam -> (cos psi, sin psi, 0), y_cam -> (0, 0, -1), z_cam -> (-sin psi, cos psi, 0).
+    Yaws 0, -55, +55, 180, +110, -110 degrees in CAM_ORDER; mounts within 1 m of the LiDAR at z = -0.3 m."""
+    Ks, Ts = [], []
+    for _, yaw, mx, my, f in _DEFAULT_MOUNTS:
+        Ks.append(np.array([[f, 0.0, 800.0], [0.0, f, 450.0], [0.0, 0.0, 1.0]]))
+        p = math.radians(yaw)
+        T = np.eye(4)
+        T[:3, 0] = (math.cos(p), math.sin(p), 0.0)
+        T[:3, 1] = (0.0, 0.0, -1.0)
+        T[:3, 2] = (-math.sin(p), math.cos(p), 0.0)
+        T[:3, 3] = (mx, my, -0.3)
+        Ts.append(T)
+    return CameraRig((900, 1600), tuple(m[0] for m in _DEFAULT_MOUNTS), np.stack(Ks), np.stack(Ts))
+
+
+def view_transform_kind(camera_view_transform: Optional[str] = None, config: Optional[Dict] = None) -> str:
+    """'project' or 'mean' from the keyword, else `model.bev_fusion.camera_view_transform` of the config, else 'mean'
+    (any letter case); anything else raises."""
+    t = camera_view_transform
+    if t is None and config is not None:
+        t = (config.get("model", {}).get("bev_fusion", {}) or {}).get("camera_view_transform")
+    if t is None:
+        return "mean"
+    k = str(t).strip().lower()
+    if k not in VIEW_TRANSFORMS:
+        raise ValueError(f"camera_view_transform must be 'mean' or 'project', got {t!r}")
+    return k
+
+
+def camera_bev_settings(config: Optional[Dict] = None) -> Tuple[int, float, CameraRig]:
+    """(num_heights, min_depth, rig) from `model.bev_fusion.camera_bev` ({num_heights: 8, min_depth: 0.1, rig: {...}}); the rig
+    entry is CameraRig.from_dict's form, absent -> default_rig()."""
+    cb = ((config or {}).get("model", {}).get("bev_fusion", {}) or {}).get("camera_bev", {}) or {}
+    nh = int(cb.get("num_heights", DEFAULT_NUM_HEIGHTS))
+    md = float(cb.get("min_depth", DEFAULT_MIN_DEPTH))
+    if nh <= 0 or not md > 0.0:
+        raise ValueError(f"camera_bev: num_heights must be > 0 and min_depth > 0, got {nh}, {md}")
+    rig = CameraRig.from_dict(cb["rig"]) if cb.get("rig") else default_rig()
+    return nh, md, rig
+
+
+# ---- the projection table ----------------------------------------------------------------------------------------------------------
+
+@dataclass
+class ProjectionTable:
+    """Sparse lift matrix A [P cells][ncam*Hc*Wc pixels] as CSR by cell (row_ptr int32 [P+1], col int32 = cam*Hc*Wc + y*Wc + x,
+    w fp32) and its exact transpose as CSR by pixel (t_row_ptr [ncam*Hc*Wc+1], t_col = cell, t_w): same entries, fp32 weights.
+    w64: the merged fp64 weights before rounding (host checks)."""
+    P: int
+    ncols: int
+    row_ptr: np.ndarray
+    col: np.ndarray
+    w: np.ndarray
+    t_row_ptr: np.ndarray
+    t_col: np.ndarray
+    t_w: np.ndarray
+    w64: np.ndarray
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col.shape[0])
+
+
+def cell_centres(pc_range, bev_h: int, bev_w: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(x [bev_w], y [bev_h]) fp64 cell centres, exactly the pillar grid's: x0 + (j + 1/2) vx, y0 + (i + 1/2) vy, with x0, y0, vx, vy
+    the fp32 values of encoders.pillar_grid (row i = y, column j = x)."""
+    from .encoders import pillar_grid
+    x0, y0, vx, vy, _ = pillar_grid(pc_range, bev_h, bev_w)
+    xs = np.float64(x0) + (np.arange(bev_w, dtype=np.float64) + 0.5) * np.float64(vx)
+    ys = np.float64(y0) + (np.arange(bev_h, dtype=np.float64) + 0.5) * np.float64(vy)
+    return xs, ys
+
+
+def height_centres(pc_range, num_heights: int) -> np.ndarray:
+    z0, z1 = float(np.float32(pc_range[2])), float(np.float32(pc_range[5]))
+    return z0 + (np.arange(num_heights, dtype=np.float64) + 0.5) * (z1 - z0) / num_heights
+
+
+def build_projection_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int,
+                           num_heights: int = DEFAULT_NUM_HEIGHTS, min_depth: float = DEFAULT_MIN_DEPTH) -> ProjectionTable:
+    """The lift of rig's cameras (feature maps Hc x Wc each) onto the bev_h x bev_w grid of pc_range, in fp64:
+
+    sample (cell, height k, camera c) at p = (x_j, y_i, z_k): q = cam_to_bev[c]^-1 p; valid when q_z > min_depth and the pixel
+    (u, v) = (K q / q_z)[:2] lies in [0, W) x [0, H) of rig.image_size; its value is the bilinear sample of the feature map at
+    u_f = (u + 1/2) Wc / W - 1/2, v_f = (v + 1/2) Hc / H - 1/2 with taps outside the map reading zero (= F.grid_sample,
+    align_corners=False, padding_mode='zeros', at gx = (2u + 1) / W - 1).  Cell value = mean over its valid samples, 0 without one.
+    Duplicate (cell, pixel) entries are merged in fp64 before rounding to fp32; exact-zero weights are dropped."""
+    H, W = rig.image_size
+    ncam = rig.num_cameras
+    xs, ys = cell_centres(pc_range, bev_h, bev_w)
+    zs = height_centres(pc_range, num_heights)
+    P = bev_h * bev_w
+    gy, gx = np.meshgrid(ys, xs, indexing="ij")                                  # [bev_h][bev_w]
+    pts = np.empty((P, num_heights, 4), dtype=np.float64)
+    pts[..., 0] = gx.reshape(P, 1)
+    pts[..., 1] = gy.reshape(P, 1)
+    pts[..., 2] = zs.reshape(1, num_heights)
+    pts[..., 3] = 1.0
+    pts = pts.reshape(-1, 4)                                                      # sample s = cell * num_heights + k
+    cell_of = np.repeat(np.arange(P, dtype=np.int64), num_heights)
+    rows, cols, wts = [], [], []
+    count = np.zeros(P, dtype=np.int64)
+    for c in range(ncam):
+        q = pts @ np.linalg.inv(rig.cam_to_bev[c]).T
+        depth = q[:, 2]
+        front = depth > min_depth
+        uvw = q[front, :3] @ rig.K[c].T
+        u = uvw[:, 0] / uvw[:, 2]
+        v = uvw[:, 1] / uvw[:, 2]
+        inside = (u >= 0) & (u < W) & (v >= 0) & (v < H)
+        cells = cell_of[front][inside]
+        u, v = u[inside], v[inside]
+        np.add.at(count, cells, 1)
+        uf = (u + 0.5) * Wc / W - 0.5
+        vf = (v + 0.5) * Hc / H - 0.5
+        x0 = np.floor(uf)
+        y0 = np.floor(vf)
+        lx, ly = uf - x0, vf - y0
+        x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+        for dy, wy in ((0, 1.0 - ly), (1, ly)):
+            for dx, wx in ((0, 1.0 - lx), (1, lx)):
+                xi, yi = x0 + dx, y0 + dy
+                ok = (xi >= 0) & (xi < Wc) & (yi >= 0) & (yi < Hc)
+                rows.append(cells[ok])
+                cols.append(c * Hc * Wc + yi[ok] * Wc + xi[ok])
+                wts.append((wx * wy)[ok])
+    ncols = ncam * Hc * Wc
+    r = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    cl = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+    wt = np.concatenate(wts) if wts else np.zeros(0, np.float64)
+    wt = wt / np.maximum(count[r], 1)
+    key = r * ncols + cl
+    uniq, inv = np.unique(key, return_inverse=True)                               # sorted by (cell, pixel)
+    merged = np.bincount(inv, weights=wt, minlength=uniq.shape[0])
+    keep = merged != 0.0
+    uniq, merged = uniq[keep], merged[keep]
+    r, cl = uniq // ncols, uniq % ncols
+    w32 = merged.astype(np.float32)
+    if P * ncols >= 2 ** 63 or ncols >= 2 ** 31 or r.shape[0] >= 2 ** 31:
+        raise ValueError("projection table too large for int32 indices")
+    row_ptr = np.zeros(P + 1, dtype=np.int64)
+    np.cumsum(np.bincount(r, minlength=P), out=row_ptr[1:])
+    order = np.lexsort((r, cl))                                                   # by pixel, then cell
+    t_row_ptr = np.zeros(ncols + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cl, minlength=ncols), out=t_row_ptr[1:])
+    return ProjectionTable(P, ncols, row_ptr.astype(np.int32), cl.astype(np.int32), w32,
+                           t_row_ptr.astype(np.int32), r[order].astype(np.int32), w32[order], merged)
+
+
+def apply_table_fp64(t: ProjectionTable, feats: np.ndarray) -> np.ndarray:
+    """CPU fp64 application of the cell table with its fp64 weights: feats [B][ncols][C] -> [B][P][C] (host tests)."""
+    B, _, C = feats.shape
+    out = np.zeros((B, t.P, C), dtype=np.float64)
+    rows = np.repeat(np.arange(t.P), np.diff(t.row_ptr))
+    w = t.w64
+    for b in range(B):
+        np.add.at(out[b], rows, feats[b][t.col] * w[:, None])
+    return out

@@ -519,8 +519,62 @@ class RadarEngine(_Engine):
 
 # ---- BEV fusion (ref src/fusion.py:209-297) ----------------------------------------------------------------
 
+@dataclass
+class CameraTable:
+    """camera_rig.ProjectionTable on the device: the cell table (rows = BEV cells) for the forward and its transpose (rows = camera
+    feature pixels) for the backward, int32 / fp32."""
+    P: int
+    ncols: int
+    row_ptr: torch.Tensor
+    col: torch.Tensor
+    w: torch.Tensor
+    t_row_ptr: torch.Tensor
+    t_col: torch.Tensor
+    t_w: torch.Tensor
+
+    def project(self, x, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
+        """y[b][cell][0:C] (row stride y_cs) = the lift of x = NHWC camera features [B][ncols][C]."""
+        L.csr_gather(self.row_ptr, self.col, self.w, self.P, self.ncols, x, self.ncols * C, C, y, self.P * (y_cs or C),
+                     y_cs or C, B, C)
+
+    def project_backward(self, dy, dx, B: int, C: int) -> None:
+        """dx [B][ncols][C] = the transpose applied to dy [B][P][C]: every element of dx written once."""
+        L.csr_gather(self.t_row_ptr, self.t_col, self.t_w, self.ncols, self.P, dy, self.P * C, C, dx, self.ncols * C, C, B, C)
+
+
+def camera_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraTable:
+    """The projection table of FlexibleBEVFusion `fus` ('project' branch) for ncam cameras of Hc x Wc features, built on the host in
+    fp64 (camera_rig.build_projection_table) on first use and cached on the fusion's engine until set_camera_rig."""
+    rig = fus.camera_rig
+    if ncam != rig.num_cameras:
+        raise L.BevfError(f"BEV fusion (camera_view_transform='project'): the camera rig has {rig.num_cameras} cameras "
+                          f"({', '.join(rig.names)}) but the camera input has {ncam} (a 4-D input is one camera); pass "
+                          f"(B, {rig.num_cameras}, C, H, W) features or call set_camera_rig() with a matching rig")
+    eng = fus._eng()
+    key = (rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_num_heights,
+           fus.cam_min_depth, str(dev))
+    tab = eng._camera_tables.get(key)
+    if tab is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.BevfError("BEV fusion: the camera projection table is built on first use, which cannot happen inside a graph "
+                              "capture -- run the forward once before capturing")
+        from . import camera_rig as CR
+        t = CR.build_projection_table(rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, fus.cam_num_heights, fus.cam_min_depth)
+        d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
+        tab = CameraTable(t.P, t.ncols, d(t.row_ptr), d(t.col), d(t.w), d(t.t_row_ptr), d(t.t_col), d(t.t_w))
+        eng._camera_tables[key] = tab
+    return tab
+
+
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
+
+    def __init__(self, module: nn.Module):
+        super().__init__(module)
+        self._camera_tables: Dict[tuple, CameraTable] = {}
+
+    def drop_camera_tables(self) -> None:
+        self._camera_tables.clear()
 
     def pack(self) -> None:
         m = self.module
@@ -571,7 +625,19 @@ class FusionEngine(_Engine):
                                f"[{B}, {ccs}, {Sh}, {Sw}] to have {self.f1.cin} channels, but got {ccs} channels instead")
         concat = self.buf("concat", B * P * ccs)
         slot = 0
-        if "c" in present:
+        if "c" in present and getattr(m, "camera_view_transform", "mean") == "project":
+            # camera rig -> BEV grid (one gather), then camera_proj on the grid, its second conv into the concat slice
+            _, ncam, Hc, Wc = cam_geom
+            Cc = self.cam1.cin
+            tab = camera_table(m, ncam, Hc, Wc, cam.device)
+            proj = self.buf("cam_proj", B * P * Cc)
+            with _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (ncam * Hc * Wc + P)):
+                tab.project(cam, proj, B, Cc)
+            t1 = self.buf("cam_t1", B * P * self.cam1.cout)
+            _run_conv(self.cam1, proj, t1, B, Sh, Sw)
+            _run_conv(self.cam2, t1, concat[slot * bc:], B, Sh, Sw, y_cs=ccs)
+            slot += 1
+        elif "c" in present:
             _, ncam, Hc, Wc = cam_geom
             Cc = self.cam1.cin
             pooled = cam

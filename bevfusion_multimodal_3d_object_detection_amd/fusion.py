@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as E
+from . import camera_rig as CR
 from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, _cfg,  # noqa: F401
                        lidar_encoder_kind, load_config)
 
@@ -36,6 +37,10 @@ class FlexibleBEVFusion(nn.Module):
     Extension (opt-in, lidar_encoder_type / model.lidar_encoder.type 'PointPillars'): the LiDAR input is the pillar
     canvas (B, pfn_channels, bev_h, bev_w), already on the fusion grid, and the branch is
     lidar_bev = conv3x3(pfn_channels -> 128)+BN+ReLU -> conv3x3(128 -> bev_channels)+BN+ReLU (no lidar_init / lidar_upsample).
+    Extension (opt-in, camera_view_transform / model.bev_fusion.camera_view_transform 'project'): the camera
+    features of every camera are projected onto the BEV grid through a fixed camera rig (camera_rig.py: num_heights points above
+    each cell, bilinear samples averaged over those that hit an image), and camera_proj -- same modules and keys -- runs on the BEV
+    grid after the projection, with no resize.  One rig per module (set_camera_rig); per-frame calibration is not supported.
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -43,11 +48,17 @@ class FlexibleBEVFusion(nn.Module):
                  lidar_channels: Optional[int] = None, radar_channels: Optional[int] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, bev_channels: Optional[int] = None,
                  pc_range: Optional[List[float]] = None, config: Optional[Dict] = None,
-                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None):
+                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
+                 camera_view_transform: Optional[str] = None):
         super().__init__()
         config = _cfg(config, config_path)
         default_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
         self.lidar_kind = lidar_encoder_kind(lidar_encoder_type, config)
+        # camera branch: 'mean' (the reference's camera average + resize) or 'project' (camera rig -> BEV grid)
+        self.camera_view_transform = CR.view_transform_kind(camera_view_transform, config)
+        self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.DEFAULT_NUM_HEIGHTS, CR.DEFAULT_MIN_DEPTH, None
+        if self.camera_view_transform == "project":
+            self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.camera_bev_settings(config)
         pillars = self.lidar_kind == "pillars"
         if config is not None:
             mc = config.get("model", {})
@@ -102,6 +113,22 @@ class FlexibleBEVFusion(nn.Module):
         if self._engine is None:
             self._engine = E.FusionEngine(self)
         return self._engine
+
+    @property
+    def camera_rig(self) -> CR.CameraRig:
+        """The rig of the 'project' camera branch (camera_rig.default_rig() unless set)."""
+        if self._camera_rig is None:
+            self._camera_rig = CR.default_rig()
+        return self._camera_rig
+
+    def set_camera_rig(self, rig: "CR.CameraRig") -> None:
+        """Replace the camera rig of the 'project' branch; its projection tables are rebuilt on next use (outside a graph capture:
+        re-capture a GraphedDetector after a rig change).  The rig is fixed for every frame until the next call."""
+        if not isinstance(rig, CR.CameraRig):
+            raise TypeError(f"set_camera_rig: expected a camera_rig.CameraRig, got {type(rig).__name__}")
+        self._camera_rig = rig
+        if self._engine is not None:
+            self._engine.drop_camera_tables()
 
     def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features):
         """Internal fast path on NHWC camera features (no layout change)."""
@@ -250,7 +277,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  use_radar: Optional[bool] = None, num_classes: Optional[int] = None,
                  fusion_type: Optional[str] = None, detection_head: Optional[str] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
-                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None):
+                 config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
+                 camera_view_transform: Optional[str] = None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -290,7 +318,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
             self.radar_encoder = (MultiRadarEncoder(config=config) if config is not None
                                   else MultiRadarEncoder(input_channels=7, feat_dim=256, num_radars=5))
         if self.fusion_type == "bev":
-            extra = dict(lidar_encoder_type=self.lidar_encoder_type)
+            extra = dict(lidar_encoder_type=self.lidar_encoder_type, camera_view_transform=camera_view_transform)
             if self.use_lidar and pillars:
                 extra["lidar_channels"] = self.lidar_encoder.pfn_channels
             self.fusion = FlexibleBEVFusion(use_camera=self.use_camera, use_lidar=self.use_lidar,
@@ -378,10 +406,13 @@ class GraphedDetector:
 def create_detector(modality_config: Optional[str] = None, fusion_type: Optional[str] = None,
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
-                    lidar_encoder_type: Optional[str] = None, **kwargs) -> FlexibleMultiModal3DDetector:
+                    lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
+                    **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
-    lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type)."""
+    lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
+    camera_view_transform: 'project' selects the camera -> BEV projection branch, 'mean' the reference's camera average (None: the
+    config's model.bev_fusion.camera_view_transform, else 'mean')."""
     config = _cfg(config, config_path)
     if config is not None and modality_config is None:
         modality_config = config.get("model", {}).get("modality_config", "all")
@@ -394,7 +425,8 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
     return FlexibleMultiModal3DDetector(use_camera=use_camera, use_lidar=use_lidar, use_radar=use_radar,
                                         num_classes=num_classes, fusion_type=fusion_type,
                                         detection_head=detection_head, config=config,
-                                        lidar_encoder_type=lidar_encoder_type, **kwargs)
+                                        lidar_encoder_type=lidar_encoder_type, camera_view_transform=camera_view_transform,
+                                        **kwargs)
 
 
 def test_all_configurations():

@@ -973,7 +973,8 @@ class RadarTape:
 class FusionTape:
     """FlexibleBEVFusion (ref src/fusion.py:209-297): NHWC camera features [B*ncam*Hc*Wc*C] with cam_geom = (B, ncam, Hc, Wc),
     LiDAR (B, C_l) vectors or the PointPillars NHWC canvas on the fusion grid, radar (B, C_r) vectors -> fused NHWC map
-    [B*H*W*cout].  Each modality present fills one bev_channels slot of the concatenated map, in the order camera, LiDAR, radar."""
+    [B*H*W*cout].  Camera branch 'mean': camera average, camera_proj on the image grid, bilinear resize; 'project': the rig's
+    projection table (engine.camera_table) onto the grid, camera_proj there, the transposed table in the backward.  Each modality present fills one bev_channels slot of the concatenated map, in the order camera, LiDAR, radar."""
 
     def __init__(self, fus):
         self.fus = fus
@@ -995,7 +996,23 @@ class FusionTape:
         dev = next(f for f in (cam_feat, lid_feat, rad_feat) if f is not None).device
         concat = _new(B * P * ccs, dev)
         slot = 0
-        if self.has_cam:
+        self.cam_project = self.has_cam and getattr(fus, "camera_view_transform", "mean") == "project"
+        if self.cam_project:
+            # camera rig -> BEV grid (gather over the cell table), camera_proj's two conv+BN+ReLU on the grid, then the slice copy
+            _, ncam, Hc, Wc = cam_geom
+            Cc = fus.camera_proj[0].weight.shape[1]
+            self.cam_pool_geom = (B, ncam, Hc * Wc, Cc)
+            self.cam_table = E.camera_table(fus, ncam, Hc, Wc, dev)
+            proj = _new(B * P * Cc, dev)
+            self.cam_table.project(cam_feat, proj, B, Cc)
+            self.cp1 = ConvBNLayer(fus.camera_proj[0], fus.camera_proj[1], True)
+            self.cp2 = ConvBNLayer(fus.camera_proj[3], fus.camera_proj[4], True)
+            t1, _, _ = self.cp1.forward(proj, B, Sh, Sw)
+            t2, _, _ = self.cp2.forward(t1, B, Sh, Sw)
+            self._slot(concat, slot)[:] = t2[:B * P * bc].view(B * P, bc)
+            self.cam_slot = slot
+            slot += 1
+        elif self.has_cam:
             _, ncam, Hc, Wc = cam_geom
             Cc = fus.camera_proj[0].weight.shape[1]
             self.cam_pool_geom = (B, ncam, Hc * Wc, Cc)
@@ -1081,7 +1098,15 @@ class FusionTape:
             dlid = self.li0.backward(self.li2.backward(dgrid0, sink), sink)
         if dlid is not None and on_lidar is not None:
             on_lidar(dlid)
-        if self.has_cam:
+        if self.cam_project:
+            dt1, _ = self.cp2.backward(self._slot(dconcat, self.cam_slot).contiguous().view(-1), sink)
+            dproj, _ = self.cp1.backward(dt1, sink)
+            Bc, ncam, Pc, Cc = self.cam_pool_geom
+            dcam = _new(Bc * ncam * Pc * Cc, dfused.device)
+            self.cam_table.project_backward(dproj, dcam, Bc, Cc)                # transposed table: every element written once
+            if on_camera is not None:
+                on_camera(dcam)
+        elif self.has_cam:
             dt1, _ = self.cp2.backward(self.cam_resize.backward(dconcat[self.cam_slot * bc:]), sink)
             dcam, _ = self.cp1.backward(dt1, sink)
             Bc, ncam, Pc, Cc = self.cam_pool_geom

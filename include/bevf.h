@@ -353,6 +353,24 @@ int bevf_pillar_pfn_backward_f32(const bevf_pillar_geom* g, const float* dcanvas
 int bevf_scatter_voxels_f32(const float* features, const int64_t* coords, const int32_t* num_voxels, int32_t* owner,
                             float* out, int B, int Nv, int C, int D, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Camera -> BEV projection (csrc/camera_bev.hip): the opt-in camera branch `model.bev_fusion.camera_view_transform:
+ * project`.  Not in the reference (it averages the cameras and stretches the map): the lift is a fixed sparse matrix built
+ * on the host from the camera rig (camera_rig.py), applied here as a CSR gather
+ *     y[b][r][0:C] = sum over e in [row_ptr[r], row_ptr[r+1]) of w[e] * x[b][col[e]][0:C]
+ * x: [b] at x + b * x_bs, row i at x_cs elements; y likewise (x_bs / y_bs in elements): the output may be a channel slice.
+ * Entries are summed in table order in fp32 (bf16 entry: bf16 x / y, fp32 accumulation, round to nearest even on the
+ * store).  A row without entries is written as zeros; every output row r < nrows is written exactly once.  No atomics:
+ * bit-reproducible.  The forward runs the cell table (rows = BEV cells, col = cam*Hc*Wc + y*Wc + x), the backward the
+ * transposed table (rows = camera pixels, col = cell) on the output gradient.  Needs C % (16 / element size) == 0,
+ * C <= 1024 fp32 / 2048 bf16, 16-byte aligned x / y, 16-byte multiples for all strides, col[e] < the caller's column
+ * count, x and y not overlapping.  col / w may be NULL when the table has no entries.
+ * ------------------------------------------------------------------------------------------ */
+int bevf_csr_gather_f32(const int32_t* row_ptr, const int32_t* col, const float* w, int nrows, const float* x,
+                        size_t x_bs, int x_cs, float* y, size_t y_bs, int y_cs, int B, int C, void* stream);
+int bevf_csr_gather_bf16(const int32_t* row_ptr, const int32_t* col, const float* w, int nrows, const void* x,
+                         size_t x_bs, int x_cs, void* y, size_t y_bs, int y_cs, int B, int C, void* stream);
+
 /* ==========================================================================================
  * bf16 storage, fp32 accumulate (BASELINE configs 3 and 5).  Same layouts and geometry as the fp32 entry
  * points, element type bfloat16 wherever a pointer is typed void*: the convolution runs on

@@ -202,6 +202,13 @@ SIGNATURES = {
                             + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_csr_gather_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
                              + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_camera_table_build_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_float] * 2
+                                    + [C.c_int, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p, C.c_void_p]),
+    "bevf_camera_table_transpose": (C.c_int, [C.c_void_p] * 3 + [C.c_size_t] + [C.c_int] * 3 + [C.c_void_p] * 5),
+    "bevf_csr_gather_frames_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_int, C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_csr_gather_frames_bf16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                              C.c_size_t, C.c_int, C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
 }
 
 
@@ -1088,3 +1095,56 @@ def csr_gather(row_ptr, col, w, nrows: int, ncols: int, x, x_bs: int, x_cs: int,
         raise BevfError("csr_gather: x and y share storage")
     _call("bevf_csr_gather_" + _sfx(x), _pc(row_ptr, torch.int32), _pc(col, torch.int32) if nnz else None,
           _pc(w) if nnz else None, nrows, _p(x, x.dtype), x_bs, x_cs, _p(y, y.dtype), y_bs, y_cs, B, C)
+
+
+def camera_table_capacity(P: int, num_heights: int, ncam: int) -> int:
+    """Entries per frame that a device-built projection table can need at worst: every (cell, height, camera) sample valid with
+    four distinct taps."""
+    return P * num_heights * ncam * 4
+
+
+def camera_table_work_elems(B: int, cap: int, nrows: int) -> int:
+    """int32 elements of the work buffer of camera_table_build (nrows = P) / camera_table_transpose (nrows = ncols)."""
+    return 2 * B * cap + B * nrows
+
+
+def camera_table_build(calib, B: int, ncam: int, grid: Sequence[float], bev_h: int, bev_w: int, z_range: Sequence[float],
+                       num_heights: int, min_depth: float, image_size: Sequence[int], Hc: int, Wc: int, row_ptr, col, w, cap: int,
+                       work) -> None:
+    """The projection tables of B frames from calib [B][ncam][4][4] fp64 (camera_rig.calib_matrices) on the device
+    (bevf_camera_table_build_f64): row_ptr [B][P + 1], col / w [B][cap].  grid = (x0, y0, vx, vy) of encoders.pillar_grid, z_range =
+    (z0, z1), image_size = (H, W)."""
+    P = bev_h * bev_w
+    if cap < camera_table_capacity(P, num_heights, ncam):
+        raise BevfError(f"camera_table_build: capacity {cap} below the worst case {camera_table_capacity(P, num_heights, ncam)}")
+    _need("camera_table_build", calib=(calib, B * ncam * 16), row_ptr=(row_ptr, B * (P + 1)), col=(col, B * cap), w=(w, B * cap),
+          work=(work, camera_table_work_elems(B, cap, P)))
+    _call("bevf_camera_table_build_f64", _pc(calib, torch.float64), B, ncam, *(float(v) for v in grid), bev_h, bev_w,
+          float(z_range[0]), float(z_range[1]), num_heights, float(min_depth), int(image_size[0]), int(image_size[1]), Hc, Wc,
+          _pc(row_ptr, torch.int32), _pc(col, torch.int32), _pc(w), cap, _pc(work, torch.int32))
+
+
+def camera_table_transpose(row_ptr, col, w, cap: int, B: int, P: int, ncols: int, t_row_ptr, t_col, t_w, work) -> None:
+    """The per-frame tables of camera_table_build as CSR by pixel (bevf_camera_table_transpose): t_row_ptr [B][ncols + 1], t_col /
+    t_w [B][cap], rows in ascending cell order, deterministic."""
+    _need("camera_table_transpose", row_ptr=(row_ptr, B * (P + 1)), col=(col, B * cap), w=(w, B * cap),
+          t_row_ptr=(t_row_ptr, B * (ncols + 1)), t_col=(t_col, B * cap), t_w=(t_w, B * cap),
+          work=(work, camera_table_work_elems(B, cap, ncols)))
+    _call("bevf_camera_table_transpose", _pc(row_ptr, torch.int32), _pc(col, torch.int32), _pc(w), cap, B, P, ncols,
+          _pc(t_row_ptr, torch.int32), _pc(t_col, torch.int32), _pc(t_w), _pc(work, torch.int32))
+
+
+def csr_gather_frames(row_ptr, col, w, cap: int, nrows: int, ncols: int, x, x_bs: int, x_cs: int, y, y_bs: int, y_cs: int, B: int,
+                      C: int) -> None:
+    """csr_gather with one table per frame (bevf_csr_gather_frames): frame b reads row_ptr[b] ([B][nrows + 1], offsets within the
+    frame) and col / w [b * cap ...]; every col < ncols and row_ptr[b][nrows] <= cap by construction of the table."""
+    if cap <= 0:
+        raise BevfError("csr_gather_frames: capacity must be positive")
+    _need("csr_gather_frames", row_ptr=(row_ptr, B * (nrows + 1)), col=(col, B * cap), w=(w, B * cap),
+          x=(x, (B - 1) * x_bs + _strided(ncols, C, x_cs)), y=(y, (B - 1) * y_bs + _strided(nrows, C, y_cs)))
+    if y.dtype != x.dtype:
+        raise BevfError(f"csr_gather_frames: x is {x.dtype}, y is {y.dtype}")
+    if x.is_cuda and y.is_cuda and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("csr_gather_frames: x and y share storage")
+    _call("bevf_csr_gather_frames_" + _sfx(x), _pc(row_ptr, torch.int32), nrows + 1, _pc(col, torch.int32), _pc(w), cap, nrows,
+          _p(x, x.dtype), x_bs, x_cs, _p(y, y.dtype), y_bs, y_cs, B, C)

@@ -6,8 +6,10 @@ map bilinearly there and averages over the samples that hit an image.  With a st
 over (BEV cell) x (camera feature pixel), built here once on the host in fp64 and applied on the device by
 bevf_csr_gather (csrc/camera_bev.hip) -- the forward on the cell table, the backward on its exact transpose.
 
-One rig per module: calibration that changes from frame to frame is not supported (the table would have to be rebuilt per
-frame).  DESIGN.md 3.2d.
+The module's rig is the default for every frame.  Calibration that changes from frame to frame (vehicles, scenes, resize / crop
+augmentation) goes in as `camera_calib=` of the fusion / detector forward: `calib_matrices(rigs)` packs one projection matrix per
+(frame, camera) and the same table is then built per frame ON THE DEVICE (csrc/camera_calib.hip: bevf_camera_table_build_f64,
+its transpose by bevf_camera_table_transpose, applied by bevf_csr_gather_frames).  DESIGN.md 3.2d.
 """
 from __future__ import annotations
 
@@ -133,6 +135,52 @@ def default_rig() -> CameraRig:
         T[:3, 3] = (mx, my, -0.3)
         Ts.append(T)
     return CameraRig((900, 1600), tuple(m[0] for m in _DEFAULT_MOUNTS), np.stack(Ks), np.stack(Ts))
+
+
+def calib_matrices(rigs: Sequence[CameraRig]) -> np.ndarray:
+    """fp64 [B, ncam, 4, 4] for a sequence of B rigs (one per frame; same image_size and camera count): per camera, with
+    E = cam_to_bev^-1, rows 0-2 = K . E[0:3] and row 3 = E[2] -- a BEV point p = (x, y, z, 1) has depth row3 . p and pixel
+    (u, v) = (row0 . p, row1 . p) / (row2 . p).  The `camera_calib=` input of the 'project' branch (device table build)."""
+    rigs = list(rigs)
+    if not rigs or not all(isinstance(r, CameraRig) for r in rigs):
+        raise ValueError("calib_matrices: expected a non-empty sequence of camera_rig.CameraRig")
+    first = rigs[0]
+    out = np.empty((len(rigs), first.num_cameras, 4, 4), dtype=np.float64)
+    for b, r in enumerate(rigs):
+        if r.image_size != first.image_size or r.num_cameras != first.num_cameras:
+            raise ValueError(f"calib_matrices: frame {b} has image_size {r.image_size} and {r.num_cameras} cameras, frame 0 has "
+                             f"{first.image_size} and {first.num_cameras}")
+        for c in range(r.num_cameras):
+            E = np.linalg.inv(r.cam_to_bev[c])
+            out[b, c, :3] = r.K[c] @ E[:3]
+            out[b, c, 3] = E[2]
+    return out
+
+
+def _axis_rotation(axis: int, deg: float) -> np.ndarray:
+    c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    m = np.eye(3)
+    m[i, i], m[i, j], m[j, i], m[j, j] = c, -s, s, c
+    return m
+
+
+def jittered_rig(seed: int, rig: Optional[CameraRig] = None) -> CameraRig:
+    """`rig` (default_rig() unless given) with a seeded jitter per camera, for tests and benchmarks of per-frame calibration: yaw /
+    pitch / roll (about z / x / y of the BEV frame, applied as Rz . Rx . Ry in front of the camera's rotation) each uniform in +-3
+    degrees, mount +-0.3 m per axis, focal length +-10 %, principal point +-20 px per axis; numpy.random.default_rng(seed)."""
+    g = np.random.default_rng(seed)
+    rig = default_rig() if rig is None else rig
+    K, T = rig.K.copy(), rig.cam_to_bev.copy()
+    for c in range(rig.num_cameras):
+        yaw, pitch, roll = g.uniform(-3.0, 3.0, 3)
+        T[c, :3, :3] = _axis_rotation(2, yaw) @ _axis_rotation(0, pitch) @ _axis_rotation(1, roll) @ T[c, :3, :3]
+        T[c, :3, 3] += g.uniform(-0.3, 0.3, 3)
+        f = 1.0 + g.uniform(-0.1, 0.1)
+        K[c, 0, 0] *= f
+        K[c, 1, 1] *= f
+        K[c, :2, 2] += g.uniform(-20.0, 20.0, 2)
+    return CameraRig(rig.image_size, rig.names, K, T)
 
 
 def view_transform_kind(camera_view_transform: Optional[str] = None, config: Optional[Dict] = None) -> str:

@@ -566,12 +566,84 @@ def camera_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraTabl
     return tab
 
 
+class FrameCameraTables:
+    """The per-frame sibling of CameraTable: one projection table per frame, built on the device from a [B][ncam][4][4] fp64
+    calibration tensor (camera_rig.calib_matrices) into grow-only buffers of the fusion's engine, of the worst-case capacity
+    P * num_heights * ncam * 4 entries per frame -- no host synchronisation and no allocation once the buffers exist, so build,
+    transposition and gather run inside a graph capture.  `version` counts the builds -- eager ones in build(), the replay of a
+    captured one through invalidate(), which GraphedDetector calls: a tape that finds another version in its backward rebuilds
+    from the calibration it kept."""
+
+    def __init__(self, eng: "_Engine"):
+        self.eng = eng
+        self.version = 0
+        self.t_version = -1
+
+    def build(self, calib: torch.Tensor, image_size, B: int, ncam: int, Hc: int, Wc: int) -> None:
+        import numpy as np
+        from .encoders import pillar_grid
+        m = self.eng.module
+        self.B, self.P, self.ncols = B, m.bev_h * m.bev_w, ncam * Hc * Wc
+        self.cap = cap = L.camera_table_capacity(self.P, m.cam_num_heights, ncam)
+        buf = self.eng.buf
+        self.row_ptr = buf("ct_row_ptr", B * (self.P + 1), torch.int32)
+        self.col = buf("ct_col", B * cap, torch.int32)
+        self.w = buf("ct_w", B * cap, torch.float32)
+        self.work = buf("ct_work", L.camera_table_work_elems(B, cap, max(self.P, self.ncols)), torch.int32)
+        x0, y0, vx, vy, _ = pillar_grid(m.pc_range, m.bev_h, m.bev_w)
+        z = (float(np.float32(m.pc_range[2])), float(np.float32(m.pc_range[5])))
+        L.camera_table_build(calib, B, ncam, (x0, y0, vx, vy), m.bev_h, m.bev_w, z, m.cam_num_heights, m.cam_min_depth, image_size,
+                             Hc, Wc, self.row_ptr, self.col, self.w, cap, self.work)
+        self.version += 1
+
+    def invalidate(self) -> None:
+        """The buffers are about to be rewritten by launches this object does not see (a graph replay of a captured build)."""
+        self.version += 1
+
+    def transpose(self) -> None:
+        """The transposed tables of the current build (once per build)."""
+        if self.t_version == self.version:
+            return
+        buf, B, cap = self.eng.buf, self.B, self.cap
+        self.t_row_ptr = buf("ct_t_row_ptr", B * (self.ncols + 1), torch.int32)
+        self.t_col = buf("ct_t_col", B * cap, torch.int32)
+        self.t_w = buf("ct_t_w", B * cap, torch.float32)
+        L.camera_table_transpose(self.row_ptr, self.col, self.w, cap, B, self.P, self.ncols, self.t_row_ptr, self.t_col, self.t_w,
+                                 self.work)
+        self.t_version = self.version
+
+    def project(self, x, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
+        """y[b][cell][0:C] (row stride y_cs) = frame b's lift of x = NHWC camera features [B][ncols][C]."""
+        L.csr_gather_frames(self.row_ptr, self.col, self.w, self.cap, self.P, self.ncols, x, self.ncols * C, C, y,
+                            self.P * (y_cs or C), y_cs or C, B, C)
+
+    def project_backward(self, dy, dx, B: int, C: int) -> None:
+        """dx [B][ncols][C] = frame b's transposed table applied to dy [B][P][C]: every element of dx written once."""
+        self.transpose()
+        L.csr_gather_frames(self.t_row_ptr, self.t_col, self.t_w, self.cap, self.ncols, self.P, dy, self.P * C, C, dx,
+                            self.ncols * C, C, B, C)
+
+
+def frame_camera_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev) -> FrameCameraTables:
+    """The per-frame projection tables of FlexibleBEVFusion `fus` for camera_calib = (fp64 [B, ncam, 4, 4] tensor, image_size) as
+    FlexibleBEVFusion.camera_calib_tensor returns it, built now on the current stream."""
+    calib, image_size = camera_calib
+    if tuple(calib.shape) != (B, ncam, 4, 4):
+        raise L.BevfError(f"BEV fusion: camera_calib is {tuple(calib.shape)} but the camera features are {B} frames of {ncam} cameras")
+    eng = fus._eng()
+    if eng._frame_tables is None:
+        eng._frame_tables = FrameCameraTables(eng)
+    eng._frame_tables.build(calib.to(dev).contiguous(), image_size, B, ncam, Hc, Wc)
+    return eng._frame_tables
+
+
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
 
     def __init__(self, module: nn.Module):
         super().__init__(module)
         self._camera_tables: Dict[tuple, CameraTable] = {}
+        self._frame_tables: Optional[FrameCameraTables] = None
 
     def drop_camera_tables(self) -> None:
         self._camera_tables.clear()
@@ -601,10 +673,11 @@ class FusionEngine(_Engine):
         self.f2 = pack_conv(m.bev_fusion[3], m.bev_fusion[4], True)
 
     def run(self, cam: Optional[torch.Tensor], cam_geom: Optional[Tuple[int, int, int, int]],
-            lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int]:
+            lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor], camera_calib=None) -> Tuple[torch.Tensor, int]:
         """cam: NHWC encoder features [B*ncam][Hc][Wc][C] with cam_geom = (B, ncam, Hc, Wc); lidar (B,1024), or with a
-        PointPillars branch the NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype; radar (B,256).  Returns the
-        fused NHWC map [B][S_h*S_w][bev_channels] and B."""
+        PointPillars branch the NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype; radar (B,256).  camera_calib
+        ('project' branch): (fp64 [B, ncam, 4, 4], image_size) for per-frame tables built here, None = the module rig's table.
+        Returns the fused NHWC map [B][S_h*S_w][bev_channels] and B."""
         self.ensure_packed()
         m = self.module
         Sh, Sw, bc = m.bev_h, m.bev_w, m.bev_channels
@@ -629,7 +702,11 @@ class FusionEngine(_Engine):
             # camera rig -> BEV grid (one gather), then camera_proj on the grid, its second conv into the concat slice
             _, ncam, Hc, Wc = cam_geom
             Cc = self.cam1.cin
-            tab = camera_table(m, ncam, Hc, Wc, cam.device)
+            if camera_calib is None:
+                tab = camera_table(m, ncam, Hc, Wc, cam.device)
+            else:
+                with _span("cam_table_build"):
+                    tab = frame_camera_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
             proj = self.buf("cam_proj", B * P * Cc)
             with _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (ncam * Hc * Wc + P)):
                 tab.project(cam, proj, B, Cc)

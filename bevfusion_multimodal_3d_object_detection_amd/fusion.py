@@ -40,7 +40,9 @@ class FlexibleBEVFusion(nn.Module):
     Extension (opt-in, camera_view_transform / model.bev_fusion.camera_view_transform 'project'): the camera
     features of every camera are projected onto the BEV grid through a fixed camera rig (camera_rig.py: num_heights points above
     each cell, bilinear samples averaged over those that hit an image), and camera_proj -- same modules and keys -- runs on the BEV
-    grid after the projection, with no resize.  One rig per module (set_camera_rig); per-frame calibration is not supported.
+    grid after the projection, with no resize.  The module's rig (set_camera_rig) serves every frame unless the forward gets
+    `camera_calib=`: one CameraRig per frame, or the fp64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device) --
+    then every frame is lifted through its own table, built on the device inside the step.
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -130,21 +132,50 @@ class FlexibleBEVFusion(nn.Module):
         if self._engine is not None:
             self._engine.drop_camera_tables()
 
-    def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features):
-        """Internal fast path on NHWC camera features (no layout change)."""
-        return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features)
+    def camera_calib_tensor(self, camera_calib, B: int, ncam: int):
+        """Check a `camera_calib=` argument against B frames of ncam cameras -> (fp64 (B, ncam, 4, 4) tensor where the caller put
+        it -- host or device --, image_size), or None for None.  A sequence of CameraRig carries its own image_size; a tensor (as
+        camera_rig.calib_matrices makes it) refers to the module rig's."""
+        if camera_calib is None:
+            return None
+        if self.camera_view_transform != "project":
+            raise E.L.BevfError("camera_calib needs camera_view_transform='project': the 'mean' camera branch uses no calibration")
+        if not B:                                                        # no camera input: nothing to calibrate
+            return None
+        if isinstance(camera_calib, torch.Tensor):
+            if camera_calib.dtype != torch.float64:
+                raise E.L.BevfError(f"camera_calib must be float64 (camera_rig.calib_matrices), got {camera_calib.dtype}")
+            t, image_size = camera_calib, self.camera_rig.image_size
+        else:
+            rigs = list(camera_calib)
+            t = torch.from_numpy(CR.calib_matrices(rigs))
+            image_size = rigs[0].image_size
+        if tuple(t.shape) != (B, ncam, 4, 4):
+            raise ValueError(f"camera_calib holds {tuple(t.shape)}: expected one calibration per frame and camera, "
+                             f"({B}, {ncam}, 4, 4)")
+        return t, image_size
+
+    def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib=None):
+        """Internal fast path on NHWC camera features (no layout change); camera_calib as camera_calib_tensor returns it."""
+        return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib)
 
     def forward(self, camera_features: Optional[torch.Tensor] = None, lidar_features: Optional[torch.Tensor] = None,
-                radar_features: Optional[torch.Tensor] = None) -> torch.Tensor:
+                radar_features: Optional[torch.Tensor] = None, camera_calib=None) -> torch.Tensor:
+        """camera_calib ('project' branch only): per-frame calibration -- a sequence of B camera_rig.CameraRig or the float64
+        (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame."""
+        if camera_calib is not None:
+            cf = camera_features if self.use_camera else None
+            camera_calib = self.camera_calib_tensor(camera_calib, 0 if cf is None else cf.shape[0],
+                                                    0 if cf is None else (cf.shape[1] if cf.dim() == 5 else 1))
         E.require_cuda(camera_features, lidar_features, radar_features)
         if self.training:
             from . import training
             if training.wants_train_path(self):         # used outside the detector in train mode: batch statistics + gradients
-                return training.fusion_train_forward(self, camera_features, lidar_features, radar_features)
+                return training.fusion_train_forward(self, camera_features, lidar_features, radar_features, camera_calib)
         with torch.no_grad():
-            return self._forward_eval(camera_features, lidar_features, radar_features)
+            return self._forward_eval(camera_features, lidar_features, radar_features, camera_calib)
 
-    def _forward_eval(self, camera_features, lidar_features, radar_features) -> torch.Tensor:
+    def _forward_eval(self, camera_features, lidar_features, radar_features, camera_calib=None) -> torch.Tensor:
         cam_nhwc = cam_geom = None
         if self.use_camera and camera_features is not None:
             x = camera_features.float()
@@ -159,7 +190,7 @@ class FlexibleBEVFusion(nn.Module):
             B, Cc, H, W = lid.shape                                       # NCHW canvas -> the engine's NHWC storage
             lid = E.to_nhwc(lid).to(self._eng().dtype).view(B, H, W, Cc)
         out, B = self.forward_nhwc(cam_nhwc, cam_geom, lid,
-                                   radar_features.float() if radar_features is not None else None)
+                                   radar_features.float() if radar_features is not None else None, camera_calib)
         return E.to_nchw(out, B, self.bev_channels, self.bev_h, self.bev_w)
 
     def get_config_str(self) -> str:
@@ -334,17 +365,32 @@ class FlexibleMultiModal3DDetector(nn.Module):
         else:
             self.det_head = MLPDetectionHead()
 
+    def camera_calib_tensor(self, camera_imgs, camera_calib):
+        """`camera_calib=` of forward checked against the camera input (FlexibleBEVFusion.camera_calib_tensor); None without
+        camera images."""
+        if camera_calib is None:
+            return None
+        if not hasattr(self.fusion, "camera_calib_tensor"):
+            raise E.L.BevfError("camera_calib needs the 'bev' fusion with camera_view_transform='project'")
+        if not self.use_camera or camera_imgs is None:
+            return self.fusion.camera_calib_tensor(camera_calib, 0, 0)             # None ('mean' still raises)
+        return self.fusion.camera_calib_tensor(camera_calib, camera_imgs.shape[0], camera_imgs.shape[1] if camera_imgs.dim() == 5 else 1)
+
     def forward(self, camera_imgs: Optional[torch.Tensor] = None, lidar_points: Optional[torch.Tensor] = None,
-                radar_points: Optional[List[torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None) -> Dict[str, torch.Tensor]:
+        """camera_calib (camera_view_transform='project' only): per-frame camera calibration -- a sequence of B
+        camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
+        fusion's rig for every frame."""
+        camera_calib = self.camera_calib_tensor(camera_imgs, camera_calib)
         if self.training and (torch.is_grad_enabled() or _any_bn_training(self)):
             # under no_grad a train-mode model still normalises with batch statistics and updates the running buffers, as torch does
             from . import training                      # train-mode BN + tape + hand-written backward (training.py)
             E.require_cuda(camera_imgs, lidar_points)
-            return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points)
+            return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib)
         with torch.no_grad():
-            return self._forward_inference(camera_imgs, lidar_points, radar_points)
+            return self._forward_inference(camera_imgs, lidar_points, radar_points, camera_calib)
 
-    def _forward_inference(self, camera_imgs, lidar_points, radar_points) -> Dict[str, torch.Tensor]:
+    def _forward_inference(self, camera_imgs, lidar_points, radar_points, camera_calib=None) -> Dict[str, torch.Tensor]:
         cam = geom = lid = rad = None
         if self.use_camera and camera_imgs is not None:
             cam, geom = self.camera_encoder.forward_nhwc(camera_imgs)       # stays NHWC: no layout change
@@ -355,15 +401,15 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad)
+        fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
         return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
 
     def get_config_str(self) -> str:
         return f"{self.fusion.get_config_str()}_{self.fusion_type}_{self.detection_head_type}"
 
-    def make_graphed(self, camera_imgs=None, lidar_points=None, radar_points=None) -> "GraphedDetector":
+    def make_graphed(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None) -> "GraphedDetector":
         """Capture the inference forward for these input shapes into one hipGraph (launch-bound small batches)."""
-        return GraphedDetector(self, camera_imgs, lidar_points, radar_points)
+        return GraphedDetector(self, camera_imgs, lidar_points, radar_points, camera_calib)
 
 
 class GraphedDetector:
@@ -371,27 +417,42 @@ class GraphedDetector:
 
     Every launch of the HIP path goes to torch's current stream, so `torch.cuda.graph` records them; inputs are
     copied into static buffers, outputs are static tensors that the next replay overwrites (clone to keep).
-    Weights are baked in as of capture time: re-capture after a parameter update."""
+    Weights are baked in as of capture time: re-capture after a parameter update.  With `camera_calib` the per-frame calibration
+    is a graph input like the images (a static device tensor, copied into before the replay): the table build and the gather are
+    part of the capture, nothing is built on the host."""
 
-    def __init__(self, model: "FlexibleMultiModal3DDetector", camera_imgs, lidar_points, radar_points):
+    def __init__(self, model: "FlexibleMultiModal3DDetector", camera_imgs, lidar_points, radar_points, camera_calib=None):
         assert not model.training, "capture the inference forward: call model.eval() first"
         E.require_cuda(camera_imgs, lidar_points)
         self.model = model
+        calib = model.camera_calib_tensor(camera_imgs, camera_calib)
+        self.static_calib = None if calib is None else (calib[0].to(camera_imgs.device).clone().contiguous(), calib[1])
         c = lambda t: t.clone() if t is not None else None
         self.static_in = (c(camera_imgs), c(lidar_points), [r.clone() for r in radar_points] if radar_points else None)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):                                   # packs weights, sizes workspaces, sets kernel attributes
-                model._forward_inference(*self.static_in)
+                model._forward_inference(*self.static_in, self.static_calib)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), torch.no_grad():
-            self.static_out = model._forward_inference(*self.static_in)
+            self.static_out = model._forward_inference(*self.static_in, self.static_calib)
 
     @torch.no_grad()
-    def __call__(self, camera_imgs=None, lidar_points=None, radar_points=None) -> Dict[str, torch.Tensor]:
+    def __call__(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None) -> Dict[str, torch.Tensor]:
         si, sp, sr = self.static_in
+        if camera_calib is not None:
+            if self.static_calib is None:
+                raise E.L.BevfError("GraphedDetector: captured without camera_calib; capture again with one")
+            calib = self.model.camera_calib_tensor(si, camera_calib)
+            if calib[1] != self.static_calib[1]:
+                raise E.L.BevfError(f"GraphedDetector: captured for image_size {self.static_calib[1]}, got {calib[1]}")
+            if calib[0].data_ptr() != self.static_calib[0].data_ptr():
+                self.static_calib[0].copy_(calib[0])
+        if self.static_calib is not None:
+            # the replay rebuilds the per-frame tables in the engine's buffers: a training tape that still needs its own rebuilds them
+            self.model.fusion._eng()._frame_tables.invalidate()
         for dst, src in ((si, camera_imgs), (sp, lidar_points)):
             if dst is not None and src is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src)

@@ -984,7 +984,10 @@ class FusionTape:
         bc, rows = self.fus.bev_channels, self.B * self.H * self.W
         return buf[:rows * self.ccs].view(rows, self.ccs)[:, slot * bc:(slot + 1) * bc]
 
-    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B):
+    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None):
+        """camera_calib ('project' branch): (fp64 [B, ncam, 4, 4], image_size) -- per-frame tables built here on the device; the
+        tape keeps the calibration and the build's version, and its backward rebuilds the tables if another forward has
+        replaced them in the engine's buffers since."""
         fus = self.fus
         self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
         Sh, Sw, bc = self.H, self.W, self.cout
@@ -1002,7 +1005,12 @@ class FusionTape:
             _, ncam, Hc, Wc = cam_geom
             Cc = fus.camera_proj[0].weight.shape[1]
             self.cam_pool_geom = (B, ncam, Hc * Wc, Cc)
-            self.cam_table = E.camera_table(fus, ncam, Hc, Wc, dev)
+            self.frame_calib = None
+            if camera_calib is None:
+                self.cam_table = E.camera_table(fus, ncam, Hc, Wc, dev)
+            else:
+                self.cam_table = E.frame_camera_tables(fus, camera_calib, B, ncam, Hc, Wc, dev)
+                self.frame_calib = ((camera_calib[0].to(dev).clone(), camera_calib[1]), self.cam_table.version, (ncam, Hc, Wc))
             proj = _new(B * P * Cc, dev)
             self.cam_table.project(cam_feat, proj, B, Cc)
             self.cp1 = ConvBNLayer(fus.camera_proj[0], fus.camera_proj[1], True)
@@ -1103,6 +1111,9 @@ class FusionTape:
             dproj, _ = self.cp1.backward(dt1, sink)
             Bc, ncam, Pc, Cc = self.cam_pool_geom
             dcam = _new(Bc * ncam * Pc * Cc, dfused.device)
+            if self.frame_calib is not None and self.cam_table.version != self.frame_calib[1]:
+                self.cam_table = E.frame_camera_tables(self.fus, self.frame_calib[0], Bc, *self.frame_calib[2], dfused.device)
+                self.frame_calib = (self.frame_calib[0], self.cam_table.version, self.frame_calib[2])
             self.cam_table.project_backward(dproj, dcam, Bc, Cc)                # transposed table: every element written once
             if on_camera is not None:
                 on_camera(dcam)
@@ -1173,8 +1184,9 @@ class DetectorTape:
     the order radar, camera, LiDAR (RELU_TRACE follows it), then fusion and head.  The backward walks them in reverse and marks
     where gradients become final for the data-parallel all-reduce (sink.ready())."""
 
-    def __init__(self, model):
+    def __init__(self, model, camera_calib=None):
         self.m = model
+        self.camera_calib = camera_calib          # per-frame calibration of the 'project' camera branch (FusionTape.forward)
 
     def forward(self, imgs, pts, radars):
         m = self.m
@@ -1204,7 +1216,7 @@ class DetectorTape:
             lid_feat = self.lidar.forward(pts)
             B = self.lidar.B
         self.fusion = FusionTape(m.fusion)
-        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B)
+        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None)
         self.head = HeadTape(m.det_head)
         return self.head.forward(fused, B, self.fusion.H, self.fusion.W)
 
@@ -1296,8 +1308,8 @@ def wants_train_path(module: nn.Module) -> bool:
     return any_bn_training(module) or torch.is_grad_enabled()
 
 
-def detector_train_forward(model, imgs, pts, radars) -> Dict[str, torch.Tensor]:
-    tape = DetectorTape(model)
+def detector_train_forward(model, imgs, pts, radars, camera_calib=None) -> Dict[str, torch.Tensor]:
+    tape = DetectorTape(model, camera_calib)
     outs = _TapeFn.apply("detector", tape.forward, tape.backward, _GRAD_REDUCER, 3, imgs, pts, radars, *_trainable(model))
     return dict(zip(E.HEAD_BRANCHES, outs))
 
@@ -1419,7 +1431,7 @@ def radar_train_forward(enc, radar_list) -> torch.Tensor:
     return out
 
 
-def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_features=None) -> torch.Tensor:
+def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_features=None, camera_calib=None) -> torch.Tensor:
     """FlexibleBEVFusion.forward under train-mode BatchNorm (ref src/fusion.py:209-297) -> (B, bev_channels, bev_h, bev_w), with
     gradients for the parameters AND for the three feature inputs."""
     cam = camera_features if fus.use_camera else None
@@ -1443,7 +1455,8 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
         lid_in = None if lid is None else lid.detach().float().contiguous()
         if lid_in is not None and pillars:                             # NCHW pillar canvas -> NHWC
             lid_in = _nhwc(lid_in)
-        fused = tape.forward(cam_nhwc, geom, lid_in, None if rad is None else rad.detach().float().contiguous(), B)
+        fused = tape.forward(cam_nhwc, geom, lid_in, None if rad is None else rad.detach().float().contiguous(), B,
+                             camera_calib if cam_nhwc is not None else None)
         return (E.to_nchw(fused, B, tape.cout, tape.H, tape.W),)
 
     def bwd(douts, sink):

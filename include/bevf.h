@@ -371,6 +371,42 @@ int bevf_csr_gather_f32(const int32_t* row_ptr, const int32_t* col, const float*
 int bevf_csr_gather_bf16(const int32_t* row_ptr, const int32_t* col, const float* w, int nrows, const void* x,
                          size_t x_bs, int x_cs, void* y, size_t y_bs, int y_cs, int B, int C, void* stream);
 
+/* Per-frame camera calibration (csrc/camera_calib.hip; DESIGN.md 3.2d "Per-frame calibration"): the table of
+ * camera_rig.build_projection_table built on the device, one CSR table per frame, with no host synchronisation and no
+ * allocation (capture-safe).
+ *
+ * bevf_camera_table_build_f64.  calib [B][ncam][4][4] fp64 (camera_rig.calib_matrices): rows 0-2 = K . E[0:3], row 3 = E[2]
+ * with E = cam_to_bev^-1.  Grid: x0, y0, vx, vy = encoders.pillar_grid's fp32 values, bev_h x bev_w cells, num_heights
+ * centres over the fp32 z range [z0, z1]; the images are img_h x img_w, the feature maps Hc x Wc.  Sample (cell, height k,
+ * camera c) is valid when its depth > min_depth and its pixel lies in [0, img_w) x [0, img_h); taps, weights and the mean
+ * over the valid samples exactly as build_projection_table's docstring states.  The geometry runs in fp64; the duplicate
+ * (cell, pixel) entries of a cell are merged in fp64, exact zeros dropped, and the weight rounded to fp32 once.
+ * Output, per frame b: row_ptr [B][P + 1] (P = bev_h * bev_w; offsets within the frame), and the frame's entries at
+ * col / w [b * cap ...], sorted by pixel inside a row (the host table's order); cap >= P * num_heights * ncam * 4 entries
+ * (the worst case), only the used part is written.  work: B * cap * 8 bytes + B * P int32.  Needs num_heights * ncam <= 682.
+ * Deterministic: two builds give the same bits.
+ *
+ * bevf_camera_table_transpose.  The same (cell, pixel, w) entries as CSR by pixel, per frame: t_row_ptr [B][ncols + 1],
+ * t_col (= cell) / t_w at [b * cap ...], every row in ascending cell order (ties in the forward table's order), weights
+ * bit-equal.  Integer atomics count the rows and hand out cursor positions; each row is then rank-sorted by forward entry
+ * index, so the order does not depend on them.  work: B * cap * 8 bytes + B * ncols int32 (may be the build's).
+ *
+ * bevf_csr_gather_frames_{f32,bf16}.  bevf_csr_gather with a table per frame: frame b reads row_ptr + b * rp_stride
+ * (rp_stride >= nrows + 1) and col / w + b * e_stride.  Same strides, slice output, zero rows, fp32 accumulation in table
+ * order, no atomics, every output row written once; B <= 65535. */
+int bevf_camera_table_build_f64(const double* calib, int B, int ncam, float x0, float y0, float vx, float vy, int bev_h,
+                                int bev_w, float z0, float z1, int num_heights, double min_depth, int img_h, int img_w,
+                                int Hc, int Wc, int32_t* row_ptr, int32_t* col, float* w, size_t cap, void* work,
+                                void* stream);
+int bevf_camera_table_transpose(const int32_t* row_ptr, const int32_t* col, const float* w, size_t cap, int B, int P,
+                                int ncols, int32_t* t_row_ptr, int32_t* t_col, float* t_w, void* work, void* stream);
+int bevf_csr_gather_frames_f32(const int32_t* row_ptr, size_t rp_stride, const int32_t* col, const float* w,
+                               size_t e_stride, int nrows, const float* x, size_t x_bs, int x_cs, float* y, size_t y_bs,
+                               int y_cs, int B, int C, void* stream);
+int bevf_csr_gather_frames_bf16(const int32_t* row_ptr, size_t rp_stride, const int32_t* col, const float* w,
+                                size_t e_stride, int nrows, const void* x, size_t x_bs, int x_cs, void* y, size_t y_bs,
+                                int y_cs, int B, int C, void* stream);
+
 /* ==========================================================================================
  * bf16 storage, fp32 accumulate (BASELINE configs 3 and 5).  Same layouts and geometry as the fp32 entry
  * points, element type bfloat16 wherever a pointer is typed void*: the convolution runs on

@@ -122,6 +122,9 @@ SIGNATURES = {
     "bevf_centernet_decode_f32": (C.c_int, [C.POINTER(DecodeDesc), C.c_void_p]),
     "bevf_centernet_targets_f32": (C.c_int, [C.POINTER(TargetsDesc), C.c_void_p]),
     "bevf_nms_keep_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_boxes_iou_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "bevf_nms_boxes_work_bytes": (C.c_size_t, [C.c_int] * 2),
+    "bevf_nms_boxes_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p] * 8),
     "bevf_centernet_loss_work_floats": (C.c_size_t, []),
     "bevf_centernet_loss_f32": (C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
     "bevf_voxelize_work_bytes": (C.c_size_t, [C.c_int] * 2),
@@ -587,6 +590,68 @@ def nms_keep(heat: torch.Tensor, out: torch.Tensor, planes: int, H: int, W: int)
     if heat.numel() != planes * H * W or out.numel() != planes * H * W:
         raise BevfError("nms_keep: buffer sizes do not match planes,H,W")
     _call("bevf_nms_keep_f32", _pc(heat), _pc(out), planes, H, W)
+
+
+IOU_MODES = {"bev": 0, "3d": 1}
+NMS_MODES = {"rotate": 0, "circle": 1}
+
+
+def _box_sets(what: str, *sets) -> None:
+    for t in sets:
+        if t.dim() != 3 or t.shape[2] != 7 or t.shape[0] != sets[0].shape[0] or t.shape[0] == 0 or t.shape[1] == 0:
+            raise BevfError(f"{what}: boxes must be non-empty (B,N,7) sets with one B, got {tuple(t.shape)}")
+
+
+def boxes_iou(a: torch.Tensor, b: torch.Tensor, mode: str, count_a: Optional[torch.Tensor] = None,
+              count_b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pairwise IoU (bevf_boxes_iou_f32) of a (B,N,7) with b (B,M,7) -> (B,N,M); mode 'bev' | '3d'; count_* (B,) int32 or None."""
+    if mode not in IOU_MODES:
+        raise BevfError(f"boxes_iou: mode must be one of {sorted(IOU_MODES)}, got {mode!r}")
+    _box_sets("boxes_iou", a, b)
+    B, N, M = a.shape[0], a.shape[1], b.shape[1]
+    _need("boxes_iou", count_a=(count_a, B), count_b=(count_b, B))
+    out = torch.empty(B, N, M, dtype=torch.float32, device=a.device)
+    _call("bevf_boxes_iou_f32", _pc(a), _pc(count_a, torch.int32), _pc(b), _pc(count_b, torch.int32), _p(out), B, N, M,
+          IOU_MODES[mode])
+    return out
+
+
+def nms_boxes_work_bytes(B: int, N: int) -> int:
+    return int(lib().bevf_nms_boxes_work_bytes(B, N))
+
+
+def nms_boxes(boxes: torch.Tensor, count: Optional[torch.Tensor], mode: str, thresh: float, post_max: int,
+              scores: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+              velocities: Optional[torch.Tensor] = None, class_aware: bool = False, gather: bool = False):
+    """Greedy NMS (bevf_nms_boxes_f32) over (B,N,7) boxes in descending score order; mode 'rotate' (thresh = IoU threshold) |
+    'circle' (thresh = radius).  Returns (keep_idx (B,N) int32 padded with -1, keep_count (B,) int32) and, with gather=True, also
+    the kept boxes / scores / labels / velocities (those given) compacted in the same order, zero padded."""
+    if mode not in NMS_MODES:
+        raise BevfError(f"nms_boxes: mode must be one of {sorted(NMS_MODES)}, got {mode!r}")
+    _box_sets("nms_boxes", boxes)
+    B, N = boxes.shape[0], boxes.shape[1]
+    if N > 4096:
+        raise BevfError(f"nms_boxes: N={N} exceeds the kernel's 4096 boxes per frame")
+    if class_aware and labels is None:
+        raise BevfError("nms_boxes: class_aware needs labels")
+    if int(post_max) <= 0 or not float(thresh) >= 0.0:
+        raise BevfError("nms_boxes: post_max must be positive and the threshold / radius >= 0")
+    _need("nms_boxes", count=(count, B), scores=(scores, B * N), labels=(labels, B * N), velocities=(velocities, B * N * 2))
+    dev = boxes.device
+    keep_idx = torch.empty(B, N, dtype=torch.int32, device=dev)
+    keep_count = torch.empty(B, dtype=torch.int32, device=dev)
+    work = torch.empty(-(-nms_boxes_work_bytes(B, N) // 8), dtype=torch.int64, device=dev)
+    o_boxes = torch.empty(B, N, 7, device=dev) if gather else None
+    o_scores = torch.empty(B, N, device=dev) if gather and scores is not None else None
+    o_labels = torch.empty(B, N, dtype=torch.int64, device=dev) if gather and labels is not None else None
+    o_vels = torch.empty(B, N, 2, device=dev) if gather and velocities is not None else None
+    _call("bevf_nms_boxes_f32", _pc(boxes), _pc(scores), _pc(labels, torch.int64), _pc(velocities), _pc(count, torch.int32),
+          B, N, NMS_MODES[mode], float(thresh), int(class_aware), int(post_max), _p(work, torch.int64),
+          _p(keep_idx, torch.int32), _p(keep_count, torch.int32), _p(o_boxes), _p(o_scores), _p(o_labels, torch.int64),
+          _p(o_vels))
+    if gather:
+        return keep_idx, keep_count, o_boxes, o_scores, o_labels, o_vels
+    return keep_idx, keep_count
 
 
 def centernet_targets(boxes, labels, has_vel, out: dict, B: int, nmax: int, H: int, W: int, Cn: int,

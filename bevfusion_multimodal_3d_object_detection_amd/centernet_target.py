@@ -16,18 +16,29 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import box_ops
 from . import engine as E
+from .box_ops import decode_settings  # noqa: F401
 
 PC_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
 
 
 def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
-            true_labels: bool = False) -> List[Dict[str, torch.Tensor]]:
+            true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
+            nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+    box_ops.check_nms_args(nms_type, nms_iou_thresh, nms_radius, nms_pre_max, class_aware, true_labels)
     heat = predictions["heatmap"]
     E.require_cuda(heat)
     pred = {k: predictions[k].float().contiguous() for k in ("heatmap", "offset", "size", "rot", "vel")}
-    boxes, scores, labels, vels, count = L.centernet_decode(pred, max_detections, float(score_thresh),
+    K = max_detections if nms_type is None else int(nms_pre_max)
+    boxes, scores, labels, vels, count = L.centernet_decode(pred, K, float(score_thresh),
                                                             float(voxel_size), PC_RANGE[0], PC_RANGE[1], true_labels)
+    if nms_type is not None:
+        # box NMS over the count[b] candidates above score_thresh (already in descending score order); the survivors come back
+        # compacted and cut to max_detections, and their number replaces `count` in the one host sync below
+        thresh = float(nms_radius) if nms_type == "circle" else float(nms_iou_thresh)
+        _, count, boxes, scores, labels, vels = L.nms_boxes(boxes, count, nms_type, thresh, int(max_detections), scores=scores,
+                                                            labels=labels, velocities=vels, class_aware=class_aware, gather=True)
     counts = count.cpu().tolist()                     # the reference syncs here too (mask.sum() == 0, ref :362)
     out = []
     for b, n in enumerate(counts):
@@ -41,9 +52,14 @@ def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detec
 
 
 def decode_centernet_predictions(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3,
-                                 max_detections: int = 100, true_labels: bool = False) -> List[Dict[str, torch.Tensor]]:
-    """ref src/centernet_target.py:326-413 (2.048 m cells)."""
-    return _decode(predictions, score_thresh, max_detections, 2.048, true_labels)
+                                 max_detections: int = 100, true_labels: bool = False, *, nms_type: Optional[str] = None,
+                                 nms_iou_thresh: float = 0.5, nms_radius: Optional[float] = None, nms_pre_max: int = 512,
+                                 class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+    """ref src/centernet_target.py:326-413 (2.048 m cells).  nms_type 'rotate' | 'circle' (opt-in, not in the reference): decode the
+    nms_pre_max best peaks, run box NMS over those above score_thresh (box_ops; rotated IoU > nms_iou_thresh, or centres closer
+    than nms_radius metres; class_aware: within a label only, needs true_labels) and return the first max_detections survivors."""
+    return _decode(predictions, score_thresh, max_detections, 2.048, true_labels, nms_type, nms_iou_thresh, nms_radius,
+                   nms_pre_max, class_aware)
 
 
 def _nms(heat: torch.Tensor, kernel: int = 3) -> torch.Tensor:

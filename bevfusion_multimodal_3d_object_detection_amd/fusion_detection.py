@@ -9,20 +9,25 @@ importable names that raise on construction (out of scope a
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
 from . import centernet_target as _ct
+from .box_ops import decode_settings  # noqa: F401
 from .fusion import CenterNetHead, _OutOfScope  # noqa: F401  (same head; ref :376-473 duplicates fusion.py)
 
 
 def decode_centernet_predictions(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3,
-                                 max_detections: int = 100, true_labels: bool = False) -> List[Dict[str, torch.Tensor]]:
-    """ref src/fusion_detection.py:695-780 (voxel_size 0.512)."""
-    return _ct._decode(predictions, score_thresh, max_detections, 0.512, true_labels)
+                                 max_detections: int = 100, true_labels: bool = False, *, nms_type: Optional[str] = None,
+                                 nms_iou_thresh: float = 0.5, nms_radius: Optional[float] = None, nms_pre_max: int = 512,
+                                 class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+    """ref src/fusion_detection.py:695-780 (voxel_size 0.512).  The nms_* / class_aware keywords switch the box NMS on, as in
+    centernet_target.decode_centernet_predictions."""
+    return _ct._decode(predictions, score_thresh, max_detections, 0.512, true_labels, nms_type, nms_iou_thresh, nms_radius,
+                       nms_pre_max, class_aware)
 
 
 _nms = _ct._nms

@@ -258,6 +258,44 @@ int bevf_centernet_targets_f32(const bevf_targets_desc* d, void* stream);
 /* _nms of ref src/centernet_target.py:416-421: out = heat * (maxpool3x3(heat) == heat), planes = B*C.  */
 int bevf_nms_keep_f32(const float* heat, float* out, int planes, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Box-to-box geometry of the decode path (no counterpart in the reference: its YAML's nms_threshold is unread and
+ * its only IoU, inference.py _compute_iou_3d, is axis-aligned).
+ *
+ * Box convention, the one the decode and the reference's drawing code imply: a box [x, y, z, w, l, h, yaw] is the
+ * rectangle centred at (x, y) with extent l ALONG the heading (cos yaw, sin yaw) and w ACROSS it; its z-extent is
+ * [z - h/2, z + h/2].  The reference's axis-aligned formula (w along x, l along y) therefore coincides with the rotated
+ * one at yaw = pi/2, not at yaw = 0.
+ *
+ * All entry points take padded per-frame sets [B][N][7] and int32 count[B] (NULL = every frame holds N boxes; values
+ * are clamped to [0, N]).  Deterministic (two runs are bit-equal), no atomics, no allocation, no host synchronisation.
+ *
+ * bevf_boxes_iou_f32: out[B][N][M] = IoU of a[b][i] with b[b][j].  mode BEVF_IOU_BEV: area of the intersection of the two
+ * rotated rectangles / (area_a + area_b - inter); BEVF_IOU_3D: that intersection times the z-overlap / (vol_a + vol_b -
+ * inter_vol).  Box b is moved into box a's frame before any other arithmetic.  A box with w <= 0 or l <= 0 (for 3D also
+ * h <= 0) has IoU 0 with everything; every value is finite and in [0, 1] (NaN / inf inputs give 0); entries with
+ * i >= count_a[b] or j >= count_b[b] are 0.
+ *
+ * bevf_nms_boxes_f32: greedy NMS per frame over boxes already in descending score order: box i is kept iff no kept box
+ * j < i suppresses it.  BEVF_NMS_ROTATE: suppress when IoU_bev(i, j) > thresh; BEVF_NMS_CIRCLE: when the squared centre
+ * distance < thresh^2 (thresh = the radius in metres).  class_aware: only a box with the same label suppresses.  N <= 4096.
+ * Outputs, compacted in input order and truncated to post_max: keep_idx [B][N] (indices into the frame, -1 padded),
+ * keep_count [B], and -- each optional, NULL to skip -- the gathered boxes [B][N][7], scores [B][N], labels [B][N],
+ * velocities [B][N][2], zero padded.  scores / velocities are only gathered; labels are also read when class_aware.
+ * work: bevf_nms_boxes_work_bytes(B, N) bytes, 8-byte aligned (the [B][N][ceil(N/64)] suppression mask).
+ * ------------------------------------------------------------------------------------------ */
+#define BEVF_IOU_BEV 0
+#define BEVF_IOU_3D 1
+#define BEVF_NMS_ROTATE 0
+#define BEVF_NMS_CIRCLE 1
+int bevf_boxes_iou_f32(const float* a, const int32_t* count_a, const float* b, const int32_t* count_b, float* out,
+                       int B, int N, int M, int mode, void* stream);
+size_t bevf_nms_boxes_work_bytes(int B, int N);
+int bevf_nms_boxes_f32(const float* boxes, const float* scores, const int64_t* labels, const float* velocities,
+                       const int32_t* count, int B, int N, int mode, float thresh, int class_aware, int post_max,
+                       void* work, int32_t* keep_idx, int32_t* keep_count, float* out_boxes, float* out_scores,
+                       int64_t* out_labels, float* out_velocities, void* stream);
+
 /* CenterNetLoss.forward, ref src/centernet_target.py:476-622: penalty-reduced focal loss on
  * clamp(sigmoid(pred)) -- the reference applies sigmoid to the already-sigmoided head output and so does
  * this -- and mask-weighted gather-L1 for offset/size/rot/vel.  out[6] = total, heatmap, offset, size, rot,

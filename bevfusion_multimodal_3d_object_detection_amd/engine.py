@@ -637,38 +637,179 @@ def frame_camera_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int
     return eng._frame_tables
 
 
+def concat_slots(fus: nn.Module, branches, feats, text: str, B: Optional[int] = None):
+    """-> ((branch, input) of every modality that has both, in slot order [camera, LiDAR, radar]; channels of the concatenated map,
+    checked against bev_fusion's first conv; frames B, the first input's leading dimension unless given).  text: the mismatch
+    message (FusionEngine's is torch's own, training.FusionTape has another)."""
+    present = [(b, x) for b, x in zip(branches, feats) if b is not None and x is not None]
+    if not present:
+        raise ValueError("No modality features provided")
+    B = B or present[0][1].shape[0]
+    ccs = fus.bev_channels * len(present)
+    cout, cin = fus.bev_fusion[0].weight.shape[:2]
+    if ccs != cin:
+        raise RuntimeError(text.format(cout=cout, cin=cin, B=B, ccs=ccs, h=fus.bev_h, w=fus.bev_w))
+    return present, ccs, B
+
+
+class _FusionBranch:
+    """One input branch of FusionEngine: pack(m) folds its weights, run(x, B, out, ccs, cam_geom, camera_calib) turns the branch input
+    x into the concat slice it owns (out = concat[slot * bc:], bev_channels wide, row stride ccs).  Workspaces: the engine's buf()."""
+
+    def __init__(self, eng: "FusionEngine"):
+        self.eng, m = eng, eng.module
+        self.grid = (m.bev_h, m.bev_w, m.bev_channels)
+
+
+class _CameraBranch(_FusionBranch):
+    def pack(self, m) -> None:
+        self.c1 = pack_conv(m.camera_proj[0], m.camera_proj[1], True)
+        self.c2 = pack_conv(m.camera_proj[3], m.camera_proj[4], True)
+
+
+class CameraMeanBranch(_CameraBranch):
+    """The reference's camera branch: camera average, camera_proj on the image grid, bilinear resize into the concat slice."""
+
+    def run(self, cam, B, out, ccs, geom, _) -> None:
+        _, ncam, Hc, Wc = geom
+        buf, (Sh, Sw, bc), Cc = self.eng.buf, self.grid, self.c1.cin
+        pooled = cam
+        if ncam > 1:
+            pooled = buf("cam_mean", B * Hc * Wc * Cc)
+            with _span("bev_pool", nbytes=float(cam.element_size()) * B * Hc * Wc * Cc * (ncam + 1)):
+                L.cam_mean(cam, pooled, B, ncam, Hc * Wc, Cc)
+        t1 = buf("cam_t1", B * Hc * Wc * self.c1.cout)
+        _run_conv(self.c1, pooled, t1, B, Hc, Wc)
+        t2 = buf("cam_t2", B * Hc * Wc * self.c2.cout)
+        _run_conv(self.c2, t1, t2, B, Hc, Wc)
+        with _span("bev_pool", nbytes=float(t2.element_size()) * B * bc * (Hc * Wc + Sh * Sw)):
+            L.bilinear_nhwc(t2, out, B, Hc, Wc, bc, bc, Sh, Sw, ccs)
+
+
+class CameraProjectBranch(_CameraBranch):
+    """The same camera_proj after camera rig -> BEV grid (one gather), its second conv into the concat slice.  camera_calib None:
+    the module rig's cached table; else per-frame tables built here into the engine's buffers."""
+
+    def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
+        _, ncam, Hc, Wc = geom
+        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
+        if camera_calib is None:
+            tab = camera_table(m, ncam, Hc, Wc, cam.device)
+        else:
+            with _span("cam_table_build"):
+                tab = frame_camera_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
+        proj = buf("cam_proj", B * Sh * Sw * Cc)
+        with _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (ncam * Hc * Wc + Sh * Sw)):
+            tab.project(cam, proj, B, Cc)
+        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
+        _run_conv(self.c1, proj, t1, B, Sh, Sw)
+        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+
+
+class LidarVectorBranch(_FusionBranch):
+    """Input: the PointNet vector (B, C_l).  lidar_init to a start_size^2 canvas, conv, x2 bilinear, conv into the concat slice."""
+
+    def pack(self, m) -> None:
+        l0, l2 = m.lidar_init[0], m.lidar_init[2]
+        self.li0 = (l0.weight.detach().contiguous(), l0.bias.detach().float().contiguous())
+        self.li2 = (l2.weight.detach().contiguous(), l2.bias.detach().float().contiguous())
+        self.up1 = pack_conv(m.lidar_upsample[0], m.lidar_upsample[1], True)
+        self.up2 = pack_conv(m.lidar_upsample[4], m.lidar_upsample[5], True)
+
+    def run(self, x, B, out, ccs, *_) -> None:
+        buf, (Sh, Sw, bc), s0 = self.eng.buf, self.grid, self.eng.module.lidar_start_size
+        hid = buf("lid_h", B * self.li0[0].shape[0], torch.float32)       # small per-frame vectors stay fp32
+        L.linear(x.float().contiguous(), self.li0[0], self.li0[1], hid, B, self.li0[0].shape[1], self.li0[0].shape[0], True)
+        O = self.li2[0].shape[0]
+        ch = O // (s0 * s0)
+        grid0 = buf("lid_g0", B * O)
+        L.linear(hid, self.li2[0], self.li2[1], grid0, B, self.li2[0].shape[1], O, False, s0 * s0, ch)
+        g1 = buf("lid_g1", B * s0 * s0 * self.up1.cout)
+        _run_conv(self.up1, grid0, g1, B, s0, s0)
+        s1 = 2 * s0
+        g2 = buf("lid_g2", B * s1 * s1 * self.up1.cout)
+        L.bilinear_nhwc(g1, g2, B, s0, s0, self.up1.cout, self.up1.cout, s1, s1, self.up1.cout)
+        if (s1, s1) == (Sh, Sw):
+            _run_conv(self.up2, g2, out, B, s1, s1, y_cs=ccs)
+        else:
+            # extension beyond the reference (which crashes at the concat for BEV != 50x50, SURVEY.md 0.2):
+            # bilinear resize of the 50x50 LiDAR map, exactly like the camera branch
+            g3 = buf("lid_g3", B * s1 * s1 * bc)
+            _run_conv(self.up2, g2, g3, B, s1, s1)
+            L.bilinear_nhwc(g3, out, B, s1, s1, bc, bc, Sh, Sw, ccs)
+
+
+class LidarPillarsBranch(_FusionBranch):
+    """Input: the PointPillars NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype, already on the fusion grid -- two
+    conv+BN+ReLU, the second into the concat slice."""
+
+    def pack(self, m) -> None:
+        self.c1 = pack_conv(m.lidar_bev[0], m.lidar_bev[1], True)
+        self.c2 = pack_conv(m.lidar_bev[3], m.lidar_bev[4], True)
+
+    def run(self, x, B, out, ccs, *_) -> None:
+        Sh, Sw, _ = self.grid
+        if x.dim() != 4 or tuple(x.shape[1:]) != (Sh, Sw, self.c1.cin) or x.dtype != self.eng.dtype:
+            raise L.BevfError(f"BEV fusion (PointPillars): expected an NHWC {self.eng.dtype} canvas (B, {Sh}, {Sw}, {self.c1.cin}), "
+                              f"got {x.dtype} {tuple(x.shape)}")
+        t = self.eng.buf("lid_bev1", B * Sh * Sw * self.c1.cout)
+        _run_conv(self.c1, x, t, B, Sh, Sw)
+        _run_conv(self.c2, t, out, B, Sh, Sw, y_cs=ccs)
+
+
+class RadarBranch(_FusionBranch):
+    """Input: the radar vector (B, C_r).  radar_proj, broadcast to every cell, radar_refine's two conv+BN+ReLU."""
+
+    def pack(self, m) -> None:
+        r0 = m.radar_proj[0]
+        self.rp = (r0.weight.detach().contiguous(), r0.bias.detach().float().contiguous())
+        # exact kernel whatever the mode: the 5x5 border-class shortcut below must reproduce the full-map convolution
+        # bit for bit, which a position-dependent Winograd tiling would not (and these two launches cost nothing)
+        self.c1 = pack_conv(m.radar_refine[0], m.radar_refine[1], True, wino_ok=False)
+        self.c2 = pack_conv(m.radar_refine[3], m.radar_refine[4], True, wino_ok=False)
+
+    def run(self, x, B, out, ccs, *_) -> None:
+        buf, (Sh, Sw, bc) = self.eng.buf, self.grid
+        rv = buf("rad_v", B * bc, torch.float32)
+        L.linear(x.float().contiguous(), self.rp[0], self.rp[1], rv, B, self.rp[0].shape[1], bc, True)
+        # exact shortcut: two 3x3/pad-1 convs on a constant image have 5x5 distinct pixels (bevpool.hip)
+        collapse = Sh >= 5 and Sw >= 5 and self.eng.collapse_radar
+        h, w = (5, 5) if collapse else (Sh, Sw)
+        r0 = buf("rad_0", B * h * w * bc)
+        L.broadcast_nhwc(rv, r0, B, h * w, bc, bc)
+        r1 = buf("rad_1", B * h * w * bc)
+        _run_conv(self.c1, r0, r1, B, h, w)
+        if collapse:
+            r2 = buf("rad_2", B * 25 * bc)
+            _run_conv(self.c2, r1, r2, B, 5, 5)
+            L.expand_border_classes(r2, out, B, Sh, Sw, bc, ccs)
+        else:
+            _run_conv(self.c2, r1, out, B, Sh, Sw, y_cs=ccs)
+
+
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
+    BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, pointnet=LidarVectorBranch, pillars=LidarPillarsBranch)
 
     def __init__(self, module: nn.Module):
         super().__init__(module)
         self._camera_tables: Dict[tuple, CameraTable] = {}
         self._frame_tables: Optional[FrameCameraTables] = None
+        m = module
+        self.branches = [self.BRANCHES[m.camera_view_transform](self) if m.use_camera else None,
+                         self.BRANCHES[m.lidar_kind](self) if m.use_lidar else None, RadarBranch(self) if m.use_radar else None]
 
     def drop_camera_tables(self) -> None:
         self._camera_tables.clear()
 
+    def invalidate_frame_tables(self) -> None:
+        """A graph replay is about to rebuild the per-frame tables (FrameCameraTables.invalidate)."""
+        self._frame_tables.invalidate()
+
     def pack(self) -> None:
         m = self.module
-        if m.use_camera:
-            self.cam1 = pack_conv(m.camera_proj[0], m.camera_proj[1], True)
-            self.cam2 = pack_conv(m.camera_proj[3], m.camera_proj[4], True)
-        if m.use_lidar and getattr(m, "lidar_kind", "pointnet") == "pillars":
-            self.lb1 = pack_conv(m.lidar_bev[0], m.lidar_bev[1], True)
-            self.lb2 = pack_conv(m.lidar_bev[3], m.lidar_bev[4], True)
-        elif m.use_lidar:
-            l0, l2 = m.lidar_init[0], m.lidar_init[2]
-            self.li0 = (l0.weight.detach().contiguous(), l0.bias.detach().float().contiguous())
-            self.li2 = (l2.weight.detach().contiguous(), l2.bias.detach().float().contiguous())
-            self.lup1 = pack_conv(m.lidar_upsample[0], m.lidar_upsample[1], True)
-            self.lup2 = pack_conv(m.lidar_upsample[4], m.lidar_upsample[5], True)
-        if m.use_radar:
-            r0 = m.radar_proj[0]
-            self.rp = (r0.weight.detach().contiguous(), r0.bias.detach().float().contiguous())
-            # exact kernel whatever the mode: the 5x5 border-class shortcut below must reproduce the full-map convolution
-            # bit for bit, which a position-dependent Winograd tiling would not (and these two launches cost nothing)
-            self.rr1 = pack_conv(m.radar_refine[0], m.radar_refine[1], True, wino_ok=False)
-            self.rr2 = pack_conv(m.radar_refine[3], m.radar_refine[4], True, wino_ok=False)
+        for branch in filter(None, self.branches):
+            branch.pack(m)
         self.f1 = pack_conv(m.bev_fusion[0], m.bev_fusion[1], True)
         self.f2 = pack_conv(m.bev_fusion[3], m.bev_fusion[4], True)
 
@@ -682,103 +823,12 @@ class FusionEngine(_Engine):
         m = self.module
         Sh, Sw, bc = m.bev_h, m.bev_w, m.bev_channels
         P = Sh * Sw
-        present = []
-        if m.use_camera and cam is not None:
-            present.append("c")
-        if m.use_lidar and lidar is not None:
-            present.append("l")
-        if m.use_radar and radar is not None:
-            present.append("r")
-        if not present:
-            raise ValueError("No modality features provided")
-        B = cam_geom[0] if "c" in present else (lidar.shape[0] if "l" in present else radar.shape[0])
-        ccs = bc * len(present)
-        if ccs != self.f1.cin:
-            raise RuntimeError(f"Given groups=1, weight of size [{self.f1.cout}, {self.f1.cin}, 3, 3], expected input"
-                               f"[{B}, {ccs}, {Sh}, {Sw}] to have {self.f1.cin} channels, but got {ccs} channels instead")
+        text = ("Given groups=1, weight of size [{cout}, {cin}, 3, 3], expected input[{B}, {ccs}, {h}, {w}] to have {cin} channels, "
+                "but got {ccs} channels instead")
+        present, ccs, B = concat_slots(m, self.branches, (cam, lidar, radar), text, cam_geom and cam_geom[0])
         concat = self.buf("concat", B * P * ccs)
-        slot = 0
-        if "c" in present and getattr(m, "camera_view_transform", "mean") == "project":
-            # camera rig -> BEV grid (one gather), then camera_proj on the grid, its second conv into the concat slice
-            _, ncam, Hc, Wc = cam_geom
-            Cc = self.cam1.cin
-            if camera_calib is None:
-                tab = camera_table(m, ncam, Hc, Wc, cam.device)
-            else:
-                with _span("cam_table_build"):
-                    tab = frame_camera_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
-            proj = self.buf("cam_proj", B * P * Cc)
-            with _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (ncam * Hc * Wc + P)):
-                tab.project(cam, proj, B, Cc)
-            t1 = self.buf("cam_t1", B * P * self.cam1.cout)
-            _run_conv(self.cam1, proj, t1, B, Sh, Sw)
-            _run_conv(self.cam2, t1, concat[slot * bc:], B, Sh, Sw, y_cs=ccs)
-            slot += 1
-        elif "c" in present:
-            _, ncam, Hc, Wc = cam_geom
-            Cc = self.cam1.cin
-            pooled = cam
-            if ncam > 1:
-                pooled = self.buf("cam_mean", B * Hc * Wc * Cc)
-                with _span("bev_pool", nbytes=float(cam.element_size()) * B * Hc * Wc * Cc * (ncam + 1)):
-                    L.cam_mean(cam, pooled, B, ncam, Hc * Wc, Cc)
-            t1 = self.buf("cam_t1", B * Hc * Wc * self.cam1.cout)
-            _run_conv(self.cam1, pooled, t1, B, Hc, Wc)
-            t2 = self.buf("cam_t2", B * Hc * Wc * self.cam2.cout)
-            _run_conv(self.cam2, t1, t2, B, Hc, Wc)
-            with _span("bev_pool", nbytes=float(t2.element_size()) * B * bc * (Hc * Wc + Sh * Sw)):
-                L.bilinear_nhwc(t2, concat[slot * bc:], B, Hc, Wc, bc, bc, Sh, Sw, ccs)
-            slot += 1
-        if "l" in present and getattr(m, "lidar_kind", "pointnet") == "pillars":
-            # PointPillars: the canvas is already on the fusion grid -- two conv+BN+ReLU, the second into the concat slice
-            if lidar.dim() != 4 or tuple(lidar.shape[1:]) != (Sh, Sw, self.lb1.cin) or lidar.dtype != self.dtype:
-                raise L.BevfError(f"BEV fusion (PointPillars): expected an NHWC {self.dtype} canvas (B, {Sh}, {Sw}, {self.lb1.cin}), "
-                                  f"got {lidar.dtype} {tuple(lidar.shape)}")
-            t = self.buf("lid_bev1", B * P * self.lb1.cout)
-            _run_conv(self.lb1, lidar, t, B, Sh, Sw)
-            _run_conv(self.lb2, t, concat[slot * bc:], B, Sh, Sw, y_cs=ccs)
-            slot += 1
-        elif "l" in present:
-            s0 = m.lidar_start_size
-            hid = self.buf("lid_h", B * self.li0[0].shape[0], torch.float32)       # small per-frame vectors stay fp32
-            L.linear(lidar.float().contiguous(), self.li0[0], self.li0[1], hid, B, self.li0[0].shape[1], self.li0[0].shape[0], True)
-            O = self.li2[0].shape[0]
-            ch = O // (s0 * s0)
-            grid0 = self.buf("lid_g0", B * O)
-            L.linear(hid, self.li2[0], self.li2[1], grid0, B, self.li2[0].shape[1], O, False, s0 * s0, ch)
-            g1 = self.buf("lid_g1", B * s0 * s0 * self.lup1.cout)
-            _run_conv(self.lup1, grid0, g1, B, s0, s0)
-            s1 = 2 * s0
-            g2 = self.buf("lid_g2", B * s1 * s1 * self.lup1.cout)
-            L.bilinear_nhwc(g1, g2, B, s0, s0, self.lup1.cout, self.lup1.cout, s1, s1, self.lup1.cout)
-            if (s1, s1) == (Sh, Sw):
-                _run_conv(self.lup2, g2, concat[slot * bc:], B, s1, s1, y_cs=ccs)
-            else:
-                # extension beyond the reference (which crashes at the concat for BEV != 50x50):
-                # bilinear resize of the 50x50 LiDAR map, exactly like the camera branch
-                g3 = self.buf("lid_g3", B * s1 * s1 * bc)
-                _run_conv(self.lup2, g2, g3, B, s1, s1)
-                L.bilinear_nhwc(g3, concat[slot * bc:], B, s1, s1, bc, bc, Sh, Sw, ccs)
-            slot += 1
-        if "r" in present:
-            rv = self.buf("rad_v", B * bc, torch.float32)
-            L.linear(radar.float().contiguous(), self.rp[0], self.rp[1], rv, B, self.rp[0].shape[1], bc, True)
-            if Sh >= 5 and Sw >= 5 and self.collapse_radar:
-                # exact shortcut: two 3x3/pad-1 convs on a constant image have 5x5 distinct pixels (bevpool.hip)
-                r0 = self.buf("rad_0", B * 25 * bc)
-                L.broadcast_nhwc(rv, r0, B, 25, bc, bc)
-                r1 = self.buf("rad_1", B * 25 * bc)
-                _run_conv(self.rr1, r0, r1, B, 5, 5)
-                r2 = self.buf("rad_2", B * 25 * bc)
-                _run_conv(self.rr2, r1, r2, B, 5, 5)
-                L.expand_border_classes(r2, concat[slot * bc:], B, Sh, Sw, bc, ccs)
-            else:
-                r0 = self.buf("rad_0", B * P * bc)
-                L.broadcast_nhwc(rv, r0, B, P, bc, bc)
-                r1 = self.buf("rad_1", B * P * bc)
-                _run_conv(self.rr1, r0, r1, B, Sh, Sw)
-                _run_conv(self.rr2, r1, concat[slot * bc:], B, Sh, Sw, y_cs=ccs)
-            slot += 1
+        for slot, (branch, x) in enumerate(present):
+            branch.run(x, B, concat[slot * bc:], ccs, cam_geom, camera_calib)
         f1 = self.buf("fus_1", B * P * self.f1.cout)
         _run_conv(self.f1, concat, f1, B, Sh, Sw)
         out = self.buf("fus_2", B * P * self.f2.cout)

@@ -452,7 +452,7 @@ class GraphedDetector:
                 self.static_calib[0].copy_(calib[0])
         if self.static_calib is not None:
             # the replay rebuilds the per-frame tables in the engine's buffers: a training tape that still needs its own rebuilds them
-            self.model.fusion._eng()._frame_tables.invalidate()
+            self.model.fusion._eng().invalidate_frame_tables()
         for dst, src in ((si, camera_imgs), (sp, lidar_points)):
             if dst is not None and src is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src)

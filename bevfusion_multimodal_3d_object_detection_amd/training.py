@@ -970,163 +970,194 @@ class RadarTape:
             self.sweeps[r].backward(dper[:B * R * feat].view(B, R, feat)[:, r].contiguous().view(-1), sink)
 
 
+class ConvPair:
+    """seq's two conv+BN+ReLU (seq[0:2] and seq[3:5]) back to back, as one layer record."""
+
+    def forward(self, seq, x, B, H, W):
+        self.c1, self.c2 = ConvBNLayer(seq[0], seq[1], True), ConvBNLayer(seq[3], seq[4], True)
+        return self.c2.forward(self.c1.forward(x, B, H, W)[0], B, H, W)[0]
+
+    def backward(self, d, sink):
+        return self.c1.backward(self.c2.backward(d, sink)[0], sink)[0]
+
+
+class _FusionBranchTape:
+    """One input branch of FusionTape, owning its layer records: forward(x, B, concat, ccs, slot, cam_geom, camera_calib) fills the
+    branch's bev_channels-wide slot of the concatenated NHWC map (row stride ccs), backward(dconcat, sink) returns the gradient of x."""
+
+    def __init__(self, fus):
+        self.fus, self.H, self.W, self.bc, self.pair = fus, fus.bev_h, fus.bev_w, fus.bev_channels, ConvPair()
+
+    def _slot(self, buf):
+        """This branch's [B*H*W][bev_channels] columns of a concatenated NHWC map."""
+        rows = self.B * self.H * self.W
+        return buf[:rows * self.ccs].view(rows, self.ccs)[:, self.slot * self.bc:(self.slot + 1) * self.bc]
+
+    def _pair_to_slot(self, seq, x, B, concat, ccs, slot) -> None:
+        """seq's conv pair on the fusion grid, then the copy into the slot."""
+        self.B, self.ccs, self.slot = B, ccs, slot
+        self._slot(concat)[:] = self.pair.forward(seq, x, B, self.H, self.W)[:B * self.H * self.W * self.bc].view(-1, self.bc)
+
+    def _pair_from_slot(self, dconcat, sink):
+        return self.pair.backward(self._slot(dconcat).contiguous().view(-1), sink)
+
+
+class CameraMeanBranchTape(_FusionBranchTape):
+    """Input NHWC features, geom = (B, ncam, Hc, Wc): camera average, camera_proj on the image grid, resize into the slot."""
+
+    def forward(self, cam, B, concat, ccs, slot, geom, _) -> None:
+        _, ncam, Hc, Wc = geom
+        Cc = self.fus.camera_proj[0].weight.shape[1]
+        self.geom, self.slot = (B, ncam, Hc * Wc, Cc), slot
+        pooled = cam
+        if ncam > 1:
+            pooled = _new(B * Hc * Wc * Cc, cam.device)
+            L.cam_mean(cam, pooled, B, ncam, Hc * Wc, Cc)
+        t2 = self.pair.forward(self.fus.camera_proj, pooled, B, Hc, Wc)
+        self.resize = Bilinear()
+        self.resize.forward(t2, B, Hc, Wc, self.bc, self.H, self.W, y=concat[slot * self.bc:], y_cs=ccs)
+
+    def backward(self, dconcat, sink):
+        dcam = self.pair.backward(self.resize.backward(dconcat[self.slot * self.bc:]), sink)
+        B, ncam, Pc, Cc = self.geom
+        if ncam > 1:
+            dpooled, dcam = dcam, _new(B * ncam * Pc * Cc, dconcat.device)
+            L.cam_mean_bwd(dpooled, dcam, B, ncam, Pc, Cc)
+        return dcam
+
+
+class CameraProjectBranchTape(_FusionBranchTape):
+    """Input NHWC features, geom = (B, ncam, Hc, Wc): the projection table onto the grid (the module rig's, or per-frame tables built
+    here from calib = (fp64 [B, ncam, 4, 4], image_size)), camera_proj there, the slot copy; the transposed table in the backward.  The
+    per-frame tables live in the fusion engine's buffers: the tape keeps the calibration and the build's version, and its backward
+    rebuilds them if another forward has replaced them since."""
+
+    def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
+        _, ncam, Hc, Wc = geom
+        fus, dev = self.fus, cam.device
+        Cc = fus.camera_proj[0].weight.shape[1]
+        self.geom, self.calib = (ncam, Hc, Wc, Cc), None
+        if calib is None:
+            self.table = E.camera_table(fus, ncam, Hc, Wc, dev)
+        else:
+            self.table = E.frame_camera_tables(fus, calib, B, ncam, Hc, Wc, dev)
+            self.calib, self.version = (calib[0].to(dev).clone(), calib[1]), self.table.version
+        proj = _new(B * self.H * self.W * Cc, dev)
+        self.table.project(cam, proj, B, Cc)
+        self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
+
+    def backward(self, dconcat, sink):
+        dproj = self._pair_from_slot(dconcat, sink)
+        B, (ncam, Hc, Wc, Cc) = self.B, self.geom
+        dcam = _new(B * ncam * Hc * Wc * Cc, dconcat.device)
+        if self.calib is not None and self.table.version != self.version:
+            self.table = E.frame_camera_tables(self.fus, self.calib, B, ncam, Hc, Wc, dconcat.device)
+            self.version = self.table.version
+        self.table.project_backward(dproj, dcam, B, Cc)                     # transposed table: every element written once
+        return dcam
+
+
+class LidarVectorBranchTape(_FusionBranchTape):
+    """Input the PointNet vector (B*C_l): lidar_init to the start_size^2 canvas, conv, x2 bilinear, conv, resize to the grid."""
+
+    def forward(self, x, B, concat, ccs, slot, *_) -> None:
+        fus, s0 = self.fus, self.fus.lidar_start_size
+        self.slot = slot
+        self.li0 = LinearLayer(fus.lidar_init[0], True)
+        O = fus.lidar_init[2].weight.shape[0]
+        self.li2 = LinearLayer(fus.lidar_init[2], False, (s0 * s0, O // (s0 * s0)))
+        hid = self.li0.forward(x, B)
+        grid0 = self.li2.forward(hid, B)
+        self.c1 = ConvBNLayer(fus.lidar_upsample[0], fus.lidar_upsample[1], True)
+        self.c2 = ConvBNLayer(fus.lidar_upsample[4], fus.lidar_upsample[5], True)
+        g1, _, _ = self.c1.forward(grid0, B, s0, s0)
+        self.up = Bilinear()
+        s1 = 2 * s0
+        g2 = self.up.forward(g1, B, s0, s0, self.c1.cout, s1, s1)
+        g3, _, _ = self.c2.forward(g2, B, s1, s1)
+        self.resize = Bilinear()                                       # (the identity map when s1 == H == W)
+        self.resize.forward(g3, B, s1, s1, self.bc, self.H, self.W, y=concat[slot * self.bc:], y_cs=ccs)
+
+    def backward(self, dconcat, sink):
+        dg2, _ = self.c2.backward(self.resize.backward(dconcat[self.slot * self.bc:]), sink)
+        dgrid0, _ = self.c1.backward(self.up.backward(dg2), sink)
+        return self.li0.backward(self.li2.backward(dgrid0, sink), sink)
+
+
+class LidarPillarsBranchTape(_FusionBranchTape):
+    """Input the PointPillars NHWC canvas, on the fusion grid already: lidar_bev's two conv+BN+ReLU, then the slot copy."""
+
+    def forward(self, x, B, concat, ccs, slot, *_) -> None:
+        self._pair_to_slot(self.fus.lidar_bev, x, B, concat, ccs, slot)
+
+    def backward(self, dconcat, sink):
+        return self._pair_from_slot(dconcat, sink)
+
+
+class RadarBranchTape(_FusionBranchTape):
+    """Input the radar vector (B*C_r): radar_proj, broadcast to every cell, radar_refine's two conv+BN+ReLU, then the slot copy."""
+
+    def forward(self, x, B, concat, ccs, slot, *_) -> None:
+        P, bc = self.H * self.W, self.bc
+        self.rp = LinearLayer(self.fus.radar_proj[0], True)
+        rv = self.rp.forward(x, B)
+        r0 = _new(B * P * bc, x.device)
+        L.broadcast_nhwc(rv, r0, B, P, bc, bc)
+        self._pair_to_slot(self.fus.radar_refine, r0, B, concat, ccs, slot)
+
+    def backward(self, dconcat, sink):
+        P, bc = self.H * self.W, self.bc
+        dr0 = self._pair_from_slot(dconcat, sink)
+        drv = torch.cat([colsum(dr0[b * P * bc:], P, bc) for b in range(self.B)])      # d(broadcast) = sum over cells
+        return self.rp.backward(drv.contiguous(), sink)
+
+
 class FusionTape:
     """FlexibleBEVFusion (ref src/fusion.py:209-297): NHWC camera features [B*ncam*Hc*Wc*C] with cam_geom = (B, ncam, Hc, Wc),
     LiDAR (B, C_l) vectors or the PointPillars NHWC canvas on the fusion grid, radar (B, C_r) vectors -> fused NHWC map
-    [B*H*W*cout].  Camera branch 'mean': camera average, camera_proj on the image grid, bilinear resize; 'project': the rig's
-    projection table (engine.camera_table) onto the grid, camera_proj there, the transposed table in the backward.  Each modality present fills one bev_channels slot of the concatenated map, in the order camera, LiDAR, radar."""
+    [B*H*W*cout].  One branch tape per modality the module was built with; each one present fills one bev_channels slot of the
+    concatenated map.  The branches run forward in the order camera, LiDAR, radar and backward in reverse, and both orders are
+    relied on: RELU_TRACE records in forward order, and DetectorTape marks the gradients final (sink.ready()) in the camera
+    callback, after radar and LiDAR have contributed theirs."""
+
+    BRANCHES = dict(mean=CameraMeanBranchTape, project=CameraProjectBranchTape, pointnet=LidarVectorBranchTape,
+                    pillars=LidarPillarsBranchTape)
 
     def __init__(self, fus):
         self.fus = fus
-
-    def _slot(self, buf, slot):
-        """The [B*H*W][bev_channels] columns of `slot` in a concatenated NHWC map."""
-        bc, rows = self.fus.bev_channels, self.B * self.H * self.W
-        return buf[:rows * self.ccs].view(rows, self.ccs)[:, slot * bc:(slot + 1) * bc]
+        self.branches = [self.BRANCHES[fus.camera_view_transform](fus) if fus.use_camera else None,
+                         self.BRANCHES[fus.lidar_kind](fus) if fus.use_lidar else None, RadarBranchTape(fus) if fus.use_radar else None]
 
     def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None):
-        """camera_calib ('project' branch): (fp64 [B, ncam, 4, 4], image_size) -- per-frame tables built here on the device; the
-        tape keeps the calibration and the build's version, and its backward rebuilds the tables if another forward has
-        replaced them in the engine's buffers since."""
+        """camera_calib ('project' branch): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape."""
         fus = self.fus
         self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
-        Sh, Sw, bc = self.H, self.W, self.cout
-        P = Sh * Sw
-        self.has_cam, self.has_lid, self.has_rad = (f is not None for f in (cam_feat, lid_feat, rad_feat))
-        self.ccs = ccs = bc * (int(self.has_cam) + int(self.has_lid) + int(self.has_rad))
-        if ccs != fus.bev_fusion[0].weight.shape[1]:
-            raise RuntimeError(f"expected input to have {fus.bev_fusion[0].weight.shape[1]} channels, but got {ccs} channels instead")
-        dev = next(f for f in (cam_feat, lid_feat, rad_feat) if f is not None).device
-        concat = _new(B * P * ccs, dev)
-        slot = 0
-        self.cam_project = self.has_cam and getattr(fus, "camera_view_transform", "mean") == "project"
-        if self.cam_project:
-            # camera rig -> BEV grid (gather over the cell table), camera_proj's two conv+BN+ReLU on the grid, then the slice copy
-            _, ncam, Hc, Wc = cam_geom
-            Cc = fus.camera_proj[0].weight.shape[1]
-            self.cam_pool_geom = (B, ncam, Hc * Wc, Cc)
-            self.frame_calib = None
-            if camera_calib is None:
-                self.cam_table = E.camera_table(fus, ncam, Hc, Wc, dev)
-            else:
-                self.cam_table = E.frame_camera_tables(fus, camera_calib, B, ncam, Hc, Wc, dev)
-                self.frame_calib = ((camera_calib[0].to(dev).clone(), camera_calib[1]), self.cam_table.version, (ncam, Hc, Wc))
-            proj = _new(B * P * Cc, dev)
-            self.cam_table.project(cam_feat, proj, B, Cc)
-            self.cp1 = ConvBNLayer(fus.camera_proj[0], fus.camera_proj[1], True)
-            self.cp2 = ConvBNLayer(fus.camera_proj[3], fus.camera_proj[4], True)
-            t1, _, _ = self.cp1.forward(proj, B, Sh, Sw)
-            t2, _, _ = self.cp2.forward(t1, B, Sh, Sw)
-            self._slot(concat, slot)[:] = t2[:B * P * bc].view(B * P, bc)
-            self.cam_slot = slot
-            slot += 1
-        elif self.has_cam:
-            _, ncam, Hc, Wc = cam_geom
-            Cc = fus.camera_proj[0].weight.shape[1]
-            self.cam_pool_geom = (B, ncam, Hc * Wc, Cc)
-            pooled = cam_feat
-            if ncam > 1:
-                pooled = _new(B * Hc * Wc * Cc, dev)
-                L.cam_mean(cam_feat, pooled, B, ncam, Hc * Wc, Cc)
-            self.cp1 = ConvBNLayer(fus.camera_proj[0], fus.camera_proj[1], True)
-            self.cp2 = ConvBNLayer(fus.camera_proj[3], fus.camera_proj[4], True)
-            t1, _, _ = self.cp1.forward(pooled, B, Hc, Wc)
-            t2, _, _ = self.cp2.forward(t1, B, Hc, Wc)
-            self.cam_resize = Bilinear()
-            self.cam_resize.forward(t2, B, Hc, Wc, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
-            self.cam_slot = slot
-            slot += 1
-        self.lid_pillars = self.has_lid and fus.lidar_kind == "pillars"
-        if self.lid_pillars:
-            # PointPillars: the NHWC canvas is on the fusion grid already -- lidar_bev's two conv+BN+ReLU, then the slice copy
-            self.lb1 = ConvBNLayer(fus.lidar_bev[0], fus.lidar_bev[1], True)
-            self.lb2 = ConvBNLayer(fus.lidar_bev[3], fus.lidar_bev[4], True)
-            t1, _, _ = self.lb1.forward(lid_feat, B, Sh, Sw)
-            t2, _, _ = self.lb2.forward(t1, B, Sh, Sw)
-            self._slot(concat, slot)[:] = t2[:B * P * bc].view(B * P, bc)
-            self.lid_slot = slot
-            slot += 1
-        elif self.has_lid:
-            s0 = fus.lidar_start_size
-            self.li0 = LinearLayer(fus.lidar_init[0], True)
-            O = fus.lidar_init[2].weight.shape[0]
-            self.li2 = LinearLayer(fus.lidar_init[2], False, (s0 * s0, O // (s0 * s0)))
-            hid = self.li0.forward(lid_feat, B)
-            grid0 = self.li2.forward(hid, B)
-            self.lu1 = ConvBNLayer(fus.lidar_upsample[0], fus.lidar_upsample[1], True)
-            self.lu2 = ConvBNLayer(fus.lidar_upsample[4], fus.lidar_upsample[5], True)
-            g1, _, _ = self.lu1.forward(grid0, B, s0, s0)
-            self.lid_up = Bilinear()
-            s1 = 2 * s0
-            g2 = self.lid_up.forward(g1, B, s0, s0, self.lu1.cout, s1, s1)
-            g3, _, _ = self.lu2.forward(g2, B, s1, s1)
-            self.lid_resize = Bilinear()                                   # (the identity map when s1 == Sh == Sw)
-            self.lid_resize.forward(g3, B, s1, s1, bc, Sh, Sw, y=concat[slot * bc:], y_cs=ccs)
-            self.lid_slot = slot
-            slot += 1
-        if self.has_rad:
-            self.rp = LinearLayer(fus.radar_proj[0], True)
-            rv = self.rp.forward(rad_feat, B)
-            r0 = _new(B * P * bc, dev)
-            L.broadcast_nhwc(rv, r0, B, P, bc, bc)
-            self.rr1 = ConvBNLayer(fus.radar_refine[0], fus.radar_refine[1], True)
-            self.rr2 = ConvBNLayer(fus.radar_refine[3], fus.radar_refine[4], True)
-            r1, _, _ = self.rr1.forward(r0, B, Sh, Sw)
-            r2, _, _ = self.rr2.forward(r1, B, Sh, Sw)
-            self._slot(concat, slot)[:] = r2[:B * P * bc].view(B * P, bc)
-            self.rad_slot = slot
-            slot += 1
+        feats = (cam_feat, lid_feat, rad_feat)
+        present, ccs, B = E.concat_slots(fus, self.branches, feats,
+                                         "expected input to have {cin} channels, but got {ccs} channels instead", B)
+        concat = _new(B * self.H * self.W * ccs, present[0][1].device)
+        names = {tape: name for tape, name in zip(self.branches, ("camera", "lidar", "radar")) if tape is not None}
+        self.present = [(names[tape], tape) for tape, _ in present]
+        for slot, (tape, x) in enumerate(present):
+            tape.forward(x, B, concat, ccs, slot, cam_geom, camera_calib)
         self.f1 = ConvBNLayer(fus.bev_fusion[0], fus.bev_fusion[1], True)
         self.f2 = ConvBNLayer(fus.bev_fusion[3], fus.bev_fusion[4], True)          # (the producer of the head's input)
-        a1, _, _ = self.f1.forward(concat, B, Sh, Sw)
-        fused, _, _ = self.f2.forward(a1, B, Sh, Sw)
+        a1, _, _ = self.f1.forward(concat, B, self.H, self.W)
+        fused, _, _ = self.f2.forward(a1, B, self.H, self.W)
         return fused
 
     def backward(self, dfused, sink: GradSink, pre=None, on_radar=None, on_lidar=None, on_camera=None):
         """pre: BatchNorm-backward partials for f2 that arrive with dfused (or None).  Each modality's input gradient (radar (B*C_r),
         LiDAR (B*C_l) or the pillar canvas, camera NHWC) goes to its callback as soon as it exists -- the detector continues into
         that encoder there -- and is returned as well: (drad, dlid, dcam)."""
-        B, P, bc = self.B, self.H * self.W, self.cout
-        drad = dlid = dcam = None
         da1, _, pre_f1 = self.f2.backward(dfused, sink, fuse_next=self.f1, pre=pre)
         dconcat, _ = self.f1.backward(da1, sink, pre=pre_f1)
-        if self.has_rad:
-            dr1, _ = self.rr2.backward(self._slot(dconcat, self.rad_slot).contiguous().view(-1), sink)
-            dr0, _ = self.rr1.backward(dr1, sink)
-            drv = torch.cat([colsum(dr0[b * P * bc:], P, bc) for b in range(B)])      # d(broadcast) = sum over cells
-            drad = self.rp.backward(drv.contiguous(), sink)
-            if on_radar is not None:
-                on_radar(drad)
-        if self.lid_pillars:
-            dt1, _ = self.lb2.backward(self._slot(dconcat, self.lid_slot).contiguous().view(-1), sink)
-            dlid, _ = self.lb1.backward(dt1, sink)
-        elif self.has_lid:
-            dg2, _ = self.lu2.backward(self.lid_resize.backward(dconcat[self.lid_slot * bc:]), sink)
-            dgrid0, _ = self.lu1.backward(self.lid_up.backward(dg2), sink)
-            dlid = self.li0.backward(self.li2.backward(dgrid0, sink), sink)
-        if dlid is not None and on_lidar is not None:
-            on_lidar(dlid)
-        if self.cam_project:
-            dt1, _ = self.cp2.backward(self._slot(dconcat, self.cam_slot).contiguous().view(-1), sink)
-            dproj, _ = self.cp1.backward(dt1, sink)
-            Bc, ncam, Pc, Cc = self.cam_pool_geom
-            dcam = _new(Bc * ncam * Pc * Cc, dfused.device)
-            if self.frame_calib is not None and self.cam_table.version != self.frame_calib[1]:
-                self.cam_table = E.frame_camera_tables(self.fus, self.frame_calib[0], Bc, *self.frame_calib[2], dfused.device)
-                self.frame_calib = (self.frame_calib[0], self.cam_table.version, self.frame_calib[2])
-            self.cam_table.project_backward(dproj, dcam, Bc, Cc)                # transposed table: every element written once
-            if on_camera is not None:
-                on_camera(dcam)
-        elif self.has_cam:
-            dt1, _ = self.cp2.backward(self.cam_resize.backward(dconcat[self.cam_slot * bc:]), sink)
-            dcam, _ = self.cp1.backward(dt1, sink)
-            Bc, ncam, Pc, Cc = self.cam_pool_geom
-            if ncam > 1:
-                dpooled, dcam = dcam, _new(Bc * ncam * Pc * Cc, dfused.device)
-                L.cam_mean_bwd(dpooled, dcam, Bc, ncam, Pc, Cc)
-            if on_camera is not None:
-                on_camera(dcam)
-        return drad, dlid, dcam
+        hooks, grads = dict(camera=on_camera, lidar=on_lidar, radar=on_radar), dict(camera=None, lidar=None, radar=None)
+        for name, tape in reversed(self.present):
+            grads[name] = tape.backward(dconcat, sink)
+            if hooks[name] is not None:
+                hooks[name](grads[name])
+        return grads["radar"], grads["lidar"], grads["camera"]
 
 
 class HeadTape:

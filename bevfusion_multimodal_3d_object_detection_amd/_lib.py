@@ -139,6 +139,15 @@ SIGNATURES = {
     "bevf_resize_normalize_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 +
                                  [C.c_int] + [C.POINTER(C.c_float)] * 2 + [C.c_void_p]),
     "bevf_lidar_filter_pad_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.POINTER(C.c_float), C.c_void_p]),
+    # ---- training augmentation ----
+    "bevf_resample_tables_box_f64": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 5),
+    "bevf_resize_crop_u8": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
+                            [C.c_void_p]),
+    "bevf_jitter_flip_normalize_u8": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.POINTER(C.c_float)] * 2 + [C.c_void_p]),
+    "bevf_points_affine_work_floats": (C.c_size_t, [C.c_int] * 3),
+    "bevf_points_affine_filter_pad_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.POINTER(C.c_float), C.c_void_p]),
+    "bevf_points_affine_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_int] * 5 + [C.c_void_p]),
+    "bevf_boxes_affine_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
     # ---- bf16 storage path ----
     "bevf_split_weights_f32x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bevf_conv2d_nhwc_f32x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -1142,6 +1151,72 @@ def lidar_filter_pad(points, out, count, work, choice, N: int, Cc: int, max_poin
           work=(work, N * Cc + -(-N // 1024)), choice=(choice, max_points))
     _call("bevf_lidar_filter_pad_f32", _pc(points), _pc(out), _pc(count, torch.int32), _pc(work), _pc(choice, torch.int64), N, Cc,
           max_points, (C.c_float * 6)(*pc_range))
+
+
+# ---- training augmentation (csrc/augment.hip) ---------------------------------------------------------------------
+
+def resample_tables_box(windows, n: int, H: int, W: int, Ho: int, Wo: int, ksize_h: int, ksize_v: int, bounds_h, coef_h, bounds_v,
+                        coef_v) -> None:
+    """Pillow's coefficient tables for the integer windows [n][4] = (x0, x1, y0, y1), on the device (bevf_resample_tables_box_f64):
+    bounds_h [n][Wo][2], coef_h [n][Wo][ksize_h], bounds_v [n][Ho][2], coef_v [n][Ho][ksize_v], all int32."""
+    _need("resample_tables_box", windows=(windows, n * 4), bounds_h=(bounds_h, n * Wo * 2), coef_h=(coef_h, n * Wo * ksize_h),
+          bounds_v=(bounds_v, n * Ho * 2), coef_v=(coef_v, n * Ho * ksize_v))
+    i32 = torch.int32
+    _call("bevf_resample_tables_box_f64", _pc(windows, i32), n, H, W, Ho, Wo, ksize_h, ksize_v, _pc(bounds_h, i32), _pc(coef_h, i32),
+          _pc(bounds_v, i32), _pc(coef_v, i32))
+
+
+def resize_crop_u8(x, out, gray_sum, n: int, H: int, W: int, Ho: int, Wo: int, bounds_h, coef_h, ksize_h: int, bounds_v, coef_v,
+                   ksize_v: int) -> None:
+    """uint8 [n][H][W][3] -> uint8 [n][Ho][Wo][3] through the per-image tables of resample_tables_box (Pillow-identical), and
+    gray_sum [n] int64 = the sum of Pillow's gray value over each output image."""
+    _need("resize_crop_u8", x=(x, n * H * W * 3), out=(out, n * Ho * Wo * 3), gray_sum=(gray_sum, n), bounds_h=(bounds_h, n * Wo * 2),
+          coef_h=(coef_h, n * Wo * ksize_h), bounds_v=(bounds_v, n * Ho * 2), coef_v=(coef_v, n * Ho * ksize_v))
+    i32 = torch.int32
+    _call("bevf_resize_crop_u8", _pc(x, torch.uint8), _pc(out, torch.uint8), _pc(gray_sum, torch.int64), n, H, W, Ho, Wo,
+          _pc(bounds_h, i32), _pc(coef_h, i32), ksize_h, _pc(bounds_v, i32), _pc(coef_v, i32), ksize_v)
+
+
+def jitter_flip_normalize_u8(x, out, gray_sum, jitter, flip, n: int, Ho: int, Wo: int, mean: Sequence[float],
+                             std: Sequence[float]) -> None:
+    """uint8 [n][Ho][Wo][3] -> planar fp32 [n][3][Ho][Wo]: per-image jitter [n][4] = (contrast, brightness, saturation, hue shift),
+    flip [n] int32, then (x - mean) / std (bevf_jitter_flip_normalize_u8)."""
+    _need("jitter_flip_normalize_u8", x=(x, n * Ho * Wo * 3), out=(out, n * 3 * Ho * Wo), gray_sum=(gray_sum, n), jitter=(jitter, n * 4),
+          flip=(flip, n))
+    _call("bevf_jitter_flip_normalize_u8", _pc(x, torch.uint8), _pc(out), _pc(gray_sum, torch.int64), _pc(jitter), _pc(flip, torch.int32),
+          n, Ho, Wo, (C.c_float * 3)(*mean), (C.c_float * 3)(*std))
+
+
+def points_affine_work_floats(B: int, N: int, Cc: int) -> int:
+    return int(lib().bevf_points_affine_work_floats(B, N, Cc))
+
+
+def _vel_ch(vel_ch) -> Sequence[int]:
+    return (-1, -1) if vel_ch is None else (int(vel_ch[0]), int(vel_ch[1]))
+
+
+def points_affine_filter_pad(points, n_in, mat, out, count, work, B: int, N: int, Cc: int, max_points: int, vel_ch,
+                             pc_range: Sequence[float]) -> None:
+    """points [B][N][C] (n_in [B] int32 valid rows, or None) through mat [B][12], range filter, compaction, zero padding: out
+    [B][max_points][C], count [B] int32 (bevf_points_affine_filter_pad_f32); vel_ch: None or the two velocity channels."""
+    _need("points_affine_filter_pad", points=(points, B * N * Cc), n_in=(n_in, B), mat=(mat, B * 12), out=(out, B * max_points * Cc),
+          count=(count, B), work=(work, points_affine_work_floats(B, N, Cc)))
+    _call("bevf_points_affine_filter_pad_f32", _pc(points), _pc(n_in, torch.int32), _pc(mat), _pc(out), _pc(count, torch.int32),
+          _pc(work), B, N, Cc, max_points, *_vel_ch(vel_ch), (C.c_float * 6)(*pc_range))
+
+
+def points_affine(points, mat, noise, noise_std: float, B: int, N: int, Cc: int, vel_ch) -> None:
+    """points [B][N][C] through mat [B][12] in place; noise [B][N][3] (or None) times noise_std onto channels 0-2."""
+    _need("points_affine", points=(points, B * N * Cc), mat=(mat, B * 12), noise=(noise, B * N * 3))
+    _call("bevf_points_affine_f32", _pc(points), _pc(mat), _pc(noise), float(noise_std), B, N, Cc, *_vel_ch(vel_ch))
+
+
+def boxes_affine(boxes, labels, velocities, mat, scale, B: int, M: int, ncol: int) -> None:
+    """boxes [B][M][ncol] / velocities [B][M][2] (or None) through mat [B][12] in place; labels [B][M] int64 < 0 mark padding rows,
+    scale [B] the transform's isotropic scale (bevf_boxes_affine_f32)."""
+    _need("boxes_affine", boxes=(boxes, B * M * ncol), labels=(labels, B * M), velocities=(velocities, B * M * 2), mat=(mat, B * 12),
+          scale=(scale, B))
+    _call("bevf_boxes_affine_f32", _pc(boxes), _pc(labels, torch.int64), _pc(velocities), _pc(mat), _pc(scale), B, M, ncol)
 
 
 def csr_gather(row_ptr, col, w, nrows: int, ncols: int, x, x_bs: int, x_cs: int, y, y_bs: int, y_cs: int, B: int, C: int) -> None:

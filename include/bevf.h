@@ -663,6 +663,47 @@ int bevf_resize_normalize_u8(const unsigned char* x, float* out, int n, int H, i
 int bevf_lidar_filter_pad_f32(const float* points, float* out, int32_t* count, float* work, const int64_t* choice,
                               int N, int C, int max_points, const float* pc_range6, void* stream);
 
+/* ==========================================================================================
+ * Training augmentation (the `dataset.augmentation` section of the reference's YAML, ref configs/base.yaml:85-114,
+ * which the reference's drivers never read).  One world transform per frame, one image transform per (frame, camera).
+ * ========================================================================================== */
+
+/* Pillow's bilinear coefficient tables for an integer crop window per image: windows [n][4] = (x0, x1, y0, y1) in source pixels;
+ * bounds_h [n][Wo][2], coef_h [n][Wo][ksize_h], bounds_v [n][Ho][2], coef_v [n][Ho][ksize_v]; ksize_* = the table stride, at least
+ * 2 * ceil(max(1, window / out)) + 1 of the largest window.  Same fp64 operations in the same order as augment.resample_tables_box
+ * (no fused multiply-add): bit-equal to the host restatement; unused weights are 0.                                            */
+int bevf_resample_tables_box_f64(const int32_t* windows, int n, int H, int W, int Ho, int Wo, int ksize_h, int ksize_v,
+                                 int32_t* bounds_h, int32_t* coef_h, int32_t* bounds_v, int32_t* coef_v, void* stream);
+/* bevf_resize_normalize_u8's two integer passes with the per-image tables above: x [n][H][W][3] -> out [n][Ho][Wo][3] uint8
+ * (= PIL Image.resize((Wo, Ho), BILINEAR, box=window)), gray_sum [n] = sum over the output pixels of Pillow's
+ * L = (19595 R + 38470 G + 7471 B + 32768) >> 16 (zeroed here, integer atomics).                                          */
+int bevf_resize_crop_u8(const unsigned char* x, unsigned char* out, uint64_t* gray_sum, int n, int H, int W, int Ho, int Wo,
+                        const int32_t* bounds_h, const int32_t* coef_h, int ksize_h, const int32_t* bounds_v,
+                        const int32_t* coef_v, int ksize_v, void* stream);
+/* x [n][Ho][Wo][3] uint8 -> out planar fp32 [n][3][Ho][Wo]: u8 / 255, then per image jitter4 [n][4] = (contrast f_c, brightness f_b,
+ * saturation f_s, hue shift) in this order -- clamp(f_c x + (1 - f_c) m) with m = gray_sum / (Ho Wo) / 255, clamp(f_b x), the blend
+ * with 0.299 r + 0.587 g + 0.114 b, RGB -> HSV -> (h + shift) mod 1 -> RGB (torchvision's float formulas); a factor of 1 / a shift
+ * of 0 skips its step.  flip [n] != 0 stores column Wo - 1 - x.  Last (x - mean) / std as bevf_resize_normalize_u8 does it.     */
+int bevf_jitter_flip_normalize_u8(const unsigned char* x, float* out, const uint64_t* gray_sum, const float* jitter4,
+                                  const int32_t* flip, int n, int Ho, int Wo, const float* mean3, const float* std3, void* stream);
+/* B frames of points [B][N][C] (n_in [B] valid rows each, NULL = N): p' = M p + t with mat12 [B][12] (row-major 3 x 4; x' =
+ * fmaf(m2, z, fmaf(m1, y, fmaf(m0, x, m3))), rows 1 and 2 alike), channels (vel_c0, vel_c1) -- both < 0 for none -- multiplied by
+ * the upper-left 2 x 2; then bevf_lidar_filter_pad_f32's strict range filter, order-preserving compaction and zero padding: out
+ * [B][max_points][C] = the first max_points survivors, count [B] = all survivors.  An exactly-identity frame is copied bit for bit.
+ * work: bevf_points_affine_work_floats(B, N, C) floats.                                                                       */
+size_t bevf_points_affine_work_floats(int B, int N, int C);
+int bevf_points_affine_filter_pad_f32(const float* points, const int32_t* n_in, const float* mat12, float* out, int32_t* count,
+                                      float* work, int B, int N, int C, int max_points, int vel_c0, int vel_c1,
+                                      const float* pc_range6, void* stream);
+/* The same transform in place without the filter (radar): noise [B][N][3] or NULL is added to channels 0-2 times noise_std. */
+int bevf_points_affine_f32(float* points, const float* mat12, const float* noise, float noise_std, int B, int N, int C,
+                           int vel_c0, int vel_c1, void* stream);
+/* Ground-truth boxes in place: boxes [B][M][ncol] (7, or 9 with velocity in columns 7-8), labels [B][M] (< 0: padding row, left
+ * untouched), velocities [B][M][2] or NULL, scale [B] = the transform's isotropic scale.  Centre through the affine map, w l h
+ * times scale, yaw' = atan2 of the transformed heading (cos yaw, sin yaw), velocities times the upper-left 2 x 2.            */
+int bevf_boxes_affine_f32(float* boxes, const int64_t* labels, float* velocities, const float* mat12, const float* scale, int B,
+                          int M, int ncol, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

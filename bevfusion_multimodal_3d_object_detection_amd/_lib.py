@@ -221,6 +221,14 @@ SIGNATURES = {
                                              C.c_size_t, C.c_int, C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_csr_gather_frames_bf16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                               C.c_size_t, C.c_int, C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_softmax_rows_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p]),
+    "bevf_softmax_rows_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int,
+                                            C.c_void_p]),
+    "bevf_csr_lift_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_csr_lift_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+                              + [C.c_int] * 2 + [C.c_void_p]),
 }
 
 
@@ -1288,3 +1296,66 @@ def csr_gather_frames(row_ptr, col, w, cap: int, nrows: int, ncols: int, x, x_bs
         raise BevfError("csr_gather_frames: x and y share storage")
     _call("bevf_csr_gather_frames_" + _sfx(x), _pc(row_ptr, torch.int32), nrows + 1, _pc(col, torch.int32), _pc(w), cap, nrows,
           _p(x, x.dtype), x_bs, x_cs, _p(y, y.dtype), y_bs, y_cs, B, C)
+
+
+def _depth_bins(what: str, D: int) -> None:
+    if not 1 <= D <= 64:
+        raise BevfError(f"{what}: {D} depth bins, the kernels hold one bin per lane (1 <= D <= 64)")
+
+
+def softmax_rows(x, x_rs: int, y, y_rs: int, nrows: int, D: int) -> None:
+    """y[r][0:D] (row stride y_rs) = softmax(x[r][0:D]) (row stride x_rs), fp32 (bevf_softmax_rows_f32): the depth distribution."""
+    _depth_bins("softmax_rows", D)
+    _need("softmax_rows", x=(x, _strided(nrows, D, x_rs)), y=(y, _strided(nrows, D, y_rs)))
+    _call("bevf_softmax_rows_f32", _p(x), x_rs, _p(y), y_rs, nrows, D)
+
+
+def softmax_rows_bwd(pd, dpd, p_rs: int, dx, x_rs: int, x_cols: int, nrows: int, D: int) -> None:
+    """dx[r][d] = pd (dpd - sum_d pd dpd) for d < D, 0 for D <= d < x_cols (bevf_softmax_rows_bwd_f32)."""
+    _depth_bins("softmax_rows_bwd", D)
+    if not D <= x_cols <= 64:
+        raise BevfError(f"softmax_rows_bwd: {x_cols} output columns for {D} bins (D <= x_cols <= 64)")
+    _need("softmax_rows_bwd", pd=(pd, _strided(nrows, D, p_rs)), dpd=(dpd, _strided(nrows, D, p_rs)),
+          dx=(dx, _strided(nrows, x_cols, x_rs)))
+    _call("bevf_softmax_rows_bwd_f32", _p(pd), _p(dpd), p_rs, _p(dx), x_rs, x_cols, nrows, D)
+
+
+def csr_lift(row_ptr, col2, w, nrows: int, ncols: int, D: int, x, x_bs: int, x_cs: int, pd, pd_bs: int, y, y_bs: int, y_cs: int,
+             B: int, C: int) -> None:
+    """y[b][r][0:C] = sum_e w[e] * pd[b][col2[e]] * x[b][col2[e] // D][0:C] over CSR row r (bevf_csr_lift_f32): the learned-depth
+    camera -> BEV lift.  col2 = pixel * D + bin < ncols * D (checked when the table is built); pd [b] at pd_bs holds [ncols][D]."""
+    _depth_bins("csr_lift", D)
+    if row_ptr.numel() != nrows + 1:
+        raise BevfError(f"csr_lift: row_ptr holds {row_ptr.numel()} elements, needs nrows + 1 = {nrows + 1}")
+    nnz = col2.numel()
+    if w.numel() != nnz:
+        raise BevfError(f"csr_lift: {nnz} columns but {w.numel()} weights")
+    if ncols * D >= 2 ** 31:
+        raise BevfError("csr_lift: pixel * D + bin does not fit int32")
+    _need("csr_lift", x=(x, (B - 1) * x_bs + _strided(ncols, C, x_cs)), pd=(pd, (B - 1) * pd_bs + ncols * D),
+          y=(y, (B - 1) * y_bs + _strided(nrows, C, y_cs)))
+    if x.is_cuda and y.is_cuda and x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("csr_lift: x and y share storage")
+    _call("bevf_csr_lift_f32", _pc(row_ptr, torch.int32), _pc(col2, torch.int32) if nnz else None, _pc(w) if nnz else None, nrows, D,
+          _p(x), x_bs, x_cs, _p(pd), pd_bs, _p(y), y_bs, y_cs, B, C)
+
+
+def csr_lift_bwd(t_row_ptr, t_cell, t_bin, t_w, npix: int, P: int, D: int, x, x_bs: int, x_cs: int, pd, pd_bs: int, dy, dy_bs: int,
+                 dy_cs: int, dx, dx_bs: int, dx_cs: int, dpd, dpd_bs: int, B: int, C: int) -> None:
+    """The lift's backward on the transposed table (bevf_csr_lift_bwd_f32): dx [b][pix][0:C] and dpd [b][pix][0:D], every element
+    written once.  t_cell < P and t_bin < D by construction of the table."""
+    _depth_bins("csr_lift_bwd", D)
+    if t_row_ptr.numel() != npix + 1:
+        raise BevfError(f"csr_lift_bwd: t_row_ptr holds {t_row_ptr.numel()} elements, needs npix + 1 = {npix + 1}")
+    nnz = t_cell.numel()
+    if t_bin.numel() != nnz or t_w.numel() != nnz:
+        raise BevfError(f"csr_lift_bwd: {nnz} cells but {t_bin.numel()} bins and {t_w.numel()} weights")
+    _need("csr_lift_bwd", x=(x, (B - 1) * x_bs + _strided(npix, C, x_cs)), pd=(pd, (B - 1) * pd_bs + npix * D),
+          dy=(dy, (B - 1) * dy_bs + _strided(P, C, dy_cs)), dx=(dx, (B - 1) * dx_bs + _strided(npix, C, dx_cs)),
+          dpd=(dpd, (B - 1) * dpd_bs + npix * D))
+    for name, t in (("x", x), ("dy", dy)):
+        if t.is_cuda and dx.is_cuda and t.untyped_storage().data_ptr() == dx.untyped_storage().data_ptr():
+            raise BevfError(f"csr_lift_bwd: {name} and dx share storage")
+    _call("bevf_csr_lift_bwd_f32", _pc(t_row_ptr, torch.int32), _pc(t_cell, torch.int32) if nnz else None,
+          _pc(t_bin, torch.int32) if nnz else None, _pc(t_w) if nnz else None, npix, D, _p(x), x_bs, x_cs, _p(pd), pd_bs, _p(dy),
+          dy_bs, dy_cs, _p(dx), dx_bs, dx_cs, _p(dpd), dpd_bs, B, C)

@@ -21,9 +21,11 @@ import numpy as np
 
 # the reference's camera order (ref src/train_detect.py:134-135): the order of the camera axis of the image input
 CAM_ORDER = ("CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_FRONT_LEFT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_BACK_RIGHT")
-VIEW_TRANSFORMS = ("mean", "project")
+VIEW_TRANSFORMS = ("mean", "project", "lift")
 DEFAULT_NUM_HEIGHTS = 8
 DEFAULT_MIN_DEPTH = 0.1
+DEFAULT_DEPTH_BINS, DEFAULT_DEPTH_MIN, DEFAULT_DEPTH_MAX = 32, 1.0, 65.0      # the 'lift' branch's uniform depth bins (metres)
+MAX_DEPTH_BINS = 64                                                           # one bin per lane in the lift's backward kernel
 
 
 def quat_to_matrix(q: Sequence[float]) -> np.ndarray:
@@ -184,7 +186,7 @@ def jittered_rig(seed: int, rig: Optional[CameraRig] = None) -> CameraRig:
 
 
 def view_transform_kind(camera_view_transform: Optional[str] = None, config: Optional[Dict] = None) -> str:
-    """'project' or 'mean' from the keyword, else `model.bev_fusion.camera_view_transform` of the config, else 'mean'
+    """'lift', 'project' or 'mean' from the keyword, else `model.bev_fusion.camera_view_transform` of the config, else 'mean'
     (any letter case); anything else raises."""
     t = camera_view_transform
     if t is None and config is not None:
@@ -193,7 +195,7 @@ def view_transform_kind(camera_view_transform: Optional[str] = None, config: Opt
         return "mean"
     k = str(t).strip().lower()
     if k not in VIEW_TRANSFORMS:
-        raise ValueError(f"camera_view_transform must be 'mean' or 'project', got {t!r}")
+        raise ValueError(f"camera_view_transform must be 'mean', 'project' or 'lift', got {t!r}")
     return k
 
 
@@ -207,6 +209,25 @@ def camera_bev_settings(config: Optional[Dict] = None) -> Tuple[int, float, Came
         raise ValueError(f"camera_bev: num_heights must be > 0 and min_depth > 0, got {nh}, {md}")
     rig = CameraRig.from_dict(cb["rig"]) if cb.get("rig") else default_rig()
     return nh, md, rig
+
+
+def check_depth_settings(bins, depth_min, depth_max, min_depth: float = DEFAULT_MIN_DEPTH) -> Tuple[int, float, float]:
+    """(D, depth_min, depth_max) of the 'lift' branch's uniform bins, checked: D an integer in 1..64, 0 < min_depth <= depth_min <
+    depth_max; ValueError otherwise."""
+    if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= MAX_DEPTH_BINS:
+        raise ValueError(f"camera_bev.depth: bins must be an integer in 1..{MAX_DEPTH_BINS}, got {bins!r}")
+    lo, hi, md = float(depth_min), float(depth_max), float(min_depth)
+    if not (0.0 < md <= lo < hi) or not math.isfinite(hi):
+        raise ValueError(f"camera_bev.depth: need 0 < min_depth <= min < max, got min_depth {md}, min {lo}, max {hi}")
+    return int(bins), lo, hi
+
+
+def camera_lift_settings(config: Optional[Dict] = None, min_depth: float = DEFAULT_MIN_DEPTH) -> Tuple[int, float, float]:
+    """(bins, min, max) from `model.bev_fusion.camera_bev.depth` ({bins: 32, min: 1.0, max: 65.0}), checked against min_depth."""
+    cb = ((config or {}).get("model", {}).get("bev_fusion", {}) or {}).get("camera_bev", {}) or {}
+    d = cb.get("depth", {}) or {}
+    return check_depth_settings(d.get("bins", DEFAULT_DEPTH_BINS), d.get("min", DEFAULT_DEPTH_MIN), d.get("max", DEFAULT_DEPTH_MAX),
+                                min_depth)
 
 
 # ---- the projection table ----------------------------------------------------------------------------------------------------------
@@ -246,17 +267,11 @@ def height_centres(pc_range, num_heights: int) -> np.ndarray:
     return z0 + (np.arange(num_heights, dtype=np.float64) + 0.5) * (z1 - z0) / num_heights
 
 
-def build_projection_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int,
-                           num_heights: int = DEFAULT_NUM_HEIGHTS, min_depth: float = DEFAULT_MIN_DEPTH) -> ProjectionTable:
-    """The lift of rig's cameras (feature maps Hc x Wc each) onto the bev_h x bev_w grid of pc_range, in fp64:
-
-    sample (cell, height k, camera c) at p = (x_j, y_i, z_k): q = cam_to_bev[c]^-1 p; valid when q_z > min_depth and the pixel
-    (u, v) = (K q / q_z)[:2] lies in [0, W) x [0, H) of rig.image_size; its value is the bilinear sample of the feature map at
-    u_f = (u + 1/2) Wc / W - 1/2, v_f = (v + 1/2) Hc / H - 1/2 with taps outside the map reading zero (= F.grid_sample,
-    align_corners=False, padding_mode='zeros', at gx = (2u + 1) / W - 1).  Cell value = mean over its valid samples, 0 without one.
-    Duplicate (cell, pixel) entries are merged in fp64 before rounding to fp32; exact-zero weights are dropped."""
+def _camera_samples(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int, num_heights: int, min_depth: float):
+    """The shared fp64 sample geometry of build_projection_table and build_lift_table: per camera c, for its (cell, height) samples
+    in front of it (depth > min_depth) whose pixel lies inside the image, yields (c, cell index, depth q_z, u_f, v_f) with
+    (u_f, v_f) the feature-map coordinates; samples in (cell, height) order."""
     H, W = rig.image_size
-    ncam = rig.num_cameras
     xs, ys = cell_centres(pc_range, bev_h, bev_w)
     zs = height_centres(pc_range, num_heights)
     P = bev_h * bev_w
@@ -268,9 +283,7 @@ def build_projection_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: in
     pts[..., 3] = 1.0
     pts = pts.reshape(-1, 4)                                                      # sample s = cell * num_heights + k
     cell_of = np.repeat(np.arange(P, dtype=np.int64), num_heights)
-    rows, cols, wts = [], [], []
-    count = np.zeros(P, dtype=np.int64)
-    for c in range(ncam):
+    for c in range(rig.num_cameras):
         q = pts @ np.linalg.inv(rig.cam_to_bev[c]).T
         depth = q[:, 2]
         front = depth > min_depth
@@ -278,22 +291,41 @@ def build_projection_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: in
         u = uvw[:, 0] / uvw[:, 2]
         v = uvw[:, 1] / uvw[:, 2]
         inside = (u >= 0) & (u < W) & (v >= 0) & (v < H)
-        cells = cell_of[front][inside]
         u, v = u[inside], v[inside]
+        yield c, cell_of[front][inside], depth[front][inside], (u + 0.5) * Wc / W - 0.5, (v + 0.5) * Hc / H - 0.5
+
+
+def _bilinear_taps(uf: np.ndarray, vf: np.ndarray, Hc: int, Wc: int):
+    """The four bilinear taps of the samples at (uf, vf): yields (inside-the-map mask, pixel index y * Wc + x, weight) per tap."""
+    x0 = np.floor(uf)
+    y0 = np.floor(vf)
+    lx, ly = uf - x0, vf - y0
+    x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
+    for dy, wy in ((0, 1.0 - ly), (1, ly)):
+        for dx, wx in ((0, 1.0 - lx), (1, lx)):
+            xi, yi = x0 + dx, y0 + dy
+            yield (xi >= 0) & (xi < Wc) & (yi >= 0) & (yi < Hc), yi * Wc + xi, wx * wy
+
+
+def build_projection_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int,
+                           num_heights: int = DEFAULT_NUM_HEIGHTS, min_depth: float = DEFAULT_MIN_DEPTH) -> ProjectionTable:
+    """The lift of rig's cameras (feature maps Hc x Wc each) onto the bev_h x bev_w grid of pc_range, in fp64:
+
+    sample (cell, height k, camera c) at p = (x_j, y_i, z_k): q = cam_to_bev[c]^-1 p; valid when q_z > min_depth and the pixel
+    (u, v) = (K q / q_z)[:2] lies in [0, W) x [0, H) of rig.image_size; its value is the bilinear sample of the feature map at
+    u_f = (u + 1/2) Wc / W - 1/2, v_f = (v + 1/2) Hc / H - 1/2 with taps outside the map reading zero (= F.grid_sample,
+    align_corners=False, padding_mode='zeros', at gx = (2u + 1) / W - 1).  Cell value = mean over its valid samples, 0 without one.
+    Duplicate (cell, pixel) entries are merged in fp64 before rounding to fp32; exact-zero weights are dropped."""
+    P = bev_h * bev_w
+    ncam = rig.num_cameras
+    rows, cols, wts = [], [], []
+    count = np.zeros(P, dtype=np.int64)
+    for c, cells, _, uf, vf in _camera_samples(rig, Hc, Wc, pc_range, bev_h, bev_w, num_heights, min_depth):
         np.add.at(count, cells, 1)
-        uf = (u + 0.5) * Wc / W - 0.5
-        vf = (v + 0.5) * Hc / H - 0.5
-        x0 = np.floor(uf)
-        y0 = np.floor(vf)
-        lx, ly = uf - x0, vf - y0
-        x0, y0 = x0.astype(np.int64), y0.astype(np.int64)
-        for dy, wy in ((0, 1.0 - ly), (1, ly)):
-            for dx, wx in ((0, 1.0 - lx), (1, lx)):
-                xi, yi = x0 + dx, y0 + dy
-                ok = (xi >= 0) & (xi < Wc) & (yi >= 0) & (yi < Hc)
-                rows.append(cells[ok])
-                cols.append(c * Hc * Wc + yi[ok] * Wc + xi[ok])
-                wts.append((wx * wy)[ok])
+        for ok, pix, wt in _bilinear_taps(uf, vf, Hc, Wc):
+            rows.append(cells[ok])
+            cols.append(c * Hc * Wc + pix[ok])
+            wts.append(wt[ok])
     ncols = ncam * Hc * Wc
     r = np.concatenate(rows) if rows else np.zeros(0, np.int64)
     cl = np.concatenate(cols) if cols else np.zeros(0, np.int64)
@@ -325,4 +357,93 @@ def apply_table_fp64(t: ProjectionTable, feats: np.ndarray) -> np.ndarray:
     w = t.w64
     for b in range(B):
         np.add.at(out[b], rows, feats[b][t.col] * w[:, None])
+    return out
+
+
+# ---- the lift table (learned depth) ---------------------------------------------------------------------------------------------
+
+@dataclass
+class LiftTable:
+    """The projection table with a depth bin per entry (camera_view_transform 'lift'): CSR by cell, sorted by (cell, pixel, bin),
+    col2 int32 = pixel * D + bin, w fp32; and its exact transpose as CSR by pixel (t_row_ptr [ncols + 1]), sorted by (pixel, cell,
+    bin): t_cell, t_bin int32, t_w the bit-identical fp32 weight.  w64: the merged fp64 weights before rounding (host checks)."""
+    P: int
+    ncols: int
+    D: int
+    row_ptr: np.ndarray
+    col2: np.ndarray
+    w: np.ndarray
+    t_row_ptr: np.ndarray
+    t_cell: np.ndarray
+    t_bin: np.ndarray
+    t_w: np.ndarray
+    w64: np.ndarray
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col2.shape[0])
+
+
+def depth_bin_of(depth: np.ndarray, depth_bins: int, depth_min: float, depth_max: float) -> np.ndarray:
+    """floor((q_z - depth_min) * D / (depth_max - depth_min)), clamped to D - 1 (fp64; for depth_min <= q_z < depth_max)."""
+    b = np.floor((depth - depth_min) * depth_bins / (depth_max - depth_min)).astype(np.int64)
+    return np.minimum(b, depth_bins - 1)
+
+
+def build_lift_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int, num_heights: int = DEFAULT_NUM_HEIGHTS,
+                     min_depth: float = DEFAULT_MIN_DEPTH, depth_bins: int = DEFAULT_DEPTH_BINS,
+                     depth_min: float = DEFAULT_DEPTH_MIN, depth_max: float = DEFAULT_DEPTH_MAX) -> LiftTable:
+    """build_projection_table's samples and fp64 geometry with a depth bin per sample: a sample is valid when the projection's
+    conditions hold and depth_min <= q_z < depth_max; its bin is depth_bin_of(q_z) and each of its four bilinear taps carries that
+    bin; weight = tap weight / the cell's count of valid samples.  Duplicate (cell, pixel, bin) entries are merged in fp64 before
+    the single rounding to fp32, exact zeros dropped.  With D = 1, depth_min = min_depth and depth_max beyond every sample this is
+    the projection table."""
+    D, depth_min, depth_max = check_depth_settings(depth_bins, depth_min, depth_max, min_depth)
+    P, ncols = bev_h * bev_w, rig.num_cameras * Hc * Wc
+    if ncols * D >= 2 ** 31 or P * ncols * D >= 2 ** 63:
+        raise ValueError(f"lift table: {ncols} pixels x {D} bins do not fit int32 columns")
+    rows, cols, bns, wts = [], [], [], []
+    count = np.zeros(P, dtype=np.int64)
+    for c, cells, depth, uf, vf in _camera_samples(rig, Hc, Wc, pc_range, bev_h, bev_w, num_heights, min_depth):
+        ranged = (depth >= depth_min) & (depth < depth_max)
+        cells, depth, uf, vf = cells[ranged], depth[ranged], uf[ranged], vf[ranged]
+        np.add.at(count, cells, 1)
+        sample_bin = depth_bin_of(depth, D, depth_min, depth_max)
+        for ok, pix, wt in _bilinear_taps(uf, vf, Hc, Wc):
+            rows.append(cells[ok])
+            cols.append(c * Hc * Wc + pix[ok])
+            bns.append(sample_bin[ok])
+            wts.append(wt[ok])
+    r = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    cl = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+    bn = np.concatenate(bns) if bns else np.zeros(0, np.int64)
+    wt = np.concatenate(wts) if wts else np.zeros(0, np.float64)
+    wt = wt / np.maximum(count[r], 1)
+    key = (r * ncols + cl) * D + bn
+    uniq, inv = np.unique(key, return_inverse=True)                               # sorted by (cell, pixel, bin)
+    merged = np.bincount(inv.reshape(-1), weights=wt, minlength=uniq.shape[0])
+    keep = merged != 0.0
+    uniq, merged = uniq[keep], merged[keep]
+    r, c2 = uniq // (ncols * D), uniq % (ncols * D)
+    if r.shape[0] >= 2 ** 31:
+        raise ValueError("lift table too large for int32 indices")
+    w32 = merged.astype(np.float32)
+    row_ptr = np.zeros(P + 1, dtype=np.int64)
+    np.cumsum(np.bincount(r, minlength=P), out=row_ptr[1:])
+    cl, bn = c2 // D, c2 % D
+    order = np.lexsort((bn, r, cl))                                               # by pixel, then cell, then bin
+    t_row_ptr = np.zeros(ncols + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cl, minlength=ncols), out=t_row_ptr[1:])
+    return LiftTable(P, ncols, D, row_ptr.astype(np.int32), c2.astype(np.int32), w32, t_row_ptr.astype(np.int32),
+                     r[order].astype(np.int32), bn[order].astype(np.int32), w32[order], merged)
+
+
+def apply_lift_table_fp64(t: LiftTable, feats: np.ndarray, pd: np.ndarray) -> np.ndarray:
+    """CPU fp64 application of the lift table with its fp64 weights: feats [B][ncols][C], pd [B][ncols][D] -> [B][P][C]."""
+    B, _, C = feats.shape
+    out = np.zeros((B, t.P, C), dtype=np.float64)
+    rows = np.repeat(np.arange(t.P), np.diff(t.row_ptr))
+    pix = t.col2 // t.D
+    for b in range(B):
+        np.add.at(out[b], rows, feats[b][pix] * (t.w64 * pd[b].reshape(-1)[t.col2])[:, None])
     return out

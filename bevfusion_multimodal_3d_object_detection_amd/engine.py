@@ -545,12 +545,8 @@ class CameraTable:
 def camera_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraTable:
     """The projection table of FlexibleBEVFusion `fus` ('project' branch) for ncam cameras of Hc x Wc features, built on the host in
     fp64 (camera_rig.build_projection_table) on first use and cached on the fusion's engine until set_camera_rig."""
-    rig = fus.camera_rig
-    if ncam != rig.num_cameras:
-        raise L.BevfError(f"BEV fusion (camera_view_transform='project'): the camera rig has {rig.num_cameras} cameras "
-                          f"({', '.join(rig.names)}) but the camera input has {ncam} (a 4-D input is one camera); pass "
-                          f"(B, {rig.num_cameras}, C, H, W) features or call set_camera_rig() with a matching rig")
-    eng = fus._eng()
+    _check_rig_cameras(fus, ncam)
+    rig, eng = fus.camera_rig, fus._eng()
     key = (rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_num_heights,
            fus.cam_min_depth, str(dev))
     tab = eng._camera_tables.get(key)
@@ -564,6 +560,78 @@ def camera_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraTabl
         tab = CameraTable(t.P, t.ncols, d(t.row_ptr), d(t.col), d(t.w), d(t.t_row_ptr), d(t.t_col), d(t.t_w))
         eng._camera_tables[key] = tab
     return tab
+
+
+@dataclass
+class CameraLiftTable:
+    """camera_rig.LiftTable on the device ('lift' branch): the cell table with col2 = pixel * D + bin for the forward, the transpose
+    (rows = camera feature pixels; cell, bin, weight per entry) for the backward, int32 / fp32."""
+    P: int
+    ncols: int
+    D: int
+    row_ptr: torch.Tensor
+    col2: torch.Tensor
+    w: torch.Tensor
+    t_row_ptr: torch.Tensor
+    t_cell: torch.Tensor
+    t_bin: torch.Tensor
+    t_w: torch.Tensor
+
+    def lift(self, x, pd, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
+        """y[b][cell][0:C] (row stride y_cs) = sum_e w_e pd[b][pix_e][bin_e] x[b][pix_e][0:C]: x NHWC features [B][ncols][C], pd the
+        depth distribution [B][ncols][D]."""
+        L.csr_lift(self.row_ptr, self.col2, self.w, self.P, self.ncols, self.D, x, self.ncols * C, C, pd, self.ncols * self.D, y,
+                   self.P * (y_cs or C), y_cs or C, B, C)
+
+    def lift_backward(self, x, pd, dy, dx, dpd, B: int, C: int) -> None:
+        """dx [B][ncols][C] and dpd [B][ncols][D] from dy [B][P][C]: every element of both written once."""
+        L.csr_lift_bwd(self.t_row_ptr, self.t_cell, self.t_bin, self.t_w, self.ncols, self.P, self.D, x, self.ncols * C, C, pd,
+                       self.ncols * self.D, dy, self.P * C, C, dx, self.ncols * C, C, dpd, self.ncols * self.D, B, C)
+
+
+def _check_rig_cameras(fus: nn.Module, ncam: int) -> None:
+    rig = fus.camera_rig
+    if ncam != rig.num_cameras:
+        raise L.BevfError(f"BEV fusion (camera_view_transform='{fus.camera_view_transform}'): the camera rig has {rig.num_cameras} "
+                          f"cameras ({', '.join(rig.names)}) but the camera input has {ncam} (a 4-D input is one camera); pass "
+                          f"(B, {rig.num_cameras}, C, H, W) features or call set_camera_rig() with a matching rig")
+
+
+def camera_lift_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraLiftTable:
+    """The lift table of FlexibleBEVFusion `fus` ('lift' branch) for ncam cameras of Hc x Wc features, built on the host in fp64
+    (camera_rig.build_lift_table) on first use and cached on the fusion's engine, next to the projection tables, until
+    set_camera_rig."""
+    _check_rig_cameras(fus, ncam)
+    rig, eng = fus.camera_rig, fus._eng()
+    key = ("lift", rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_num_heights,
+           fus.cam_min_depth, fus.cam_depth, str(dev))
+    tab = eng._camera_tables.get(key)
+    if tab is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.BevfError("BEV fusion: the camera lift table is built on first use, which cannot happen inside a graph "
+                              "capture -- run the forward once before capturing")
+        from . import camera_rig as CR
+        t = CR.build_lift_table(rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, fus.cam_num_heights, fus.cam_min_depth,
+                                *fus.cam_depth)
+        d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
+        tab = CameraLiftTable(t.P, t.ncols, t.D, d(t.row_ptr), d(t.col2), d(t.w), d(t.t_row_ptr), d(t.t_cell), d(t.t_bin), d(t.t_w))
+        eng._camera_tables[key] = tab
+    return tab
+
+
+def depth_net_width(D: int) -> int:
+    """Output channels the depth net is run with: D rounded up to the convolution kernels' 32-channel K step, because the data
+    gradient of the layer reads its output channels as input channels (Cin % 32 == 0) and the weight gradient wants Cout % 4 == 0.
+    The padding rows of the weight and the bias are zero and the softmax reads the first D columns only."""
+    return (D + 31) // 32 * 32
+
+
+def pad_depth_net(conv, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """depth_net's (weight [width][C][1][1], bias [width]) with zero rows appended."""
+    D = conv.weight.shape[0]
+    w = torch.nn.functional.pad(conv.weight.detach(), (0, 0, 0, 0, 0, 0, 0, width - D))
+    b = torch.nn.functional.pad(conv.bias.detach().float(), (0, width - D))
+    return w.contiguous(), b.contiguous()
 
 
 class FrameCameraTables:
@@ -706,6 +774,38 @@ class CameraProjectBranch(_CameraBranch):
         _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
 
 
+class CameraLiftBranch(_CameraBranch):
+    """Learned depth: depth_net (exact 1x1 conv + bias) -> softmax over the depth bins -> the lift gather through
+    the module rig's cached lift table -> camera_proj on the BEV grid, its second conv into the concat slice.  fp32, static rig."""
+
+    def pack(self, m) -> None:
+        super().pack(m)
+        self.D = m.depth_net.weight.shape[0]
+        self.Dp = depth_net_width(self.D)
+        w, b = pad_depth_net(m.depth_net, self.Dp)
+        Cc = w.shape[1]
+        self.dn = _finish_pack(w.permute(0, 2, 3, 1).contiguous().view(-1), torch.ones(self.Dp, device=w.device), b, Cc, self.Dp,
+                               1, 1, 0, False, split_ok=False, wino_ok=False)
+
+    def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
+        _, ncam, Hc, Wc = geom
+        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
+        m.check_lift_supported(camera_calib)
+        tab = camera_lift_table(m, ncam, Hc, Wc, cam.device)
+        rows = B * ncam * Hc * Wc
+        logits = buf("lift_logits", rows * self.Dp)
+        _run_conv(self.dn, cam, logits, B * ncam, Hc, Wc)
+        pd = buf("lift_pd", rows * self.D)
+        with _span("cam_lift_softmax", nbytes=4.0 * rows * (self.Dp + self.D)):
+            L.softmax_rows(logits, self.Dp, pd, self.D, rows, self.D)
+        proj = buf("cam_proj", B * Sh * Sw * Cc)
+        with _span("cam_lift", nbytes=4.0 * B * (Cc * (ncam * Hc * Wc + Sh * Sw) + rows * self.D // B)):
+            tab.lift(cam, pd, proj, B, Cc)
+        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
+        _run_conv(self.c1, proj, t1, B, Sh, Sw)
+        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+
+
 class LidarVectorBranch(_FusionBranch):
     """Input: the PointNet vector (B, C_l).  lidar_init to a start_size^2 canvas, conv, x2 bilinear, conv into the concat slice."""
 
@@ -789,7 +889,8 @@ class RadarBranch(_FusionBranch):
 
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
-    BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, pointnet=LidarVectorBranch, pillars=LidarPillarsBranch)
+    BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, lift=CameraLiftBranch, pointnet=LidarVectorBranch,
+                    pillars=LidarPillarsBranch)
 
     def __init__(self, module: nn.Module):
         super().__init__(module)

@@ -43,6 +43,10 @@ class FlexibleBEVFusion(nn.Module):
     grid after the projection, with no resize.  The module's rig (set_camera_rig) serves every frame unless the forward gets
     `camera_calib=`: one CameraRig per frame, or the fp64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device) --
     then every frame is lifted through its own table, built on the device inside the step.
+    Extension (opt-in, camera_view_transform 'lift'): the same samples with a learned per-pixel depth distribution
+    deciding where along its ray a feature lands -- depth_net = Conv2d(camera_channels, D, 1) (this mode's only extra parameters),
+    softmax over the D uniform depth bins of model.bev_fusion.camera_bev.depth, and every sample weighted by the probability of the
+    bin its depth falls into; camera_proj on the BEV grid as in 'project'.  fp32 storage and the module's static rig only.
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -56,11 +60,13 @@ class FlexibleBEVFusion(nn.Module):
         config = _cfg(config, config_path)
         default_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
         self.lidar_kind = lidar_encoder_kind(lidar_encoder_type, config)
-        # camera branch: 'mean' (the reference's camera average + resize) or 'project' (camera rig -> BEV grid)
+        # camera branch: 'mean' (the reference's camera average + resize), 'project' (camera rig -> BEV grid) or 'lift' (+ learned depth)
         self.camera_view_transform = CR.view_transform_kind(camera_view_transform, config)
         self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.DEFAULT_NUM_HEIGHTS, CR.DEFAULT_MIN_DEPTH, None
-        if self.camera_view_transform == "project":
+        if self.camera_view_transform in ("project", "lift"):
             self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.camera_bev_settings(config)
+        if self.camera_view_transform == "lift":             # (depth bins D, depth_min, depth_max) of the learned depth distribution
+            self.cam_depth = CR.camera_lift_settings(config, self.cam_min_depth)
         pillars = self.lidar_kind == "pillars"
         if config is not None:
             mc = config.get("model", {})
@@ -95,6 +101,8 @@ class FlexibleBEVFusion(nn.Module):
         bevc = self.bev_channels
         if self.use_camera:
             self.camera_proj = nn.Sequential(*_cbr(camera_channels, 512, 3), *_cbr(512, bevc, 1))
+            if self.camera_view_transform == "lift":         # per-pixel depth logits; exists in 'lift' mode only (state-dict keys)
+                self.depth_net = nn.Conv2d(camera_channels, self.cam_depth[0], 1)
         if self.use_lidar and pillars:
             self.lidar_bev = nn.Sequential(*_cbr(lidar_channels, 128, 3), *_cbr(128, bevc, 3))
         elif self.use_lidar:
@@ -118,13 +126,13 @@ class FlexibleBEVFusion(nn.Module):
 
     @property
     def camera_rig(self) -> CR.CameraRig:
-        """The rig of the 'project' camera branch (camera_rig.default_rig() unless set)."""
+        """The rig of the 'project' / 'lift' camera branch (camera_rig.default_rig() unless set)."""
         if self._camera_rig is None:
             self._camera_rig = CR.default_rig()
         return self._camera_rig
 
     def set_camera_rig(self, rig: "CR.CameraRig") -> None:
-        """Replace the camera rig of the 'project' branch; its projection tables are rebuilt on next use (outside a graph capture:
+        """Replace the camera rig of the 'project' / 'lift' branch; its projection tables are rebuilt on next use (outside a graph capture:
         re-capture a GraphedDetector after a rig change).  The rig is fixed for every frame until the next call."""
         if not isinstance(rig, CR.CameraRig):
             raise TypeError(f"set_camera_rig: expected a camera_rig.CameraRig, got {type(rig).__name__}")
@@ -138,6 +146,7 @@ class FlexibleBEVFusion(nn.Module):
         camera_rig.calib_matrices makes it) refers to the module rig's."""
         if camera_calib is None:
             return None
+        self.check_lift_supported(camera_calib)
         if self.camera_view_transform != "project":
             raise E.L.BevfError("camera_calib needs camera_view_transform='project': the 'mean' camera branch uses no calibration")
         if not B:                                                        # no camera input: nothing to calibrate
@@ -155,6 +164,17 @@ class FlexibleBEVFusion(nn.Module):
                              f"({B}, {ncam}, 4, 4)")
         return t, image_size
 
+    def check_lift_supported(self, camera_calib=None) -> None:
+        """The 'lift' branch runs the module's static rig in fp32 storage only; raises BevfError for what it does not support."""
+        if self.camera_view_transform != "lift" or not self.use_camera:
+            return
+        if camera_calib is not None:
+            raise E.L.BevfError("camera_calib with camera_view_transform='lift' is not supported: the learned-depth lift uses the "
+                                "module's static rig (set_camera_rig); per-frame calibration needs camera_view_transform='project'")
+        if self.depth_net.weight.dtype != torch.float32:
+            raise E.L.BevfError(f"{self.depth_net.weight.dtype} storage with camera_view_transform='lift' is not supported: the "
+                                "learned-depth lift kernels are fp32 only (bf16 models: camera_view_transform='project' or 'mean')")
+
     def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib=None):
         """Internal fast path on NHWC camera features (no layout change); camera_calib as camera_calib_tensor returns it."""
         return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib)
@@ -163,6 +183,7 @@ class FlexibleBEVFusion(nn.Module):
                 radar_features: Optional[torch.Tensor] = None, camera_calib=None) -> torch.Tensor:
         """camera_calib ('project' branch only): per-frame calibration -- a sequence of B camera_rig.CameraRig or the float64
         (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame."""
+        self.check_lift_supported(camera_calib)
         if camera_calib is not None:
             cf = camera_features if self.use_camera else None
             camera_calib = self.camera_calib_tensor(camera_calib, 0 if cf is None else cf.shape[0],
@@ -382,6 +403,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame."""
         camera_calib = self.camera_calib_tensor(camera_imgs, camera_calib)
+        if hasattr(self.fusion, "check_lift_supported"):
+            self.fusion.check_lift_supported()
         if self.training and (torch.is_grad_enabled() or _any_bn_training(self)):
             # under no_grad a train-mode model still normalises with batch statistics and updates the running buffers, as torch does
             from . import training                      # train-mode BN + tape + hand-written backward (training.py)

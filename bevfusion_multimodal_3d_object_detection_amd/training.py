@@ -1057,6 +1057,63 @@ class CameraProjectBranchTape(_FusionBranchTape):
         return dcam
 
 
+class _PaddedDepthNet:
+    """depth_net as ConvBNLayer sees it: weight / bias with zero rows appended up to engine.depth_net_width (the data-gradient conv
+    reads the layer's output channels as its Cin, a multiple of 32), and a sink that hands the first D rows of their gradients to the
+    real parameters."""
+
+    def __init__(self, conv, width: int):
+        self.real, self.D = conv, conv.weight.shape[0]
+        self.weight, self.bias = E.pad_depth_net(conv, width)
+        self.weight.requires_grad_(conv.weight.requires_grad)
+        self.bias.requires_grad_(conv.bias.requires_grad)
+        self.stride, self.padding = conv.stride, conv.padding
+
+    def sink(self, sink: GradSink):
+        pad = self
+
+        class _Sink:
+            def add(self, p, g):
+                real = pad.real.weight if p is pad.weight else pad.real.bias
+                sink.add(real, g.reshape(p.shape)[:pad.D])
+        return _Sink()
+
+
+class CameraLiftBranchTape(_FusionBranchTape):
+    """Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net -> softmax over the depth bins -> the lift gather through the module
+    rig's lift table -> camera_proj on the grid, the slot copy.  Keeps x and Pd; the backward runs the transposed table (dx and dPd
+    in one pass), the softmax backward and depth_net's gradients, whose data gradient takes dx as its residual input: dcam =
+    dx_lift + dx_depthnet without another pass over the feature map."""
+
+    def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
+        _, ncam, Hc, Wc = geom
+        fus, dev = self.fus, cam.device
+        fus.check_lift_supported(calib)
+        Cc = fus.camera_proj[0].weight.shape[1]
+        self.table = tab = E.camera_lift_table(fus, ncam, Hc, Wc, dev)
+        self.geom, self.Dp = (ncam, Hc, Wc, Cc), E.depth_net_width(tab.D)
+        rows = B * tab.ncols
+        self.padded = _PaddedDepthNet(fus.depth_net, self.Dp)
+        self.dn = ConvBNLayer(self.padded, None, relu=False)
+        logits, _, _ = self.dn.forward(cam, B * ncam, Hc, Wc)
+        self.x, self.pd = cam, _new(rows * tab.D, dev)
+        L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
+        proj = _new(B * self.H * self.W * Cc, dev)
+        tab.lift(cam, self.pd, proj, B, Cc)
+        self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
+
+    def backward(self, dconcat, sink):
+        dproj = self._pair_from_slot(dconcat, sink)
+        B, (ncam, Hc, Wc, Cc), tab, dev = self.B, self.geom, self.table, dconcat.device
+        rows = B * tab.ncols
+        dx, dpd = _new(rows * Cc, dev), _new(rows * tab.D, dev)
+        tab.lift_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # transposed table: every element written once
+        dlogit = _new(rows * self.Dp, dev)
+        L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
+        dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
+        return dcam
+
+
 class LidarVectorBranchTape(_FusionBranchTape):
     """Input the PointNet vector (B*C_l): lidar_init to the start_size^2 canvas, conv, x2 bilinear, conv, resize to the grid."""
 
@@ -1120,8 +1177,8 @@ class FusionTape:
     relied on: RELU_TRACE records in forward order, and DetectorTape marks the gradients final (sink.ready()) in the camera
     callback, after radar and LiDAR have contributed theirs."""
 
-    BRANCHES = dict(mean=CameraMeanBranchTape, project=CameraProjectBranchTape, pointnet=LidarVectorBranchTape,
-                    pillars=LidarPillarsBranchTape)
+    BRANCHES = dict(mean=CameraMeanBranchTape, project=CameraProjectBranchTape, lift=CameraLiftBranchTape,
+                    pointnet=LidarVectorBranchTape, pillars=LidarPillarsBranchTape)
 
     def __init__(self, fus):
         self.fus = fus

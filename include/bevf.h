@@ -445,6 +445,43 @@ int bevf_csr_gather_frames_bf16(const int32_t* row_ptr, size_t rp_stride, const 
                                 size_t e_stride, int nrows, const void* x, size_t x_bs, int x_cs, void* y, size_t y_bs,
                                 int y_cs, int B, int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Learned-depth camera -> BEV lift (csrc/camera_lift.hip): the opt-in camera branch `model.bev_fusion.camera_view_transform:
+ * lift`.  None of these has a counterpart in the reference (it has no view transform at all).  fp32 only,
+ * stream-ordered, capture-safe (nothing allocated), no atomics, every output element written exactly once, two launches
+ * give the same bits.  D = depth bins, 1 <= D <= 64.
+ *
+ * bevf_softmax_rows_f32.  y[r][0:D] (row stride y_rs) = softmax of x[r][0:D] (row stride x_rs) for r < nrows: row maximum
+ * subtracted, expf, the sum by a fixed butterfly over the row's lanes, one division per element.  No reference counterpart.
+ *
+ * bevf_softmax_rows_bwd_f32.  dx[r][d] (row stride x_rs) = pd[r][d] * (dpd[r][d] - sum_d pd[r][d] * dpd[r][d]) for d < D and
+ * 0 for D <= d < x_cols (x_cols <= 64: the padding columns of a logit buffer wider than D); pd / dpd rows at stride p_rs.
+ * No reference counterpart.
+ *
+ * bevf_csr_lift_f32.  y[b][r][0:C] = sum over e in [row_ptr[r], row_ptr[r+1]) of w[e] * pd[b][col2[e]] * x[b][col2[e] / D][0:C]
+ * -- bevf_csr_gather_f32 with a per-frame scalar per entry: col2 = pixel * D + bin (camera_rig.build_lift_table), pd [b] at
+ * pd + b * pd_bs holds the depth distribution [pixel][D] densely.  Same strides, slice output, zero rows, fp32 accumulation in
+ * table order as bevf_csr_gather_f32; with D = 1 and pd == 1 the same bits.  Needs C % 4 == 0, C <= 1024, 16-byte aligned
+ * x / y and 16-byte multiples for their strides, col2[e] < pixels * D.  No reference counterpart.
+ *
+ * bevf_csr_lift_bwd_f32.  The transposed table, CSR by pixel with (t_cell, t_bin, t_w) per entry, one wave per (pixel, frame):
+ *     dx [b][pix][0:C] = sum_e t_w[e] * pd[b][pix][t_bin[e]] * dy[b][t_cell[e]][0:C]
+ *     dpd[b][pix][d]   = sum over e with t_bin[e] == d of t_w[e] * <x[b][pix][0:C], dy[b][t_cell[e]][0:C]>
+ * in table order; the dot product is reduced over the wave by a fixed butterfly.  Bins and pixels without an entry get
+ * zeros.  dpd [b] at dpd + b * dpd_bs, dense [pixel][D] like pd.  B <= 65535; t_cell / t_bin / t_w may be NULL when the table
+ * has no entries.  No reference counterpart.
+ * ------------------------------------------------------------------------------------------ */
+int bevf_softmax_rows_f32(const float* x, int x_rs, float* y, int y_rs, size_t nrows, int D, void* stream);
+int bevf_softmax_rows_bwd_f32(const float* pd, const float* dpd, int p_rs, float* dx, int x_rs, int x_cols, size_t nrows,
+                              int D, void* stream);
+int bevf_csr_lift_f32(const int32_t* row_ptr, const int32_t* col2, const float* w, int nrows, int D, const float* x,
+                      size_t x_bs, int x_cs, const float* pd, size_t pd_bs, float* y, size_t y_bs, int y_cs, int B, int C,
+                      void* stream);
+int bevf_csr_lift_bwd_f32(const int32_t* t_row_ptr, const int32_t* t_cell, const int32_t* t_bin, const float* t_w, int npix,
+                          int D, const float* x, size_t x_bs, int x_cs, const float* pd, size_t pd_bs, const float* dy,
+                          size_t dy_bs, int dy_cs, float* dx, size_t dx_bs, int dx_cs, float* dpd, size_t dpd_bs, int B,
+                          int C, void* stream);
+
 /* ==========================================================================================
  * bf16 storage, fp32 accumulate (BASELINE configs 3 and 5).  Same layouts and geometry as the fp32 entry
  * points, element type bfloat16 wherever a pointer is typed void*: the convolution runs on

@@ -63,8 +63,10 @@ struct WinoArgs {
   // (a patch spans at most two images).  HS = 0: block rows per image, SB = N * TBY.
   int HS, SB;
   unsigned div_mul;    // ceil(2^32 / HS) (stacked) or ceil(2^32 / TBY) (0 for TBY = 1): row -> image by one s_mul_hi (the host checks the range)
-  unsigned long long* stamps;   // DIAG instantiations only (bevf_debug_wino_stamps): 5 x s_memtime per workgroup
+  unsigned long long* stamps;   // DIAG instantiations only (bevf_debug_wino_stamps): kWinoStamps x s_memtime per workgroup
 };
+
+constexpr int kWinoStamps = 6;  // start / first patch DMA issued / first operands transformed / K loop done / epilogue issued / stores acknowledged
 
 constexpr int PITCH = 36;                                      // floats per patch pixel in LDS (32 + 4 pad); 18x18 or 34x10 pixels
 constexpr int PDMA = 12;                                       // LDS-DMA instructions per wave and chunk (4 waves x 12 x 64 slots)
@@ -76,11 +78,13 @@ constexpr int LDS_BYTES = (2 * PATCH_FLOATS + 2 * BG_FLOATS) * 4;
 // tile rows 4w .. 4w+3) -- the host takes whichever covers the map with fewer blocks (57x100: 28 -> 26, 113x200: 104 -> 100).
 template <bool RES, bool RELU, bool STATS = false, int BNB = 0, int GEO = 0, bool DIAG = false>
 __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
-  auto stamp = [&](int i) {                                         // diagnostic launches only; the buffer is read by nothing else
+  auto stamp_at = [&](int i, unsigned long long tm) {                // diagnostic launches only; the buffer is read by nothing else
     if constexpr (DIAG) {
-      if (threadIdx.x == 0)
-        p.stamps[(size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 5 + i] = __builtin_amdgcn_s_memtime();
+      if (threadIdx.x == 0) p.stamps[(size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kWinoStamps + i] = tm;
     }
+  };
+  auto stamp = [&](int i) {
+    if constexpr (DIAG) stamp_at(i, __builtin_amdgcn_s_memtime());
   };
   stamp(0);
   constexpr int BHP = GEO ? 32 : 16, BWP = GEO ? 8 : 16;          // block height / width in pixels
@@ -101,14 +105,12 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   //      slot s = pixel s / 9, piece s % 9 (8 = pad) --------------------------------------------------------------------
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)kOob, 0x00020000);
   // n / rb: image and in-image row of the block's first pixel row; hw: rows after which a row index wraps into the next image
-  // The 12 slot offsets of a wave are what stands between the workgroup's start and its first HBM request, beside fp32 MFMAs that
-  // share the vector ALU with them: 24-bit multiplies only (full rate; every factor is < 2^24: a pixel index because the tensor stays
-  // below 2 GiB with >= 32 channels of 4 bytes), no division (3D grid, one s_mul_hi for the image of a row).
-  auto make_pv = [&](unsigned (&pv)[PDMA], int& n, int& rb, int& hw, int& bx, int& ct) {
-    bx = blockIdx.x;
-    const int sp = blockIdx.y;
-    ct = blockIdx.z;
-    int n0, r0;                                                     // image / in-image row of the patch's first row (block row - 1)
+  // The 12 slot offsets of a wave are what stands between the workgroup's start and its last HBM request (one wave per SIMD: ~5 cycles
+  // per dependent instruction, ~2.5 k cycles in all -- as much as the wait that follows, tools/wino_stamps.py): 24-bit multiplies (every
+  // factor is < 2^24: a pixel index because the tensor stays below 2 GiB with >= 32 channels of 4 bytes), no division (3D grid, one
+  // s_mul_hi for the image of a row).
+  // block row sp of the grid -> n0 / r0: image and in-image row of the patch's first row (block row - 1); n, rb, hw as above
+  auto block_rows = [&](int sp, int& n0, int& r0, int& n, int& rb, int& hw) {
     if (p.HS) {
       const int s0 = BHP * sp - 1 + p.HS, q0 = (int)__umulhi((unsigned)s0, p.div_mul);   // s0 / HS (+ HS: the division never sees -1)
       n0 = q0 - 1;
@@ -124,28 +126,44 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
       hw = 0x7fffffff;
       n = n0;
     }
-    const int ix0 = BWP * bx - 1;
-    const unsigned nh0 = (unsigned)(n0 * p.H), xcs4 = (unsigned)(p.x_cs * 4);
-#pragma unroll
-    for (int j = 0; j < PDMA; ++j) {
-      const unsigned sl = (unsigned)((4 * j + wave) * 64 + lane);
-      const unsigned pix = __umul24(sl, 7282u) >> 16, piece = sl - 9u * pix;                    // sl / 9 for sl < 3072
-      const unsigned py = __umul24(pix, GEO ? 6554u : 3641u) >> 16, px = pix - __umul24(py, (unsigned)PWP);   // pix / 10 (or / 18) for pix < 1024
-      int iy = r0 + (int)py;
-      const int ix = ix0 + (int)px;
-      const bool wr = iy >= hw;
-      iy -= wr ? hw : 0;
-      const bool ok = sl < (unsigned)PSLOTSG && piece < 8u && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W &&
-                      (unsigned)(n0 + (wr ? 1 : 0)) < (unsigned)p.N;
-      const unsigned row = nh0 + (wr ? (unsigned)p.H : 0u) + (unsigned)iy;                      // image row index over the batch
-      pv[j] = ok ? __umul24(__umul24(row, (unsigned)p.W) + (unsigned)ix, xcs4) + 16u * piece : kOob;
-    }
+  };
+  // byte offset in x of pixel pix (< 1024) of the patch that starts at row r0 of image n0, column ix0; ok: the pixel exists (inside the
+  // image, not in a dead row, image < N) -- whoever uses the offset sends every other lane to kOob
+  auto pixel_off = [&](unsigned pix, int n0, int r0, int hw, int ix0, bool& ok) {
+    const unsigned py = __umul24(pix, GEO ? 6554u : 3641u) >> 16, px = pix - __umul24(py, (unsigned)PWP);   // pix / 10 (or / 18) for pix < 1024
+    int iy = r0 + (int)py;
+    const int ix = ix0 + (int)px;
+    const bool wr = iy >= hw;
+    iy -= wr ? hw : 0;
+    ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && (unsigned)(n0 + (wr ? 1 : 0)) < (unsigned)p.N;
+    const unsigned row = (unsigned)(n0 * p.H) + (wr ? (unsigned)p.H : 0u) + (unsigned)iy;       // image row index over the batch
+    return __umul24(__umul24(row, (unsigned)p.W) + (unsigned)ix, (unsigned)(p.x_cs * 4));
   };
   auto patch_dma_from = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff, int buf, int j) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(patch + buf * PATCH_FLOATS + (4 * j + wave) * 256),
                                              16, voff, soff, 0, 0);
   };
   auto patch_dma = [&](unsigned voff, unsigned soff, int buf, int j) { patch_dma_from(rsx, voff, soff, buf, j); };
+  // the twelve slot offsets of this block's patch; each slot's chunk-0 DMA is issued as soon as its offset exists, so that its latency
+  // and its transfer into LDS (48 KB at 64 bytes per clock: ~770 cycles for the patch) run under the arithmetic of the slots behind it
+  auto make_pv = [&](unsigned (&pv)[PDMA], int& n, int& rb, int& hw, int& bx, int& ct) {
+    bx = blockIdx.x;
+    ct = blockIdx.z;
+    int n0, r0;
+    block_rows(blockIdx.y, n0, r0, n, rb, hw);
+    const int ix0 = BWP * bx - 1;
+#pragma unroll
+    for (int j = 0; j < PDMA; ++j) {
+      const unsigned sl = (unsigned)((4 * j + wave) * 64 + lane);
+      const unsigned pix = __umul24(sl, 7282u) >> 16, piece = sl - 9u * pix;                    // sl / 9 for sl < 3072
+      bool pok;
+      const unsigned off = pixel_off(pix, n0, r0, hw, ix0, pok);
+      const bool in_patch = (4 * j + 3) * 64 + 63 < PSLOTSG || sl < (unsigned)PSLOTSG;          // (wave < 4: only the last instruction's slots can lie past the patch)
+      pv[j] = (in_patch && piece < 8u && pok) ? off + 16u * piece : kOob;
+      patch_dma(pv[j], 0, 0, j);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
   // RES: in a tile's LAST chunk the "next chunk" slots have nothing to fetch; two of them (group 0's first two) then touch one 16-byte
   // piece of every 128-byte line of this wave's residual pixels -- the data lands in the idle patch buffer and is never read, but the
   // lines are in L2 when the epilogue asks for them ~3 groups later (the epilogue waited 4.7k cycles for HBM here: tools/wino_stamps.py)
@@ -202,8 +220,8 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
     for (int i = 0; i < 8; ++i) dma_piece((unsigned)(ct0 * G) * (BG_FLOATS * 4), 0, i);
   }
   make_pv(pv, n, rb, hw, bx, ct);
-#pragma unroll
-  for (int j = 0; j < PDMA; ++j) patch_dma(pv[j], 0, 0, j);
+  unsigned long long t_issued = 0;                                  // DIAG: everything the first wait depends on is in flight from here
+  if constexpr (DIAG) t_issued = __builtin_amdgcn_s_memtime();
   // Staging schedule (filter image of group g+1 and a third of a later patch chunk per group, everything by LDS-DMA, no
   // register staging and no ds_write in the loop): chunk c+1's patch is fetched in three parts, in the last group of
   // chunk c-1 and groups 0, 1 of chunk c, always AFTER the group's filter pieces.  Loads retire in order, so the
@@ -212,8 +230,9 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   // adds vmcnt(0) before any ds_write that follows an LDS-DMA: in-kernel ablation put 13 % of the kernel on those waits.)
 #pragma unroll
   for (int j = 0; j < 4; ++j) patch_dma(NCH > 1 ? pv[j] : kOob, 128, 1, j);
-  asm volatile("s_waitcnt vmcnt(4)");
-  __syncthreads();
+  // (wait + barrier as ONE asm, as at a group's end: __syncthreads() waits vmcnt(0), i.e. also for the four chunk-1 loads just issued,
+  //  which nothing reads before group 3; the first group's end, vmcnt(4) behind twelve younger loads, covers them)
+  asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
   for (int q = 0; q < 4; ++q) load_patch(0, 0, q);
 #pragma unroll
@@ -221,10 +240,12 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) cols_row(r);
   int pbuf = 0;                                                     // patch buffer holding the current chunk
-  stamp(1);
+  stamp_at(1, t_issued);
+  stamp(2);
 
   // one channel group (8 channels = 2 MFMA k-steps); gl = position in the 32-channel patch chunk (static)
-  //   pvl / psoff: where the NEXT chunk's patch comes from (this tile's next chunk, or the next tile's chunk 0)
+  //   pvl / psoff: where the NEXT chunk's patch comes from; in the tile's last chunk the slots have nothing to fetch (kOob: the DMA
+  //   writes zeros into the idle buffer) except, in the RES instantiations, group 0's first two: the residual prefetch (see rsr_pf)
   //   bimg: byte offset of the NEXT group's filter image in p.u (bnext false: nothing follows)
   auto group = [&](auto glc, auto firstc, const unsigned psoff, const unsigned bimg, const bool bnext) {
     constexpr int gl = decltype(glc)::value;
@@ -344,7 +365,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
     }
 
     asm volatile("s_waitcnt vmcnt(0)");                             // (the last, all-out-of-range patch part: LDS is reused below)
-    stamp(2);
+    stamp(3);
     if constexpr (STATS || BNB != 0) __syncthreads();              // ... by EVERY wave's zero-writing DMAs before any wave's partial sums land there
     // ---- epilogue: output transform per (tile, channel), scale/shift (+res) (+relu), store ----------------------------
     // acc[f][nb][r]: tile 4 kq + r of this wave = (tile row kq>>1, tile column 4 (kq&1) + r), channel ct*64 + nb*16 + (lane&15)
@@ -497,9 +518,9 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
       };
       if (interior) emit(std::true_type{}); else emit(std::false_type{});
       if constexpr (DIAG) {
-        stamp(3);                                                   // everything issued ...
+        stamp(4);                                                   // everything issued ...
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp(4);                                                   // ... and every store acknowledged
+        stamp(5);                                                   // ... and every store acknowledged
       }
       if constexpr (STATS || BNB != 0) {                            // one partial row per tile block: the four waves' sums in fixed order
         __syncthreads();
@@ -549,7 +570,7 @@ __global__ __launch_bounds__(256) void wino_filter_transform(const float* __rest
 }  // namespace
 
 static unsigned long long* g_wino_stamps = nullptr;
-// Diagnostic (tools/wino_stamps.py): buf = device buffer of 5 x 8 bytes per workgroup of the NEXT plain launches (relu, optional residual),
+// Diagnostic (tools/wino_stamps.py): buf = device buffer of 6 x 8 bytes (kWinoStamps) per workgroup of the NEXT plain launches (relu, optional residual),
 // or null to stop
 extern "C" int bevf_debug_wino_stamps(void* buf) {
   g_wino_stamps = static_cast<unsigned long long*>(buf);
@@ -661,7 +682,7 @@ extern "C" int bevf_conv3x3_wino_f32(const bevf_conv_desc* d, void* stream) {
     hipLaunchKernelGGL((wino_f32<false, false, true>), grid, block, LDS_BYTES, st, a);
     return bevf_check_launch("bevf_conv3x3_wino_f32");
   }
-  if (g_wino_stamps && d->relu) {                                  // diagnostic launch: same kernel, five time stamps per workgroup
+  if (g_wino_stamps && d->relu) {                                  // diagnostic launch: same kernel, six time stamps per workgroup
     a.stamps = g_wino_stamps;
     auto go = [&](auto kern) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fused fp32 Winograd convolution on the 3x3 / stride 1 layer shapes of config 2 at B=8 (TF direct-equivalent), with both
 block geometries (16x16-pixel and 32x8-pixel blocks), each per image and over the images' rows stacked into one map; the launcher
-(auto) picks the tiling with the fewest blocks."""
+(auto) picks the tiling with the fewest blocks.
+usage: wino_bench.py [name,name,...] [auto]   ("auto": only the tiling the launcher picks; BEVF_AB_LIB=<other .so> for an A/B)"""
 import os
 import sys
 
@@ -9,6 +10,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from bevfusion_multimodal_3d_object_detection_amd import _lib as L
+
+if os.environ.get("BEVF_AB_LIB"):
+    L.LIB_PATH = os.environ["BEVF_AB_LIB"]
 
 SHAPES = {  # name: (N, H, W, Cin, Cout, residual)
     "layer1": (48, 225, 400, 64, 64, False), "layer1r": (48, 225, 400, 64, 64, True),
@@ -18,7 +22,10 @@ SHAPES = {  # name: (N, H, W, Cin, Cout, residual)
     "t_layer2": (48, 56, 100, 128, 128, True), "t_layer3": (48, 28, 50, 256, 256, True), "t_layer4": (48, 14, 25, 512, 512, True),
 }
 dev = torch.device("cuda")
-names = sys.argv[1].split(",") if len(sys.argv) > 1 else list(SHAPES)
+names = sys.argv[1].split(",") if len(sys.argv) > 1 and sys.argv[1] != "all" else list(SHAPES)
+TILINGS = ((1, "16x16"), (2, "32x8"), (3, "16x16 stacked"), (4, "32x8 stacked"), (0, "auto"))
+if len(sys.argv) > 2 and sys.argv[2] == "auto":
+    TILINGS = TILINGS[-1:]
 for name in names:
     N, H, W, Cin, Cout, res = SHAPES[name]
     x = torch.randn(N * H * W * Cin, device=dev)
@@ -28,7 +35,7 @@ for name in names:
     r = torch.randn(N * H * W * Cout, device=dev) if res else None
     flops = 2.0 * N * H * W * Cout * 9 * Cin
     line = f"{name:8s} N={N} {H}x{W} {Cin}->{Cout}{' +res' if res else ''}:"
-    for tile, label in ((1, "16x16"), (2, "32x8"), (3, "16x16 stacked"), (4, "32x8 stacked"), (0, "auto")):
+    for tile, label in TILINGS:
         y = torch.empty(N * H * W * Cout, device=dev)
         run = lambda: L.conv3x3_wino(x, u, sc, sh, y, N=N, H=H, W=W, Cin=Cin, x_cs=Cin, Cout=Cout, y_cs=Cout, relu=True,
                                      res=r, res_cs=Cout if res else 0, tile=tile)

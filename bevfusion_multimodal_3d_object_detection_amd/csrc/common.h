@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/bevf.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -27,6 +29,29 @@ static inline int bevf_check_launch(const char* what) {
     return BEVF_ERR_LAUNCH;
   }
   return BEVF_OK;
+}
+
+// Every launch that asks for dynamic LDS goes through bevf_launch.  Above the 64 KB default a kernel has to opt in, and
+// the runtime keeps that opt-in per device: bevf_grant_lds (api.hip) remembers the bytes granted per (kernel, device),
+// raises them when a launch needs more, and reports a refusal instead of leaving it to the launch.
+int bevf_grant_lds(const char* entry, const void* kernel, size_t lds_bytes);
+
+template <typename... P, typename... A>
+static inline int bevf_launch(const char* entry, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream,
+                              const A&... args) {
+  if (lds_bytes > 64 * 1024) {
+    const int rc = bevf_grant_lds(entry, reinterpret_cast<const void*>(kernel), lds_bytes);
+    if (rc != BEVF_OK) return rc;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+  return bevf_check_launch(entry);
+}
+
+// Runtime flag -> template argument: f(std::true_type{}) or f(std::false_type{}); nest one call per flag and name only the
+// combinations that should exist as kernels inside.
+template <typename F>
+static inline int bevf_dispatch_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
 static inline bool bevf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -852,44 +852,25 @@ extern "C" int bevf_conv3x3_bf16(const bevf_conv_desc* d, void* stream) {
   // blocks (2 per CU).  Auto: tools/conv3x3_bench.py
   constexpr int lds128 = C3Geo<128, 2, 16>::LDS_BYTES, lds64 = C3Geo<64, 2, 16>::LDS_BYTES, lds64s = C3Geo<64, 1, 16>::LDS_BYTES,
                 lds64t = C3Geo<64, 1, 32>::LDS_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16<64, 2, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16<128, 2, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds128);
-    attr_done = true;
-  }
   const int variant = CT == 128 ? 1 : ((d->tile && d->tile < 4) ? d->tile : (d->Cin >= 128 ? 2 : C3_AUTO_SHORTK));
   if (variant == 3) { a.TBY = (d->H + 31) / 32; }
   const long long ntiles = (long long)d->N * a.TBY * a.TBX * a.nct;
   BEVF_REQUIRE(ntiles < (1ll << 31), "conv3x3_bf16: too many tiles");
   const dim3 grid((unsigned)ntiles), block(256);
   if (CT == 64 && d->Cin == 64 && (d->tile == 5 || (d->tile == 0 && C3_AUTO_WIDE64))) {      // both channel halves in one patch image
-    static bool wattr = false;
     constexpr int ldsw = 4 * 12 * 1024 + 8 * 4096;
-    if (!wattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_wide64<64>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw);
-      wattr = true;
-    }
     a.TBY = (d->H + 15) / 16;
     const long long nt16 = (long long)d->N * a.TBY * a.TBX * a.nct;
-    hipLaunchKernelGGL((conv3x3_bf16_wide64<64>), dim3((unsigned)nt16), block, ldsw, st, a);
-    return bevf_check_launch("bevf_conv3x3_bf16");
+    return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16_wide64<64>, dim3((unsigned)nt16), block, ldsw, st, a);
   }
   if (CT == 64 && (d->tile == 4 || (d->tile == 0 && C3_AUTO_PERSIST && d->Cin < 128))) {                // persistent form (two patch buffers, 16-row blocks)
-    static bool pattr = false;
-    if (!pattr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_bf16_persist<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds64);
-      pattr = true;
-    }
     a.TBY = (d->H + 15) / 16;
     const long long nt16 = (long long)d->N * a.TBY * a.TBX * a.nct;
     const dim3 pgrid((unsigned)(nt16 < 512 ? nt16 : 512));          // 2 workgroups per CU
-    hipLaunchKernelGGL((conv3x3_bf16_persist<64>), pgrid, block, lds64, st, a, (int)nt16);
-    return bevf_check_launch("bevf_conv3x3_bf16");
+    return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16_persist<64>, pgrid, block, lds64, st, a, (int)nt16);
   }
-  if (CT == 128) hipLaunchKernelGGL((conv3x3_bf16<128, 2, 16>), grid, block, lds128, st, a);
-  else if (variant == 3) hipLaunchKernelGGL((conv3x3_bf16<64, 1, 32>), grid, block, lds64t, st, a);
-  else if (variant == 2) hipLaunchKernelGGL((conv3x3_bf16<64, 1, 16>), grid, block, lds64s, st, a);
-  else hipLaunchKernelGGL((conv3x3_bf16<64, 2, 16>), grid, block, lds64, st, a);
-  return bevf_check_launch("bevf_conv3x3_bf16");
+  if (CT == 128) return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16<128, 2, 16>, grid, block, lds128, st, a);
+  if (variant == 3) return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16<64, 1, 32>, grid, block, lds64t, st, a);
+  if (variant == 2) return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16<64, 1, 16>, grid, block, lds64s, st, a);
+  return bevf_launch("bevf_conv3x3_bf16", conv3x3_bf16<64, 2, 16>, grid, block, lds64, st, a);
 }

@@ -52,6 +52,37 @@ static void fastdiv_make(int d, unsigned* mul, unsigned* sh) {
   *sh = (unsigned)(s - 1);
 }
 
+// bevf_conv_desc -> ConvArgs for the implicit-GEMM entry points: the rules they share, reported as "<who>: ...", then the fill
+// (tile counts and the hybrid split stay zero for the launch helpers).  x_es / w_es = bytes per activation / weight element.
+// The rules that only one kernel has (y / colmax presence, y_cs, ...) stay in its entry point.
+static int conv_args_from_desc(const bevf_conv_desc* d, const char* who, int x_es, int w_es, ConvArgs* out) {
+  BEVF_REQUIRE(d && d->x && d->w, "%s: null x/w", who);
+  BEVF_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "%s: empty shape", who);
+  BEVF_REQUIRE(d->Cin > 0 && d->Cin % (128 / x_es) == 0, "%s: Cin=%d must be a positive multiple of %d", who, d->Cin, 128 / x_es);
+  BEVF_REQUIRE(d->x_cs >= d->Cin && d->x_cs % (16 / x_es) == 0, "%s: x_cs=%d must be >= Cin and a multiple of %d", who, d->x_cs, 16 / x_es);
+  BEVF_REQUIRE(bevf_aligned16(d->x) && bevf_aligned16(d->w), "%s: x/w must be 16-byte aligned", who);
+  BEVF_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "%s: bad kernel geometry", who);
+  BEVF_REQUIRE((d->H + 2 * d->pad - d->KH) / d->stride + 1 == d->Ho && (d->W + 2 * d->pad - d->KW) / d->stride + 1 == d->Wo,
+               "%s: Ho/Wo (%d,%d) inconsistent with H,W,k,stride,pad", who, d->Ho, d->Wo);
+  BEVF_REQUIRE(!d->res || d->res_cs >= d->Cout, "%s: res_cs < Cout", who);
+  BEVF_REQUIRE((long long)d->N * d->H * d->W * d->x_cs * x_es < (1ll << 31) &&
+                   (long long)d->Cout * d->KH * d->KW * d->Cin * w_es < (1ll << 31),
+               "%s: input / weight buffers must stay below 2 GiB (32-bit buffer offsets)", who);
+  const long long M = (long long)d->N * d->Ho * d->Wo;
+  BEVF_REQUIRE(M < (1ll << 31), "%s: pixel count overflows int32", who);
+  ConvArgs& a = *out;
+  a.x = d->x; a.w = d->w; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.y = d->y; a.colmax = d->colmax;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.x_cs = d->x_cs;
+  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.y_cs = d->y_cs; a.res_cs = d->res_cs;
+  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+  a.relu = d->relu; a.rows_per_group = d->rows_per_group;
+  a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.tilesM = a.tilesN = 0;
+  a.m_split = 0; a.nbig = 0; a.tilesN_big = 0;
+  fastdiv_make(d->Ho * d->Wo, &a.div_hw_mul, &a.div_hw_sh);
+  fastdiv_make(d->Wo, &a.div_w_mul, &a.div_w_sh);
+  return BEVF_OK;
+}
+
 // Epilogue of one workgroup tile.  acc[mi][ni] is the 32x32 MFMA tile (mi, ni) of this wave: C[i][j] with
 // j = lane&31 (channel) and i = (r&3) + 8*(r>>2) + 4*(lane>>5) (pixel).  T = storage type of y / res.
 template <typename T, int BM, int BN, int WM, int WN>

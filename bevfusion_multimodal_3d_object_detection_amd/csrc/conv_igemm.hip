@@ -272,15 +272,7 @@ int launch(const ConvArgs& a0, hipStream_t st) {
   a.tilesM = (a.M + BM - 1) / BM;
   a.tilesN = (a.Cout + BN - 1) / BN;
   constexpr size_t lds_bytes = size_t(2) * (BM + BN) * BK * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (lds_bytes > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm<T, BM, BN, WM, WN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_igemm<T, BM, BN, WM, WN>), dim3(a.tilesM * a.tilesN), dim3(256), lds_bytes, st, a);
-  return bevf_check_launch("bevf_conv2d_nhwc_f32");
+  return bevf_launch("bevf_conv2d_nhwc_f32", conv_igemm<T, BM, BN, WM, WN>, dim3(a.tilesM * a.tilesN), dim3(256), lds_bytes, st, a);
 }
 
 template <typename T, int BM, int BN, int WM, int WN>
@@ -293,15 +285,7 @@ int launch_hybrid(const ConvArgs& a0, int big_mtiles, hipStream_t st) {
   a.tilesM = (a.M - a.m_split + 63) / 64;
   const int nsmall = a.tilesM * a.tilesN;
   constexpr size_t lds_bytes = size_t(2) * (BM + BN) * BK * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (lds_bytes > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_hybrid<T, BM, BN, WM, WN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_igemm_hybrid<T, BM, BN, WM, WN>), dim3(a.nbig + nsmall), dim3(256), lds_bytes, st, a);
-  return bevf_check_launch("bevf_conv2d_nhwc_f32");
+  return bevf_launch("bevf_conv2d_nhwc_f32", conv_igemm_hybrid<T, BM, BN, WM, WN>, dim3(a.nbig + nsmall), dim3(256), lds_bytes, st, a);
 }
 
 constexpr int kResidentBig = 512;     // 256 CUs x 2 workgroups (64-80 KB of LDS each)
@@ -321,35 +305,14 @@ static int split_big_mtiles(long long M, int BM, int tilesN_big, int resident = 
 
 template <typename T>
 int conv_entry(const bevf_conv_desc* d, void* stream) {
-  constexpr int ES = (int)sizeof(T), BKE = 128 / ES;
-  BEVF_REQUIRE(d && d->x && d->w, "conv: null x/w");
-  BEVF_REQUIRE(d->y || d->colmax, "conv: neither y nor colmax given");
-  BEVF_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "conv: empty shape");
-  BEVF_REQUIRE(d->Cin > 0 && d->Cin % BKE == 0, "conv: Cin=%d must be a positive multiple of %d", d->Cin, BKE);
-  BEVF_REQUIRE(d->x_cs >= d->Cin && d->x_cs % (16 / ES) == 0, "conv: x_cs=%d must be >= Cin and a multiple of %d", d->x_cs, 16 / ES);
-  BEVF_REQUIRE(bevf_aligned16(d->x) && bevf_aligned16(d->w), "conv: x/w must be 16-byte aligned");
-  BEVF_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "conv: bad kernel geometry");
-  BEVF_REQUIRE((d->H + 2 * d->pad - d->KH) / d->stride + 1 == d->Ho && (d->W + 2 * d->pad - d->KW) / d->stride + 1 == d->Wo,
-               "conv: Ho/Wo (%d,%d) inconsistent with H,W,k,stride,pad", d->Ho, d->Wo);
-  BEVF_REQUIRE(!d->y || d->y_cs >= d->Cout, "conv: y_cs=%d < Cout=%d", d->y_cs, d->Cout);
-  BEVF_REQUIRE(!d->res || d->res_cs >= d->Cout, "conv: res_cs < Cout");
-  BEVF_REQUIRE(!d->colmax || (d->rows_per_group > 0 && d->relu), "conv: colmax needs rows_per_group > 0 and relu");
-  BEVF_REQUIRE((long long)d->N * d->H * d->W * d->x_cs * ES < (1ll << 31) &&
-                   (long long)d->Cout * d->KH * d->KW * d->Cin * ES < (1ll << 31),
-               "conv: input / weight buffers must stay below 2 GiB (32-bit buffer offsets)");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  BEVF_REQUIRE(M < (1ll << 31) && (long long)d->N * d->H * d->W < (1ll << 31), "conv: pixel count overflows int32");
-
+  constexpr int ES = (int)sizeof(T);
   ConvArgs a;
-  a.x = d->x; a.w = d->w; a.scale = d->scale; a.shift = d->shift; a.res = d->res; a.y = d->y; a.colmax = d->colmax;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.x_cs = d->x_cs;
-  a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.y_cs = d->y_cs; a.res_cs = d->res_cs;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.relu = d->relu; a.rows_per_group = d->rows_per_group;
-  a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.tilesM = a.tilesN = 0;
-  a.m_split = 0; a.nbig = 0; a.tilesN_big = 0;
-  fastdiv_make(d->Ho * d->Wo, &a.div_hw_mul, &a.div_hw_sh);
-  fastdiv_make(d->Wo, &a.div_w_mul, &a.div_w_sh);
+  if (const int rc = conv_args_from_desc(d, "conv", ES, ES, &a)) return rc;
+  BEVF_REQUIRE(d->y || d->colmax, "conv: neither y nor colmax given");
+  BEVF_REQUIRE(!d->y || d->y_cs >= d->Cout, "conv: y_cs=%d < Cout=%d", d->y_cs, d->Cout);
+  BEVF_REQUIRE(!d->colmax || (d->rows_per_group > 0 && d->relu), "conv: colmax needs rows_per_group > 0 and relu");
+  BEVF_REQUIRE((long long)d->N * d->H * d->W < (1ll << 31), "conv: pixel count overflows int32");
+  const long long M = a.M;
   hipStream_t st = static_cast<hipStream_t>(stream);
 
   switch (d->tile) {

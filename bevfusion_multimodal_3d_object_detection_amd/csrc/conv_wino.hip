@@ -650,72 +650,23 @@ extern "C" int bevf_conv3x3_wino_f32(const bevf_conv_desc* d, void* stream) {
     a.div_mul = (unsigned)(((1ull << 32) + dv - 1) / dv);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
-  }
   const dim3 grid((unsigned)a.TBX, (unsigned)a.SB, (unsigned)a.nct), block(256);
-  if (d->bnb_x) {
-    static bool bnb_attr = false;
-    if (!bnb_attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      bnb_attr = true;
-    }
-    if (d->res) {
-      if (d->bnb_y) hipLaunchKernelGGL((wino_f32<true, false, false, 2>), grid, block, LDS_BYTES, st, a);
-      else hipLaunchKernelGGL((wino_f32<true, false, false, 1>), grid, block, LDS_BYTES, st, a);
-    } else {
-      if (d->bnb_y) hipLaunchKernelGGL((wino_f32<false, false, false, 2>), grid, block, LDS_BYTES, st, a);
-      else hipLaunchKernelGGL((wino_f32<false, false, false, 1>), grid, block, LDS_BYTES, st, a);
-    }
-    return bevf_check_launch("bevf_conv3x3_wino_f32");
-  }
-  if (d->stats) {
-    hipLaunchKernelGGL((wino_f32<false, false, true>), grid, block, LDS_BYTES, st, a);
-    return bevf_check_launch("bevf_conv3x3_wino_f32");
-  }
-  if (g_wino_stamps && d->relu) {                                  // diagnostic launch: same kernel, six time stamps per workgroup
-    a.stamps = g_wino_stamps;
-    auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      hipLaunchKernelGGL(kern, grid, block, LDS_BYTES, st, a);
-    };
-    if (d->res) { if (geo1) go(&wino_f32<true, true, false, 0, 1, true>); else go(&wino_f32<true, true, false, 0, 0, true>); }
-    else { if (geo1) go(&wino_f32<false, true, false, 0, 1, true>); else go(&wino_f32<false, true, false, 0, 0, true>); }
-    return bevf_check_launch("bevf_conv3x3_wino_f32");
-  }
-  if (geo1) {
-    static bool attr1 = false;
-    if (!attr1) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, false, false, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<false, true, false, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, false, false, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32<true, true, false, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-      attr1 = true;
-    }
-    if (d->res) {
-      if (d->relu) hipLaunchKernelGGL((wino_f32<true, true, false, 0, 1>), grid, block, LDS_BYTES, st, a);
-      else hipLaunchKernelGGL((wino_f32<true, false, false, 0, 1>), grid, block, LDS_BYTES, st, a);
-    } else {
-      if (d->relu) hipLaunchKernelGGL((wino_f32<false, true, false, 0, 1>), grid, block, LDS_BYTES, st, a);
-      else hipLaunchKernelGGL((wino_f32<false, false, false, 0, 1>), grid, block, LDS_BYTES, st, a);
-    }
-    return bevf_check_launch("bevf_conv3x3_wino_f32");
-  }
-  if (d->res) {
-    if (d->relu) hipLaunchKernelGGL((wino_f32<true, true>), grid, block, LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((wino_f32<true, false>), grid, block, LDS_BYTES, st, a);
-  } else {
-    if (d->relu) hipLaunchKernelGGL((wino_f32<false, true>), grid, block, LDS_BYTES, st, a);
-    else hipLaunchKernelGGL((wino_f32<false, false>), grid, block, LDS_BYTES, st, a);
-  }
-  return bevf_check_launch("bevf_conv3x3_wino_f32");
+  auto go = [&](auto kern) { return bevf_launch("bevf_conv3x3_wino_f32", kern, grid, block, LDS_BYTES, st, a); };
+  // the launchable instantiations of wino_f32<RES, RELU, STATS, BNB, GEO, DIAG>: BNB 1 / 2 x RES, STATS, DIAG x RES x GEO, plain RES x RELU x GEO
+  if (d->bnb_x)
+    return bevf_dispatch_bool(d->res != nullptr, [&](auto R) {
+      constexpr bool res = decltype(R)::value;
+      return d->bnb_y ? go(&wino_f32<res, false, false, 2>) : go(&wino_f32<res, false, false, 1>);
+    });
+  if (d->stats) return go(&wino_f32<false, false, true>);
+  const bool diag = g_wino_stamps && d->relu;                      // diagnostic launch: same kernel, six time stamps per workgroup
+  if (diag) a.stamps = g_wino_stamps;
+  return bevf_dispatch_bool(d->res != nullptr, [&](auto R) {
+    return bevf_dispatch_bool(geo1, [&](auto G) {
+      constexpr bool res = decltype(R)::value;
+      constexpr int geo = decltype(G)::value;
+      if (diag) return go(&wino_f32<res, true, false, 0, geo, true>);
+      return d->relu ? go(&wino_f32<res, true, false, 0, geo>) : go(&wino_f32<res, false, false, 0, geo>);
+    });
+  });
 }

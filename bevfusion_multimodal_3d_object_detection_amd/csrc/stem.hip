@@ -478,16 +478,9 @@ static int stem_entry(const float* x, const float* w, const float* scale, const 
   const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
   const long long grid = (long long)N * tilesH * tilesW;
   BEVF_REQUIRE(grid < (1ll << 31), "stem: grid too large");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv7x7<TO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemLds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(stem_conv7x7<TO>, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x,
+  return bevf_launch("bevf_stem_conv7x7", stem_conv7x7<TO>, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x,
                      w, scale, shift, static_cast<TO*>(y), H, W, Ho, Wo, tilesW, tilesH,
                      (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0, relu);
-  return bevf_check_launch("bevf_stem_conv7x7");
 }
 extern "C" int bevf_stem_conv7x7_f32(const float* x, const float* w, const float* scale, const float* shift,
                                      float* y, int N, int H, int W, int relu, void* stream) {
@@ -521,14 +514,8 @@ extern "C" int bevf_stem_pool_f32(const float* x, const float* w, const float* s
   const int rps = (Hp + best_seg - 1) / best_seg, nseg = (Hp + rps - 1) / rps;
   const long long grid = (long long)N * tilesW * nseg;
   BEVF_REQUIRE(grid < (1ll << 31), "stem_pool: grid too large");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pool7x7), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemLds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(stem_pool7x7, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x, w, scale, shift, y,
-                     H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
-  return bevf_check_launch("bevf_stem_pool_f32");
+  return bevf_launch("bevf_stem_pool_f32", stem_pool7x7, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x, w,
+                     scale, shift, y, H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
 }
 
 template <typename T>
@@ -560,16 +547,9 @@ extern "C" int bevf_stem_wgrad_f32(const float* x, const float* dy, float* dw, i
   const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
   const long long tiles = (long long)N * tilesH * tilesW;
   BEVF_REQUIRE(tiles < (1ll << 31), "stem_wgrad: too many tiles");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_wgrad), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kStemWgradLds);
-    attr_done = true;
-  }
   const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);          // 2 workgroups per CU, each over many tiles
-  hipLaunchKernelGGL(stem_wgrad, dim3(grid), dim3(256), kStemWgradLds, static_cast<hipStream_t>(stream), x, dy, dw, N, H, W, Ho,
-                     Wo, tilesW, tilesH, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
-  return bevf_check_launch("bevf_stem_wgrad_f32");
+  return bevf_launch("bevf_stem_wgrad_f32", stem_wgrad, dim3(grid), dim3(256), kStemWgradLds, static_cast<hipStream_t>(stream), x, dy, dw,
+                     N, H, W, Ho, Wo, tilesW, tilesH, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
 }
 
 // ---- bf16 stem (bf16-storage models): 7x7 stride-2 conv on v_mfma_f32_32x32x16_bf16 -----------------------------------
@@ -1113,16 +1093,9 @@ extern "C" int bevf_stem_conv7x7_bf16mma(const float* x, const void* w_packed, c
   const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
   const long long grid = (long long)N * tilesH * tilesW;
   BEVF_REQUIRE(grid < (1ll << 31), "stem bf16: grid too large");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv7x7_bf16mma<__bf16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemBf16Lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(stem_conv7x7_bf16mma<__bf16>, dim3((unsigned)grid), dim3(256), kStemBf16Lds,
+  return bevf_launch("bevf_stem_conv7x7_bf16mma", stem_conv7x7_bf16mma<__bf16>, dim3((unsigned)grid), dim3(256), kStemBf16Lds,
                      static_cast<hipStream_t>(stream), x, static_cast<const __bf16*>(w_packed), scale, shift,
                      static_cast<__bf16*>(y), H, W, Ho, Wo, tilesW, tilesH, relu);
-  return bevf_check_launch("bevf_stem_conv7x7_bf16mma");
 }
 
 // bf16 stem + max-pool fused (fp32 image in, bf16 pooled NHWC out [N][Hp][Wp][64]); bit-identical to
@@ -1147,21 +1120,9 @@ extern "C" int bevf_stem_pool_bf16mma(const float* x, const void* w_packed, cons
   const int rps = (Hp + best_seg - 1) / best_seg, nseg = (Hp + rps - 1) / rps;
   const long long grid = (long long)N * tilesW * nseg;
   BEVF_REQUIRE(grid < (1ll << 31), "stem_pool bf16: grid too large");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pool7x7_bf16mma), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kStemBf16Lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pool7x7_bf16v2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kStemBf16V2Lds);
-    attr_done = true;
-  }
   // BEVF_STEM_BF16_EXPAND=1: the round-2 kernel (column tile expanded in LDS), kept for A/B; default: fragments straight from the patch
   static const bool expand = getenv("BEVF_STEM_BF16_EXPAND") != nullptr;
-  if (expand)
-    hipLaunchKernelGGL(stem_pool7x7_bf16mma, dim3((unsigned)grid), dim3(256), kStemBf16Lds, static_cast<hipStream_t>(stream), x,
-                       static_cast<const __bf16*>(w_packed), scale, shift, static_cast<__bf16*>(y), H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps);
-  else
-    hipLaunchKernelGGL(stem_pool7x7_bf16v2, dim3((unsigned)grid), dim3(256), kStemBf16V2Lds, static_cast<hipStream_t>(stream), x,
-                       static_cast<const __bf16*>(w_packed), scale, shift, static_cast<__bf16*>(y), H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps);
-  return bevf_check_launch("bevf_stem_pool_bf16mma");
+  return bevf_launch("bevf_stem_pool_bf16mma", expand ? stem_pool7x7_bf16mma : stem_pool7x7_bf16v2, dim3((unsigned)grid), dim3(256),
+                     expand ? kStemBf16Lds : kStemBf16V2Lds, static_cast<hipStream_t>(stream), x, static_cast<const __bf16*>(w_packed), scale,
+                     shift, static_cast<__bf16*>(y), H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps);
 }

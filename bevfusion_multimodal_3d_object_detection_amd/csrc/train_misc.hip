@@ -757,8 +757,8 @@ extern "C" int bevf_sparse_rows_wgrad_f32(const float* S, const int32_t* idx, co
 extern "C" int bevf_sparse_rows_scatter_add_f32(const float* S, const int32_t* idx, const float* W, float* dA, int G, int P, int C, int K,
                                                 void* stream) {
   BEVF_REQUIRE(S && idx && W && dA && G > 0 && G < 65536 && P > 0 && C > 0 && C <= 16384 && K > 0, "sparse_rows_scatter_add: bad arguments");
-  hipLaunchKernelGGL(sparse_rows_scatter, dim3((unsigned)C, (unsigned)G), dim3(256), (size_t)C * sizeof(int), ST, S, idx, W, dA, P, C, K);
-  return bevf_check_launch("bevf_sparse_rows_scatter_add_f32");
+  return bevf_launch("bevf_sparse_rows_scatter_add_f32", sparse_rows_scatter, dim3((unsigned)C, (unsigned)G), dim3(256), (size_t)C * sizeof(int), ST,
+                     S, idx, W, dA, P, C, K);
 }
 extern "C" int bevf_zero_stuff_nhwc_f32(const float* dy, float* out, int N, int Ho, int Wo, int C, int H, int W, int s,
                                         void* stream) {
@@ -826,17 +826,9 @@ extern "C" int bevf_head_tail_bwd_f32(const bevf_head_bwd_desc* d, void* stream)
   const long long total = (long long)d->B * d->P;
   unsigned grid = (unsigned)((total + 255) / 256 > 512 ? 512 : (total + 255) / 256);
   const size_t lds_tiled = lds + (size_t)(256 * (ctot | 1) + 256 * d->hc) * sizeof(float);
-  if (lds_tiled <= 160 * 1024) {                         // tile of 256 pixels fits: the shuffle-free kernel
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_tail_bwd_tiled), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(head_tail_bwd_tiled, dim3(grid), dim3(256), lds_tiled, ST, a);
-    return bevf_check_launch("bevf_head_tail_bwd_f32");
-  }
-  hipLaunchKernelGGL(head_tail_bwd, dim3(grid), dim3(256), lds, ST, a);
-  return bevf_check_launch("bevf_head_tail_bwd_f32");
+  if (lds_tiled <= 160 * 1024)                           // tile of 256 pixels fits: the shuffle-free kernel
+    return bevf_launch("bevf_head_tail_bwd_f32", head_tail_bwd_tiled, dim3(grid), dim3(256), lds_tiled, ST, a);
+  return bevf_launch("bevf_head_tail_bwd_f32", head_tail_bwd, dim3(grid), dim3(256), lds, ST, a);
 }
 extern "C" int bevf_centernet_loss_bwd_f32(const bevf_loss_desc* d, float* const dpred[5], float* scratch2, void* stream) {
   BEVF_REQUIRE(d && d->pred_heatmap && d->tgt_heatmap && d->ind && d->reg_mask && dpred && scratch2, "loss_bwd: null pointer");
@@ -864,8 +856,7 @@ extern "C" int bevf_smallk_wgrad_f32(const float* dy, const float* x, float* dw,
   const int lanes = 256 / Cout;
   int G = (M + lanes - 1) / lanes;
   if (G > 512) G = 512;
-  hipLaunchKernelGGL(smallk_wgrad, dim3(G), dim3(256), (size_t)Cout * K * sizeof(float), ST, dy, x, dw, M, K, Cout);
-  return bevf_check_launch("bevf_smallk_wgrad_f32");
+  return bevf_launch("bevf_smallk_wgrad_f32", smallk_wgrad, dim3(G), dim3(256), (size_t)Cout * K * sizeof(float), ST, dy, x, dw, M, K, Cout);
 }
 extern "C" int bevf_grad_norm_f32(const float* g, size_t n, double* work512, float max_norm, float* out2, void* stream) {
   BEVF_REQUIRE(g && work512 && out2 && n > 0, "grad_norm: bad arguments");

@@ -1,6 +1,7 @@
 // Backward / optimiser kernels around the MFMA convolutions (training step).
 // Everything here is HBM- or latency-bound; 16 B per lane where the layout allows.
 #include "common.h"
+#include "bn_rows.h"
 
 namespace {
 
@@ -30,7 +31,13 @@ __global__ __launch_bounds__(256) void relu_mask(float* __restrict__ dy, const f
 }
 
 // ---- max-pool 3x3 s2 p1 with argmax (first maximum in scan order, as torch) and its gather backward ---------------
-__global__ __launch_bounds__(256) void maxpool_fwd_idx(const float* __restrict__ x, float* __restrict__ y,
+// AFFINE: x is the raw pre-BatchNorm map and the maximum is taken over relu(batchnorm(x)) evaluated on load (the ResNet stem in
+// training): the normalised 64-channel stem map -- the largest activation of the step -- is never written; values and argmax
+// codes are those of bn_apply followed by the plain kernel (BnQuad: the same fma, the same max(t, 0)).
+template <bool AFFINE>
+__global__ __launch_bounds__(256) void maxpool_fwd_idx(const float* __restrict__ x, const float* __restrict__ mean,
+                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                        const float* __restrict__ beta, float* __restrict__ y,
                                                         unsigned char* __restrict__ idx, int N, int H, int W, int C, int Ho,
                                                         int Wo) {
   const int c4 = C >> 2;
@@ -41,6 +48,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_idx(const float* __restrict__
     const int ow = (int)(pix % Wo);
     pix /= Wo;
     const int oh = (int)(pix % Ho), n = (int)(pix / Ho);
+    BnQuad q;
+    if constexpr (AFFINE) q = BnQuad(mean, invstd, gamma, beta, c);
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int best[4] = {0, 0, 0, 0};
     for (int dh = 0; dh < 3; ++dh) {
@@ -49,53 +58,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_idx(const float* __restrict__
       for (int dw = 0; dw < 3; ++dw) {
         const int iw = 2 * ow - 1 + dw;
         if ((unsigned)iw >= (unsigned)W) continue;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + ((size_t)(n * H + ih) * W + iw) * C + c);
+        f32x4 v = *reinterpret_cast<const f32x4*>(x + ((size_t)(n * H + ih) * W + iw) * C + c);
+        if constexpr (AFFINE) v = q.relu_pre(v);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (v[j] > m[j] || (v[j] != v[j])) { m[j] = v[j]; best[j] = dh * 3 + dw; }
-      }
-    }
-    *reinterpret_cast<f32x4*>(y + (size_t)i * 4) = m;
-    *reinterpret_cast<unsigned*>(idx + (size_t)i * 4) =
-        (unsigned)best[0] | ((unsigned)best[1] << 8) | ((unsigned)best[2] << 16) | ((unsigned)best[3] << 24);
-  }
-}
-// max-pool over relu(batchnorm(x)) evaluated on the fly (the ResNet stem in training): the normalised 64-channel stem map -- the
-// largest activation of the step -- is never written; values and argmax codes are those of bn_apply (same fma, same max(t, 0))
-// followed by maxpool_fwd_idx
-__global__ __launch_bounds__(256) void bn_relu_maxpool_idx(const float* __restrict__ x, const float* __restrict__ mean,
-                                                            const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ y,
-                                                            unsigned char* __restrict__ idx, int N, int H, int W, int C, int Ho,
-                                                            int Wo) {
-  const int c4 = C >> 2;
-  const long long total = (long long)N * Ho * Wo * c4;
-  GRID_STRIDE(i, total) {
-    const int c = (int)(i % c4) * 4;
-    long long pix = i / c4;
-    const int ow = (int)(pix % Wo);
-    pix /= Wo;
-    const int oh = (int)(pix % Ho), n = (int)(pix / Ho);
-    float a[4], b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      a[j] = (gamma ? gamma[c + j] : 1.f) * invstd[c + j];
-      b[j] = (beta ? beta[c + j] : 0.f) - mean[c + j] * a[j];
-    }
-    f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    int best[4] = {0, 0, 0, 0};
-    for (int dh = 0; dh < 3; ++dh) {
-      const int ih = 2 * oh - 1 + dh;
-      if ((unsigned)ih >= (unsigned)H) continue;
-      for (int dw = 0; dw < 3; ++dw) {
-        const int iw = 2 * ow - 1 + dw;
-        if ((unsigned)iw >= (unsigned)W) continue;
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + ((size_t)(n * H + ih) * W + iw) * C + c);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float v = fmaxf(fmaf(xv[j], a[j], b[j]), 0.f);
-          if (v > m[j] || (v != v)) { m[j] = v; best[j] = dh * 3 + dw; }
-        }
       }
     }
     *reinterpret_cast<f32x4*>(y + (size_t)i * 4) = m;
@@ -108,29 +75,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd(const float* __restrict__ dy,
                                                     float* __restrict__ dx, int N, int H, int W, int C, int Ho, int Wo) {
   const int c4 = C >> 2;
   const long long total = (long long)N * H * W * c4;
-  GRID_STRIDE(i, total) {                              // gather: every output window that contains this input pixel
-    const int c = (int)(i % c4) * 4;
-    long long pix = i / c4;
-    const int iw = (int)(pix % W);
-    pix /= W;
-    const int ih = (int)(pix % H), n = (int)(pix / H);
-    f32x4 g = {0.f, 0.f, 0.f, 0.f};
-    for (int oh = ih / 2; oh <= (ih + 1) / 2; ++oh) {                          // 2*oh-1 <= ih <= 2*oh+1
-      if (oh >= Ho) continue;
-      const int dh = ih - (2 * oh - 1);
-      for (int ow = iw / 2; ow <= (iw + 1) / 2; ++ow) {
-        if (ow >= Wo) continue;
-        const unsigned code = (unsigned)(dh * 3 + (iw - (2 * ow - 1)));
-        const size_t o = ((size_t)(n * Ho + oh) * Wo + ow) * C + c;
-        const unsigned id4 = *reinterpret_cast<const unsigned*>(idx + o);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(dy + o);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (((id4 >> (8 * j)) & 0xff) == code) g[j] += d[j];
-      }
-    }
-    *reinterpret_cast<f32x4*>(dx + (size_t)i * 4) = g;
-  }
+  GRID_STRIDE(i, total)                                // gather: every output window that contains this input pixel
+    *reinterpret_cast<f32x4*>(dx + (size_t)i * 4) = pool_gather(dy, idx, i / c4, (int)(i % c4) * 4, H, W, C, Ho, Wo);
 }
 
 // ---- bilinear backward (scatter with float atomics; dx zero-filled by the caller) -----------------------------------
@@ -180,8 +126,8 @@ __global__ __launch_bounds__(256) void cam_mean_bwd(const f32x4* __restrict__ dy
 // ---- group max with argmax, and its scatter backward (dx zero-filled by the caller) -----------------------------------
 // stage 1: one workgroup per (group, chunk of GM_CHUNK points): threads own channel quads, rows are read coalesced
 constexpr int GM_CHUNK = 128;
-// AFFINE: the rows are raw pre-BatchNorm values and the maximum is taken over relu(fma(x, a, b)) with a = gamma*invstd,
-// b = beta - mean*a -- bn_apply's own operations, so value and argmax equal those of the materialised activation.
+// AFFINE: the rows are raw pre-BatchNorm values and the maximum is taken over relu(batchnorm(x)) evaluated on load (BnQuad:
+// bn_apply's own operations), so value and argmax equal those of the materialised activation.
 template <bool AFFINE>
 __global__ __launch_bounds__(256) void group_max_partial(const float* __restrict__ x, float* __restrict__ pmax,
                                                           int* __restrict__ pidx, int P, int C, int nchunks,
@@ -191,19 +137,10 @@ __global__ __launch_bounds__(256) void group_max_partial(const float* __restrict
   const int p0 = ch * GM_CHUNK, p1 = (p0 + GM_CHUNK < P) ? p0 + GM_CHUNK : P;
   const int c4 = C >> 2;
   for (int cq = threadIdx.x; cq < c4; cq += 256) {
-    float fa[4] = {1.f, 1.f, 1.f, 1.f}, fb[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (AFFINE) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        fa[j] = (gamma ? gamma[cq * 4 + j] : 1.f) * invstd[cq * 4 + j];
-        fb[j] = (beta ? beta[cq * 4 + j] : 0.f) - mean[cq * 4 + j] * fa[j];
-      }
-    }
+    BnQuad q;
+    if constexpr (AFFINE) q = BnQuad(mean, invstd, gamma, beta, cq * 4);
     auto act = [&](f32x4 v) {
-      if constexpr (AFFINE) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaf(v[j], fa[j], fb[j]), 0.f);
-      }
+      if constexpr (AFFINE) v = q.relu_pre(v);
       return v;
     };
     const float* src = x + ((size_t)g * P + p0) * C + cq * 4;
@@ -675,7 +612,8 @@ extern "C" int bevf_relu_mask_f32(float* dy, const float* y, size_t n, void* str
 extern "C" int bevf_maxpool3x3s2_idx_f32(const float* x, float* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {
   BEVF_REQUIRE(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool_idx: bad arguments (C %% 4)");
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  hipLaunchKernelGGL(maxpool_fwd_idx, dim3(ew_grid((long long)N * Ho * Wo * (C / 4))), dim3(256), 0, ST, x, y, idx, N, H, W, C, Ho, Wo);
+  hipLaunchKernelGGL(maxpool_fwd_idx<false>, dim3(ew_grid((long long)N * Ho * Wo * (C / 4))), dim3(256), 0, ST, x, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, y, idx, N, H, W, C, Ho, Wo);
   return bevf_check_launch("bevf_maxpool3x3s2_idx_f32");
 }
 extern "C" int bevf_bn_relu_maxpool3x3s2_idx_f32(const float* x, const float* mean, const float* invstd, const float* gamma,
@@ -684,7 +622,7 @@ extern "C" int bevf_bn_relu_maxpool3x3s2_idx_f32(const float* x, const float* me
   BEVF_REQUIRE(x && mean && invstd && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0,
                "bn_relu_maxpool_idx: bad arguments (C %% 4)");
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  hipLaunchKernelGGL(bn_relu_maxpool_idx, dim3(ew_grid((long long)N * Ho * Wo * (C / 4))), dim3(256), 0, ST, x, mean, invstd, gamma, beta,
+  hipLaunchKernelGGL(maxpool_fwd_idx<true>, dim3(ew_grid((long long)N * Ho * Wo * (C / 4))), dim3(256), 0, ST, x, mean, invstd, gamma, beta,
                      y, idx, N, H, W, C, Ho, Wo);
   return bevf_check_launch("bevf_bn_relu_maxpool3x3s2_idx_f32");
 }

@@ -1,20 +1,18 @@
-// ResNet stem: 7x7 stride-2 pad-3 convolution of a planar 3-channel image, fused BN + ReLU,
-// on v_mfma_f32_32x32x2_f32.  ref src/encoders.py:154-156.
+// ResNet stem: 7x7 stride-2 pad-3 convolution of a planar 3-channel image, fused BN + ReLU, optionally fused with the 3x3 / stride-2
+// max-pool behind it.  ref src/encoders.py:154-157.
 //
-// One workgroup = TH = 4 output rows x 128 pixels x all 64 channels.  The 3 x (2*TH+5) input
-// rows it needs are staged once in LDS straight from the NCHW image (16-B loads along W,
-// zero-filled outside the image); the whole filter bank sits beside it as [k][channel] (packed
-// once by the host) so the B-operand reads are conflict-free, and is amortised over the rows.
-// The A operand is read element-wise out of the patch:
-//     A[pixel i of row ro][k=(c,kh,kw)] = patch[c][2*ro + kh][2*i + kw + 1]
-// (patch column 0 is image column 2*ow0 - 4, which keeps the 16-B loads aligned).
+// Five forward kernels compute the same convolution; every stage they share is ONE helper below, so "the fused kernel is
+// bit-identical to stem -> max-pool" holds because both sides run the same code (tests/test_gpu_stem_bits.py anchors the bits to the
+// kernels as they were before they shared it):
 //
-// v_mfma_f32_32x32x2_f32 consumes two k per step (lane half h takes one each) and runs at the
-// fp32 VALU rate, so the k loop must not spend VALU on addresses.  The 147 taps are therefore
-// paired so that the h=1 tap is the h=0 tap shifted by a constant: 63 pairs one patch row apart
-// (kh, kh+1), 9 pairs one column apart in the kh=6 row, one pair a channel apart, and the last
-// tap alone against a zero filter row.  Each step's addresses are then "per-group base VGPR
-// (holding the h shift) + compile-time immediate", fully unrolled: 3 ds_read_b32 + 2 MFMA per step.
+//   kernel                    patch staging      filter bank                    MFMA             after the MFMA
+//   stem_conv7x7<TO>          stage_patch        stage_filter_f32               stem_row_mma     BN (+ ReLU), buffer stores
+//   stem_pool7x7              stage_patch        stage_filter_f32               stem_row_mma     bn_relu_hmax3 x 2, PoolRows   (PoolStrip)
+//   stem_conv7x7_bf16mma<TO>  stage_patch_bf16   stage_filter_bf16, load_frags  expand_cols, load_frags, mma_bf16_11   BN (+ ReLU), buffer stores
+//   stem_pool7x7_bf16mma      stage_patch_bf16   stage_filter_bf16, load_frags  expand_cols, load_frags, mma_bf16_11   bn_relu_hmax3, PoolRows (PoolStrip)
+//   stem_pool7x7_bf16v2       two_copies         stage_filter_bf16, load_frags  ds_read_b64 fragments, mma_bf16_11     bn_relu_hmax3, PoolRows (PoolStrip)
+//
+// stem_wgrad (the weight gradient) shares stage_patch and the tile; the max-pool and the filter packing kernels stand alone.
 #include "common.h"
 
 #include <stdlib.h>
@@ -31,6 +29,13 @@ constexpr int PW = 2 * TP + 8;       // patch row pitch in floats (cols 1..261 u
 constexpr int PR = 2 * TH + 5;       // patch rows per input channel
 constexpr int KPAD = 148, NSTEP = 74;
 
+// The fp32 kernels' operand addressing.  v_mfma_f32_32x32x2_f32 consumes two k per step (lane half h takes one each) and runs at the
+// fp32 VALU rate, so the k loop must not spend VALU on addresses.  The A operand is read element-wise out of the patch:
+//     A[pixel i of row ro][k=(c,kh,kw)] = patch[c][2*ro + kh][2*i + kw + 1]
+// (patch column 0 is image column 2*ow0 - 4, which keeps the 16-B loads aligned).  The 147 taps are paired so that the h=1 tap is the
+// h=0 tap shifted by a constant: 63 pairs one patch row apart (kh, kh+1), 9 pairs one column apart in the kh=6 row, one pair a channel
+// apart, and the last tap alone against a zero filter row.  Each step's addresses are then "per-group base VGPR (holding the h shift)
+// + compile-time immediate": stem_step(p) gives step p's two immediates and its group.
 struct StemStep { int a_imm, b_imm, grp; };
 __host__ __device__ constexpr StemStep stem_step(int p) {
   if (p < 63) {                                     // (c,kh,kw) | (c,kh+1,kw), kh even
@@ -46,6 +51,7 @@ __host__ __device__ constexpr StemStep stem_step(int p) {
 }
 
 // Stage the 3 x PR input rows a tile of TH output rows x TP pixels needs into LDS, zero-filled outside the image.
+// One workgroup = TH = 4 output rows x 128 pixels x all 64 channels; the rows are staged once, straight from the NCHW image.
 // patch row (c, pr) <-> image row ih = 2*oh0 - 3 + pr of plane c; patch col <-> iw = 2*ow0 - 4 + col
 __device__ __forceinline__ void stage_patch(const float* __restrict__ x, float* patch, int n, int H, int W, int oh0, int ow0,
                                             int vec_ok, int tid, int lane, int wave) {
@@ -93,6 +99,242 @@ __device__ __forceinline__ void stage_patch(const float* __restrict__ x, float* 
   }
 }
 
+// The fp32 filter bank, pre-packed by the host as [k = c*49+kh*7+kw][co] with a zero row k = 147, -> LDS as it is ([KPAD][64]: the
+// B-operand reads of stem_row_mma are conflict-free), amortised over all rows of the workgroup.  Written for a minimal VALU count
+// (every vector-ALU instruction here queues behind the other workgroup's 64-cycle MFMAs): the lane offset is computed once.
+__device__ __forceinline__ void stage_filter_f32(const float* __restrict__ w, float* wl, int tid) {
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, KPAD * 64 * 4, 0x00020000);
+  const unsigned voff = (unsigned)tid * 16u;
+#pragma unroll
+  for (int it = 0; it < (KPAD * 16 + 255) / 256; ++it) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, voff, it * 4096, 0);
+    if (it * 256 + 255 < KPAD * 16 || tid < KPAD * 16 - it * 256)
+      *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(wl) + tid * 16 + it * 4096) = v;
+  }
+}
+
+// One output row of a wave: 32 pixels x 64 channels (acc0: channels 0..31, acc1: 32..63) over the 74 steps of stem_step, fully
+// unrolled: 3 ds_read_b32 + 2 MFMA per step.  pa[grp] / pb[grp] are the lane's patch / filter bases of each pairing group (they hold
+// the h shift; group 3 reads the filter through pb[1]).  Software pipeline over chunks of 4 steps: the 12 operand reads of chunk c+1
+// are issued before the 8 MFMAs of chunk c (two register sets, statically indexed), so LDS latency hides under MFMA.  The
+// accumulators are started by the first MFMA (C = 0).
+__device__ __forceinline__ void stem_row_mma(const char* const (&pa)[4], const char* const (&pb)[3], f32x16& acc0, f32x16& acc1) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  constexpr int CH = 4, NCH = (NSTEP + CH - 1) / CH;
+  float av[2][CH], b0v[2][CH], b1v[2][CH];
+  auto load_chunk = [&](int cidx, int set) {
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      const int p = cidx * CH + u;
+      if (p < NSTEP) {
+        const StemStep st = stem_step(p);
+        const char* const bp = pb[st.grp == 3 ? 1 : st.grp];
+        av[set][u] = *reinterpret_cast<const float*>(pa[st.grp] + st.a_imm);
+        b0v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm);
+        b1v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm + 128);
+      }
+    }
+  };
+  load_chunk(0, 0);
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    if (c + 1 < NCH) load_chunk(c + 1, (c + 1) & 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < CH; ++u) {
+      if (c * CH + u < NSTEP) {
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b0v[c & 1][u], c == 0 && u == 0 ? zero : acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b1v[c & 1][u], c == 0 && u == 0 ? zero : acc1, 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- the pooling kernels' shared stages --------------------------------------------------------------------------------------
+// A pooling workgroup streams DOWN the image: it owns a strip of TPS = 120 new stem columns (122 computed: +1.7 %; 60 pooled) and a
+// segment of pooled rows (sized on the host, see pool_segments), and computes its stem rows four at a time.  It pools in registers:
+//   * columns: the four 32-pixel wave tiles of a row start WPX = 30 pixels apart -- two pixels shared with the neighbour -- so the
+//     three columns of every window a wave owns (centres at its local even pixels 2..30) are its own: no exchange between waves;
+//   * rows: the horizontal maxima of the last two stem rows stay in registers; every odd stem row 2p+1 completes pooled row p.
+// Rows / columns outside the stem map count as 0 (= -inf after a ReLU).
+constexpr int WPX = 30, TPS = 4 * WPX;
+
+// The block's strip and segment: image n, first stem column ow0, pooled rows [p0, p1), stem rows [r_first, r_last].
+struct PoolStrip {
+  int n, ow0, p0, p1, r_first, r_last;
+  __device__ __forceinline__ PoolStrip(int block, int tilesW, int nseg, int rows_per_seg, int Hp) {
+    const int tw = block % tilesW, seg = (block / tilesW) % nseg;
+    n = block / (tilesW * nseg);
+    ow0 = tw * TPS - 2;                                            // even: the patch's 16-byte column loads stay aligned
+    p0 = seg * rows_per_seg;
+    p1 = p0 + rows_per_seg < Hp ? p0 + rows_per_seg : Hp;
+    r_first = 2 * p0 - 1;
+    r_last = 2 * (p1 - 1) + 1;
+  }
+  // every stem column the four wave tiles touch exists (workgroup-uniform)
+  __device__ __forceinline__ bool interior(int Wo) const { return ow0 >= 0 && ow0 + 3 * WPX + 32 <= Wo; }
+  // the pooled row of this segment that stem row oh completes (oh = 2p+1), or -1 (uniform)
+  __device__ __forceinline__ int completes(int oh) const {
+    const int pr = (oh - 1) >> 1;
+    return ((oh & 1) && pr >= p0 && pr < p1) ? pr : -1;
+  }
+};
+
+// One accumulator of a lane (16 values: pixels 8g + 4h + {0..3} of its wave tile, one channel) -> BatchNorm + ReLU exactly as the
+// unpooled kernels store them (before any bf16 rounding), 0 where the stem row or column does not exist -> the 8 horizontal 3-maxima
+// at the window centres rc = 0, 2, .., 14 (registers 4g and 4g+2).  col0 is the stem column of register 0; no_pred (uniform) says
+// that every column exists, which spares the per-element predicate.  The left neighbour of centre 4g lives in the other lane half:
+// register 4g+3 of half 0 for h = 1, register 4g-1 of half 1 for h = 0 (g = 0, h = 0: the neighbour wave's window, never stored).
+__device__ __forceinline__ void bn_relu_hmax3(const f32x16& acc, float sc, float sh, bool row_ok, int col0, int Wo, bool no_pred, int h,
+                                              float (&hm)[8]) {
+  float v[16];
+  if (row_ok && no_pred) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) v[r] = fmaxf(fmaf(acc[r], sc, sh), 0.f);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ok = row_ok && (unsigned)(col0 + (r & 3) + 8 * (r >> 2)) < (unsigned)Wo;
+      v[r] = ok ? fmaxf(fmaf(acc[r], sc, sh), 0.f) : 0.f;
+    }
+  }
+  float xl[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) xl[g] = __shfl_xor(v[4 * g + 3], 32);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float l0 = h ? xl[g] : (g > 0 ? xl[g - 1] : 0.f);
+    hm[2 * g] = fmaxf(fmaxf(l0, v[4 * g]), v[4 * g + 1]);
+    hm[2 * g + 1] = fmaxf(fmaxf(v[4 * g + 1], v[4 * g + 2]), v[4 * g + 3]);
+  }
+}
+
+// The vertical half of the pooling for 8 window centres: the horizontal maxima of the last two stem rows (0 before the first row).
+struct PoolRows {
+  float prev1[8], prev2[8];
+  __device__ __forceinline__ PoolRows() {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { prev1[i] = 0.f; prev2[i] = 0.f; }
+  }
+  // the pooled value of centre c once the horizontal maxima hm of stem row 2p+1 are there
+  __device__ __forceinline__ float vmax3(const float (&hm)[8], int c) const { return fmaxf(fmaxf(prev2[c], prev1[c]), hm[c]); }
+  // after every stem row
+  __device__ __forceinline__ void roll(const float (&hm)[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { prev2[i] = prev1[i]; prev1[i] = hm[i]; }
+  }
+};
+
+// ---- the bf16-MFMA kernels' shared stages -------------------------------------------------------------------------------------
+// v_mfma_f32_32x32x16_bf16 wants 8 consecutive k per lane: k = (c*7 + kh)*8 + kw (kw = 7 and k >= 168 meet zero filter columns;
+// 176 = 11 MFMA k-groups).  The bf16 MFMA is 16x faster per flop than the fp32 one, so these kernels can afford vector-ALU / LDS work
+// around it that the fp32 stem cannot.
+constexpr int KP = 176;                  // padded K (bf16 elements)
+constexpr int CP = 368;                  // row pitch in bytes of the column / weight tiles (176*2 + 16: conflict-free b128)
+constexpr int HP = 64;                   // pixels per expansion (half a tile row)
+constexpr int NG = KP / 16;              // k-groups = MFMAs per wave tile
+
+typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4s __attribute__((ext_vector_type(4)));
+
+// The bf16 filter bank [64][176] (stem_pack_bf16_kernel) -> LDS rows of pitch CP.  It only passes through LDS: each wave keeps its
+// fragments in registers (load_frags), so the bank shares the storage of what the kernel stages next.
+__device__ __forceinline__ void stage_filter_bf16(const __bf16* __restrict__ w, char* wt, int tid) {
+  for (int i = tid; i < 64 * (KP / 8); i += 256) {
+    const int ch = i / (KP / 8), q = i - ch * (KP / 8);
+    *reinterpret_cast<u32x4*>(wt + ch * CP + q * 16) = *reinterpret_cast<const u32x4*>(w + (size_t)ch * KP + q * 8);
+  }
+}
+
+// A wave's 11 fragments out of a tile of pitch CP, fragments first so that the MFMAs run back to back: rd = tile + row * CP + h * 16
+// with row = the lane's channel (filter bank -> bfrag, read once per workgroup) or pixel (column tile -> afrag).
+__device__ __forceinline__ void load_frags(const char* rd, bf16x8s (&frag)[NG]) {
+#pragma unroll
+  for (int g = 0; g < NG; ++g) frag[g] = *reinterpret_cast<const bf16x8s*>(rd + g * 32);
+}
+
+// The 11-group MFMA chain of one 32 pixel x 32 channel wave tile, started by the first MFMA (C = 0).
+__device__ __forceinline__ f32x16 mma_bf16_11(const bf16x8s (&afrag)[NG], const bf16x8s (&bfrag)[NG]) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 acc;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[g], bfrag[g], g == 0 ? zero : acc, 0, 0, 0);
+  return acc;
+}
+
+// The patch of stage_patch as bf16 ([3][PR][PW]; patch row (c, pr) <-> image row 2*oh0 - 3 + pr, patch col <-> iw = 2*ow0 - 4 + col):
+// one patch row per wave and pass, 16-byte loads that the descriptor zero-fills outside the image row; element by element when
+// the rows are not 16-byte aligned (!vec_ok).
+__device__ __forceinline__ void stage_patch_bf16(const float* __restrict__ x, char* patch, int n, int H, int W, int oh0, int ow0,
+                                                 bool vec_ok, int lane, int wave) {
+  const float* img = x + (size_t)n * 3 * H * W;
+  const int iw0 = 2 * ow0 - 4;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  for (int r = wv; r < 3 * PR; r += 4) {
+    const int c = r / PR, pr = r - c * PR;
+    const int ih = 2 * oh0 - 3 + pr;
+    const bool row_ok = (unsigned)ih < (unsigned)H;                      // wave-uniform
+    const float* row = img + ((size_t)c * H + (row_ok ? ih : 0)) * W;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, row_ok ? W * 4 : 0, 0x00020000);
+    for (int c4 = lane; c4 < PW / 4; c4 += 64) {
+      const int iw = iw0 + 4 * c4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (vec_ok) {
+        v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, iw >= 0 ? (unsigned)(iw * 4) : 0x80000000u, 0, 0));
+      } else if (row_ok) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((unsigned)(iw + j) < (unsigned)W) v[j] = row[iw + j];
+      }
+      bf16x4s b;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = (__bf16)v[j];
+      *reinterpret_cast<bf16x4s*>(patch + ((size_t)r * PW + 4 * c4) * 2) = b;
+    }
+  }
+}
+
+// The strided patch cannot supply 8 consecutive k, so per half output row (HP = 64 pixels starting at tile pixel px0 of output row
+// ro) the workgroup expands the bf16 patch into an explicit column tile col[pixel][k] in LDS: four aligned dword reads + three
+// v_alignbit per (pixel, c, kh) item and one 16-byte write (kw = 6 is followed by the zero column kw = 7); all window reads first,
+// then the shifts and the writes.  Item i = tid + 256*j <-> (pixel xp = i & 63, k-row r = xr0 + 4*j = i >> 6, r < 21): xp and the
+// r-step are fixed per thread (xr0 <= 3: the first five items exist for every thread, which keeps their reads free of branches and
+// ahead of the shifts; the sixth only for xr0 = 0).  Columns 168..175 are zeroed once by the kernel.
+__device__ __forceinline__ void expand_cols(const char* patch, char* col, int ro, int px0, int xp, int xr0) {
+  unsigned d[6][4];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const int r = xr0 + 4 * j;
+    if (j < 5 || r < 21) {                                     // (decided at compile time for all but the sixth item)
+      const int c = r / 7, kh = r - c * 7;
+      const unsigned* src = reinterpret_cast<const unsigned*>(patch + ((size_t)(c * PR + 2 * ro + kh) * PW + 2 * (px0 + xp)) * 2);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) d[j][q] = src[q];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const int r = xr0 + 4 * j;
+    if (j < 5 || r < 21) {                                     // (decided at compile time for all but the sixth item)
+      u32x4 o;
+      o[0] = __builtin_amdgcn_alignbit(d[j][1], d[j][0], 16);
+      o[1] = __builtin_amdgcn_alignbit(d[j][2], d[j][1], 16);
+      o[2] = __builtin_amdgcn_alignbit(d[j][3], d[j][2], 16);
+      o[3] = d[j][3] >> 16;                                  // kw = 6, then the zero column kw = 7
+      *reinterpret_cast<u32x4*>(col + xp * CP + r * 16) = o;
+    }
+  }
+}
+
+// stem_pool7x7_bf16v2 keeps the patch as TWO bf16 copies shifted by 1 and by 3 elements: copy 0 holds patch column e + 1 at element e,
+// copy 1 column e + 3.  v = patch columns 4 c4 .. + 3, u = the next four -> elements 4 c4 .. 4 c4 + 3 of both copies (three v_cvt_pk).
+__device__ __forceinline__ void two_copies(const f32x4& v, const f32x4& u, bf16x4s& a0, bf16x4s& a1) {
+  a0[0] = (__bf16)v[1]; a0[1] = (__bf16)v[2]; a0[2] = (__bf16)v[3]; a0[3] = (__bf16)u[0];
+  a1[0] = a0[2]; a1[1] = a0[3]; a1[2] = (__bf16)u[1]; a1[3] = (__bf16)u[2];
+}
+
+// ---- fp32 stem: stage_filter_f32 + stage_patch, then stem_row_mma per output row; BN (+ ReLU) and buffer stores ---------------
 template <typename TO>
 __global__ __launch_bounds__(256) void stem_conv7x7(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ scale,
@@ -104,24 +346,11 @@ __global__ __launch_bounds__(256) void stem_conv7x7(const float* __restrict__ x,
   float* patch = smem + KPAD * 64;       // [3][PR][PW]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  stage_filter_f32(w, wl, tid);          // first: its loads do not wait for the tile arithmetic
   const int tw = blockIdx.x % tilesW;
   const int th = (blockIdx.x / tilesW) % tilesH;
   const int n = blockIdx.x / (tilesW * tilesH);
   const int ow0 = tw * TP, oh0 = th * TH;
-
-  // Staging is written for a minimal VALU count (every vector-ALU instruction here queues behind the other
-  // workgroup's 64-cycle MFMAs): per-lane offsets are computed once, rows advance on the scalar unit.
-  // filter bank, pre-packed by the host as [k = c*49+kh*7+kw][co] with a zero row k = 147
-  {
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, KPAD * 64 * 4, 0x00020000);
-    const unsigned voff = (unsigned)tid * 16u;
-#pragma unroll
-    for (int it = 0; it < (KPAD * 16 + 255) / 256; ++it) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, voff, it * 4096, 0);
-      if (it * 256 + 255 < KPAD * 16 || tid < KPAD * 16 - it * 256)
-        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(wl) + tid * 16 + it * 4096) = v;
-    }
-  }
   stage_patch(x, patch, n, H, W, oh0, ow0, vec_ok, tid, lane, wave);
   __syncthreads();
 
@@ -138,39 +367,8 @@ __global__ __launch_bounds__(256) void stem_conv7x7(const float* __restrict__ x,
     if (oh >= Ho) break;
     const char* const ab = reinterpret_cast<const char*>(patch) + (2 * ro * PW + 2 * pix) * 4;
     const char* const pa[4] = {ab + h * PW * 4, ab + h * 4, ab + h * PR * PW * 4, ab};
-    f32x16 acc0, acc1;                               // started by the first MFMA (C = 0)
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // software pipeline over chunks of 4 steps: the 12 operand reads of chunk c+1 are issued before
-    // the 8 MFMAs of chunk c (two register sets, statically indexed), so LDS latency hides under MFMA
-    constexpr int CH = 4, NCH = (NSTEP + CH - 1) / CH;
-    float av[2][CH], b0v[2][CH], b1v[2][CH];
-    auto load_chunk = [&](int cidx, int set) {
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        const int p = cidx * CH + u;
-        if (p < NSTEP) {
-          const StemStep st = stem_step(p);
-          const char* const bp = pb[st.grp == 3 ? 1 : st.grp];
-          av[set][u] = *reinterpret_cast<const float*>(pa[st.grp] + st.a_imm);
-          b0v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm);
-          b1v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm + 128);
-        }
-      }
-    };
-    load_chunk(0, 0);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      if (c + 1 < NCH) load_chunk(c + 1, (c + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < CH; ++u) {
-        if (c * CH + u < NSTEP) {
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b0v[c & 1][u], c == 0 && u == 0 ? zero : acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b1v[c & 1][u], c == 0 && u == 0 ? zero : acc1, 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    f32x16 acc0, acc1;
+    stem_row_mma(pa, pb, acc0, acc1);
     // epilogue: column j = lane&31 -> channel, row i -> pixel wave*32 + i.  Buffer stores: the lane offset is fixed,
     // the pixel offsets are instruction immediates, and pixels past the end of the row fall outside the descriptor.
     TO* const ywave = y + ((size_t)(n * Ho + oh) * Wo + ow0 + wv32) * 64;
@@ -204,19 +402,9 @@ __global__ __launch_bounds__(256) void stem_conv7x7(const float* __restrict__ x,
 // ---- stem + 3x3/s2 max-pool in one kernel (inference, fp32): the 64-channel stem map never reaches HBM -------------------
 // ref src/encoders.py:154-157 (conv1, bn1, relu, maxpool).  The stem output is the largest activation of the whole path
 // (4.4 GB at 48 images of 900x1600); written and read back it costs the separate max-pool 1 ms of pure HBM streaming.
-// Here a workgroup streams DOWN the image: it owns a strip of stem columns and a segment of pooled rows, computes its
-// stem rows four at a time exactly like stem_conv7x7 (same patch staging, same MFMA schedule, same fma / max, so the
-// result is bit-identical to stem -> max-pool), and pools in registers:
-//   * columns: wave w computes stem pixels [30w, 30w+32) of the strip -- two pixels shared with its neighbour -- so the
-//     three columns of every window it owns (centres at its local even pixels 2..30) are its own: no exchange between
-//     waves.  In the 32x32 accumulator layout a lane holds pixels 8g+4h+{0..3}; the window centres are its registers
-//     4g and 4g+2, the only value living in the other lane half (the left neighbour of 4g) comes with four shuffles;
-//   * rows: the horizontal maxima of the last two stem rows stay in registers; every odd stem row 2p+1 completes pooled
-//     row p.  Rows / columns outside the stem map count as 0 (= -inf after a ReLU).
-// A strip is 120 new stem columns (122 computed: +1.7 %), pooled 60; segments of pooled rows are sized on the host so
-// that the grid fills whole rounds of 512 resident workgroups.
-constexpr int WPX = 30, TPS = 4 * WPX;
-
+// A PoolStrip workgroup: stage_filter_f32 once, then per chunk of four stem rows stage_patch, and per row stem_row_mma exactly like
+// stem_conv7x7 with wave w on stem pixels [30w, 30w+32) of the strip, bn_relu_hmax3 per accumulator, and on every odd row the
+// vertical maxima stored as 128-byte channel rows.
 __global__ __launch_bounds__(256) void stem_pool7x7(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ scale, const float* __restrict__ shift,
                                                      float* __restrict__ y, int H, int W, int Ho, int Wo, int Hp, int Wp,
@@ -225,120 +413,50 @@ __global__ __launch_bounds__(256) void stem_pool7x7(const float* __restrict__ x,
   float* wl = smem;                      // [KPAD][64]
   float* patch = smem + KPAD * 64;       // [3][PR][PW]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = blockIdx.x % tilesW;
-  const int seg = (blockIdx.x / tilesW) % nseg;
-  const int n = blockIdx.x / (tilesW * nseg);
-  const int ow0 = tw * TPS - 2;                                    // even: the patch's 16-byte column loads stay aligned
-  const int p0 = seg * rows_per_seg, p1 = p0 + rows_per_seg < Hp ? p0 + rows_per_seg : Hp;
-  const int r_first = 2 * p0 - 1, r_last = 2 * (p1 - 1) + 1;       // stem rows this segment needs
-  {
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, KPAD * 64 * 4, 0x00020000);
-    const unsigned voff = (unsigned)tid * 16u;
-#pragma unroll
-    for (int it = 0; it < (KPAD * 16 + 255) / 256; ++it) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, voff, it * 4096, 0);
-      if (it * 256 + 255 < KPAD * 16 || tid < KPAD * 16 - it * 256)
-        *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(wl) + tid * 16 + it * 4096) = v;
-    }
-  }
+  const PoolStrip s(blockIdx.x, tilesW, nseg, rows_per_seg, Hp);
+  stage_filter_f32(w, wl, tid);
   const int h = lane >> 5, l31 = lane & 31;
   const int wv = __builtin_amdgcn_readfirstlane(wave);
   const int pix = wv * WPX + l31;                                  // stem pixel of the strip this lane feeds to the MFMA
   const float sc0 = scale[l31], sh0 = shift[l31], sc1 = scale[l31 + 32], sh1 = shift[l31 + 32];
   const char* const bb = reinterpret_cast<const char*>(wl) + l31 * 4;
   const char* const pb[3] = {bb + h * 7 * 256, bb + h * 256, bb + h * 49 * 256};
-  const int col0 = ow0 + wv * WPX + 4 * h;                         // stem column of register 0 of this lane
-  const bool edge_cols = ow0 < 0 || ow0 + TPS + 2 > Wo;            // workgroup-uniform
-  // pooled column of centre register rc = 2c: (col0 + (rc&3) + 8*(rc>>2)) / 2
-  float prev1[16], prev2[16];                                      // horizontal maxima of the last two stem rows: [acc][centre]
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { prev1[i] = 0.f; prev2[i] = 0.f; }
+  const int col0 = s.ow0 + wv * WPX + 4 * h;                       // stem column of register 0 of this lane
+  const bool interior = s.interior(Wo);
+  PoolRows rows[2];                                                // per accumulator
 
-  for (int oh0 = r_first; oh0 <= r_last; oh0 += TH) {
+  for (int oh0 = s.r_first; oh0 <= s.r_last; oh0 += TH) {
     __syncthreads();                                               // the previous chunk's patch is fully consumed
-    stage_patch(x, patch, n, H, W, oh0, ow0, vec_ok, tid, lane, wave);
+    stage_patch(x, patch, s.n, H, W, oh0, s.ow0, vec_ok, tid, lane, wave);
     __syncthreads();
     for (int ro = 0; ro < TH; ++ro) {
       const int oh = oh0 + ro;
-      if (oh > r_last) break;
+      if (oh > s.r_last) break;
       const char* const ab = reinterpret_cast<const char*>(patch) + (2 * ro * PW + 2 * pix) * 4;
       const char* const pa[4] = {ab + h * PW * 4, ab + h * 4, ab + h * PR * PW * 4, ab};
       f32x16 acc0, acc1;
-      const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      constexpr int CH = 4, NCH = (NSTEP + CH - 1) / CH;
-      float av[2][CH], b0v[2][CH], b1v[2][CH];
-      auto load_chunk = [&](int cidx, int set) {
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-          const int p = cidx * CH + u;
-          if (p < NSTEP) {
-            const StemStep st = stem_step(p);
-            const char* const bp = pb[st.grp == 3 ? 1 : st.grp];
-            av[set][u] = *reinterpret_cast<const float*>(pa[st.grp] + st.a_imm);
-            b0v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm);
-            b1v[set][u] = *reinterpret_cast<const float*>(bp + st.b_imm + 128);
-          }
-        }
-      };
-      load_chunk(0, 0);
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        if (c + 1 < NCH) load_chunk(c + 1, (c + 1) & 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-          if (c * CH + u < NSTEP) {
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b0v[c & 1][u], c == 0 && u == 0 ? zero : acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c & 1][u], b1v[c & 1][u], c == 0 && u == 0 ? zero : acc1, 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // BatchNorm + ReLU exactly as stem_conv7x7 stores them; stem rows / columns that do not exist count as 0
+      stem_row_mma(pa, pb, acc0, acc1);
       const bool row_ok = (unsigned)oh < (unsigned)Ho;             // uniform
-      float v0[16], v1[16];
+      float hm[2][8];
+      bn_relu_hmax3(acc0, sc0, sh0, row_ok, col0, Wo, interior, h, hm[0]);
+      bn_relu_hmax3(acc1, sc1, sh1, row_ok, col0, Wo, interior, h, hm[1]);
+      const int pr = s.completes(oh);
+      if (pr >= 0) {
+        float* const yrow = y + ((size_t)(s.n * Hp + pr) * Wp) * 64 + l31;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const bool ok = row_ok && (!edge_cols || (unsigned)(col0 + (r & 3) + 8 * (r >> 2)) < (unsigned)Wo);
-        v0[r] = ok ? fmaxf(fmaf(acc0[r], sc0, sh0), 0.f) : 0.f;
-        v1[r] = ok ? fmaxf(fmaf(acc1[r], sc1, sh1), 0.f) : 0.f;
-      }
-      // horizontal 3-max at the centres rc = 0, 2, .., 14 (pixel 8g + 4h + {0, 2}); the left neighbour of rc = 4g lives in
-      // the other lane half: register 4g+3 of half 0 for h = 1, register 4g-1 of half 1 for h = 0 (g = 0, h = 0: no centre)
-      float hm[16];
-      float x0[4], x1[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        x0[g] = __shfl_xor(v0[4 * g + 3], 32);
-        x1[g] = __shfl_xor(v1[4 * g + 3], 32);
-      }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float l0 = h ? x0[g] : (g > 0 ? x0[g - 1] : 0.f), l1 = h ? x1[g] : (g > 0 ? x1[g - 1] : 0.f);
-        hm[2 * g] = fmaxf(fmaxf(l0, v0[4 * g]), v0[4 * g + 1]);
-        hm[2 * g + 1] = fmaxf(fmaxf(v0[4 * g + 1], v0[4 * g + 2]), v0[4 * g + 3]);
-        hm[8 + 2 * g] = fmaxf(fmaxf(l1, v1[4 * g]), v1[4 * g + 1]);
-        hm[8 + 2 * g + 1] = fmaxf(fmaxf(v1[4 * g + 1], v1[4 * g + 2]), v1[4 * g + 3]);
-      }
-      if (oh & 1) {                                                // stem row 2p+1 completes pooled row p (uniform branch)
-        const int pr = (oh - 1) >> 1;
-        if (pr >= p0 && pr < p1) {
-          float* const yrow = y + ((size_t)(n * Hp + pr) * Wp) * 64 + l31;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const int rc = 2 * c;
-            const int col = col0 + (rc & 3) + 8 * (rc >> 2);       // stem column of the window centre (even)
-            const bool own = (h != 0 || c != 0) && col >= 0 && (col >> 1) < Wp;   // (h = 0, rc = 0 is the neighbour's window)
-            if (own) {
-              float* const dst = yrow + (size_t)(col >> 1) * 64;
-              dst[0] = fmaxf(fmaxf(prev2[c], prev1[c]), hm[c]);
-              dst[32] = fmaxf(fmaxf(prev2[8 + c], prev1[8 + c]), hm[8 + c]);
-            }
+        for (int c = 0; c < 8; ++c) {
+          const int rc = 2 * c;
+          const int col = col0 + (rc & 3) + 8 * (rc >> 2);         // stem column of the window centre (even)
+          const bool own = (h != 0 || c != 0) && col >= 0 && (col >> 1) < Wp;   // (h = 0, rc = 0 is the neighbour's window)
+          if (own) {
+            float* const dst = yrow + (size_t)(col >> 1) * 64;
+            dst[0] = rows[0].vmax3(hm[0], c);
+            dst[32] = rows[1].vmax3(hm[1], c);
           }
         }
       }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { prev2[i] = prev1[i]; prev1[i] = hm[i]; }
+      rows[0].roll(hm[0]);
+      rows[1].roll(hm[1]);
     }
   }
 }
@@ -466,21 +584,368 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc(const T* __restrict__ x
   store16(y + (size_t)i * V, m);
 }
 
+// ---- bf16 stem (bf16-storage models) on the bf16 MFMA: stage_filter_bf16 + stage_patch_bf16, the wave's filter fragments
+// (load_frags), then per half output row expand_cols, load_frags and mma_bf16_11; BN (+ ReLU) and buffer stores.  Wave (mi, ni)
+// takes pixels 32 mi .. and channels 32 ni .. of the half row.  Even with the expansion the stem drops from ~24 % to a few % of the
+// bf16 step.
+template <typename TO>
+__global__ __launch_bounds__(256) void stem_conv7x7_bf16mma(const float* __restrict__ x, const __bf16* __restrict__ w,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             TO* __restrict__ y, int H, int W, int Ho, int Wo, int tilesW,
+                                                             int tilesH, int relu) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // The filter bank shares the column tile's storage: 44 KB per workgroup, 3 workgroups per CU.
+  char* const col = reinterpret_cast<char*>(smem);                 // [HP][CP]   bf16 column tile
+  char* const wt = col;                                            // [64][CP]   bf16 filter, k contiguous per channel (transient)
+  char* const patch = col + HP * CP;                               // [3][PR][PW] bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  stage_filter_bf16(w, wt, tid);                                   // first: its loads do not wait for the tile arithmetic
+  const int tw = blockIdx.x % tilesW;
+  const int th = (blockIdx.x / tilesW) % tilesH;
+  const int n = blockIdx.x / (tilesW * tilesH);
+  const int ow0 = tw * TP, oh0 = th * TH;
+  stage_patch_bf16(x, patch, n, H, W, oh0, ow0, (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0), lane, wave);
+  __syncthreads();
+
+  const int h = lane >> 5, l31 = lane & 31;
+  const int mi = wave >> 1, ni = wave & 1;                         // wave tile: 32 pixels x 32 channels of the half row
+  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
+  const char* const a_rd = col + (mi * 32 + l31) * CP + h * 16;
+  bf16x8s bfrag[NG];
+  load_frags(wt + (ni * 32 + l31) * CP + h * 16, bfrag);
+  __syncthreads();                                                 // filter bank consumed: its storage becomes the column tile
+  if (tid < HP) *reinterpret_cast<u32x4*>(col + tid * CP + 168 * 2) = u32x4{0u, 0u, 0u, 0u};   // zero columns 168..175, once
+  const int xp = tid & (HP - 1), xr0 = tid >> 6;                   // this thread's expand_cols items
+
+  for (int ro = 0; ro < TH; ++ro) {
+    const int oh = oh0 + ro;
+    if (oh >= Ho) break;
+    for (int hf = 0; hf < TP / HP; ++hf) {
+      if (ow0 + hf * HP >= Wo) break;
+      expand_cols(patch, col, ro, hf * HP, xp, xr0);
+      __syncthreads();
+      bf16x8s afrag[NG];
+      load_frags(a_rd, afrag);
+      const f32x16 acc = mma_bf16_11(afrag, bfrag);
+      // ---- epilogue: rows i = pixel, column j = channel ------------------------------------------------------
+      const int px0 = ow0 + hf * HP + mi * 32;
+      const int left = Wo - px0;
+      TO* const ybase = y + ((size_t)(n * Ho + oh) * Wo + px0) * 64 + ni * 32;
+      const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
+          ybase, 0, left > 0 ? ((left > 32 ? 32 : left) * 64 - ni * 32) * (int)sizeof(TO) : 0, 0x00020000);
+      const unsigned lane_off = (unsigned)((4 * h * 64 + l31) * (int)sizeof(TO));
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ioff = ((r & 3) + 8 * (r >> 2)) * 64 * (int)sizeof(TO);
+        float v = fmaf(acc[r], sc, sh);
+        if (relu) v = fmaxf(v, 0.f);
+        if constexpr (sizeof(TO) == 4)
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, lane_off + ioff, 0, 0);
+        else
+          __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), ry, lane_off + ioff, 0, 0);
+      }
+      __syncthreads();                                             // column tile free for the next expansion
+    }
+  }
+}
+
+constexpr size_t kStemBf16Lds = (size_t)HP * CP + (size_t)3 * PR * PW * 2;
+
+// ---- bf16 stem + 3x3/s2 max-pool in one kernel (bf16-storage inference): the PoolStrip streaming of stem_pool7x7 on the stages of
+// stem_conv7x7_bf16mma.  Per stem row it runs two half rows of 62 pixels (the column tile still has 64 rows; wave (mi, ni) takes pixels
+// 30 mi .. 30 mi + 31 of the half and channels 32 ni ..), so the four 32-pixel wave tiles of a row again start 30 pixels apart.
+// max commutes with the (monotonic) bf16 rounding and a missing neighbour counts as 0 after the ReLU, so the result is
+// bit-identical to bevf_stem_conv7x7_bf16mma followed by bevf_maxpool3x3s2_nhwc_bf16 -- without the 2.2 GB bf16 stem map.
+// Kept behind BEVF_STEM_BF16_EXPAND for A/B against stem_pool7x7_bf16v2.
+__global__ __launch_bounds__(256) void stem_pool7x7_bf16mma(const float* __restrict__ x, const __bf16* __restrict__ w,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             __bf16* __restrict__ y, int H, int W, int Ho, int Wo, int Hp, int Wp,
+                                                             int tilesW, int nseg, int rows_per_seg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* const col = reinterpret_cast<char*>(smem);                 // [HP][CP]   bf16 column tile
+  char* const wt = col;                                            // [64][CP]   bf16 filter (transient)
+  char* const patch = col + HP * CP;                               // [3][PR][PW] bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PoolStrip s(blockIdx.x, tilesW, nseg, rows_per_seg, Hp);
+  stage_filter_bf16(w, wt, tid);
+  __syncthreads();
+  const int h = lane >> 5, l31 = lane & 31;
+  const int mi = wave >> 1, ni = wave & 1;
+  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
+  const char* const a_rd = col + (mi * WPX + l31) * CP + h * 16;
+  bf16x8s bfrag[NG];
+  load_frags(wt + (ni * 32 + l31) * CP + h * 16, bfrag);
+  __syncthreads();                                                 // filter bank consumed: its storage becomes the column tile
+  if (tid < HP) *reinterpret_cast<u32x4*>(col + tid * CP + 168 * 2) = u32x4{0u, 0u, 0u, 0u};
+  const int xp = tid & (HP - 1), xr0 = tid >> 6;
+  const bool vec_ok = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
+  PoolRows rows[2];                                                // per half row
+
+  for (int oh0 = s.r_first; oh0 <= s.r_last; oh0 += TH) {
+    __syncthreads();                                               // the previous chunk's patch is fully consumed
+    stage_patch_bf16(x, patch, s.n, H, W, oh0, s.ow0, vec_ok, lane, wave);
+    __syncthreads();
+    for (int ro = 0; ro < TH; ++ro) {
+      const int oh = oh0 + ro;
+      if (oh > s.r_last) break;
+      const bool row_ok = (unsigned)oh < (unsigned)Ho;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        if (s.ow0 + hf * 2 * WPX >= Wo) break;                     // (uniform) nothing of this half exists
+        expand_cols(patch, col, ro, hf * 2 * WPX, xp, xr0);
+        __syncthreads();
+        bf16x8s afrag[NG];
+        load_frags(a_rd, afrag);
+        const f32x16 acc = mma_bf16_11(afrag, bfrag);
+        const int col0 = s.ow0 + hf * 2 * WPX + mi * WPX + 4 * h;  // stem column of register 0 of this lane
+        float hm[8];
+        bn_relu_hmax3(acc, sc, sh, row_ok, col0, Wo, false, h, hm);
+        const int pr = s.completes(oh);
+        if (pr >= 0) {
+          __bf16* const yrow = y + ((size_t)(s.n * Hp + pr) * Wp) * 64 + ni * 32 + l31;
+#pragma unroll
+          for (int c = 0; c < 8; ++c) {
+            const int rc = 2 * c;
+            const int cc = col0 + (rc & 3) + 8 * (rc >> 2);        // stem column of the window centre (even)
+            const bool own = (h != 0 || c != 0) && cc >= 0 && (cc >> 1) < Wp;
+            if (own) yrow[(size_t)(cc >> 1) * 64] = (__bf16)rows[hf].vmax3(hm, c);
+          }
+        }
+        rows[hf].roll(hm);
+        __syncthreads();                                           // column tile free for the next expansion
+      }
+    }
+  }
+}
+
+// ---- the same fused bf16 stem + max-pool WITHOUT the column-tile expansion (the default) ------------------------------------------
+// stem_pool7x7_bf16mma spends its time expanding: per half row every thread makes ~5 x (4 ds_read_b32 + 3 shifts + ds_write_b128: expand_cols)
+// and two barriers frame 11 MFMAs per wave -- PMC: matrix pipe 13 % busy, 55 % of the wave cycles parked, the LDS array saturated by
+// three co-resident workgroups.  Here the A fragment of a pixel is read STRAIGHT from the staged patch: the 8 k of a group
+// (c, kh) are the 8 consecutive input pixels 2q+1 .. 2q+8 of one patch row (q = strip pixel; the 8th meets the filter's zero
+// column), an odd element offset.  The patch is therefore kept as the two shifted copies of two_copies: pixel q reads copy
+// q & 1 at byte 8 (q >> 1) -- two aligned ds_read_b64 per fragment, address = lane base + immediate, no VALU, no barrier.  With the
+// copies 128 B (mod 256) apart the 32 lanes of a ds_read_b64 group cover all 64 banks once.  Staging makes both copies from two
+// aligned 16-byte global loads per lane (columns 4m .. 4m+7: the second is the neighbour's first, an L1 hit) and two ds_write_b64.
+// Barriers: two per chunk of four stem rows (was 18).  Same fragments, same mma_bf16_11, same bn_relu_hmax3 / PoolRows ->
+// bit-identical to stem_pool7x7_bf16mma for finite images (the kw = 7 product is pixel x 0 instead of 0 x 0).
+constexpr int RPB = PW * 2;                                        // bytes per patch row of one copy (264 bf16)
+constexpr int COPYB = ((3 * PR * RPB + 255) / 256) * 256 + 128;    // copy stride: == 128 (mod 256)
+// The pooled row leaves through a per-wave LDS transpose: a lane holds ONE channel of 8 pooled pixels (2-byte stores, 8 per lane and
+// half row: in-kernel ablation put 40 % of the kernel on them); written as bf16 to [16 pixels][32 channels] and read back as 16-byte
+// pieces, a wave stores its 16 x 64 bytes with ONE b128 store per lane.  Wave-local: no barrier.
+constexpr int TPITCH = 80;                                         // bytes per pixel of a transpose tile (64 + 16: the two lane halves hit different banks)
+constexpr int TTILE = 16 * TPITCH;                                 // one (wave, half row) tile
+constexpr size_t kStemBf16V2Lds = (size_t)2 * COPYB + (size_t)4 * 2 * TTILE;
+constexpr int QPR = PW / 4;                                        // 16-byte quads per patch row (66)
+constexpr int NITEM = 3 * PR * QPR, NIT = (NITEM + 255) / 256;     // staging items (row, quad) per chunk: 2574 = 10 x 256 + 14
+__host__ __device__ constexpr int stem_row_of(int r) { return r >= 21 ? (2 * PR + 6) : (r / 7) * PR + (r % 7); }   // k-group -> patch row (group 21: zero filter)
+
+__global__ __launch_bounds__(256) void stem_pool7x7_bf16v2(const float* __restrict__ x, const __bf16* __restrict__ w,
+                                                            const float* __restrict__ scale, const float* __restrict__ shift,
+                                                            __bf16* __restrict__ y, int H, int W, int Ho, int Wo, int Hp, int Wp,
+                                                            int tilesW, int nseg, int rows_per_seg) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* const lds = reinterpret_cast<char*>(smem);                 // [2 copies][3 * PR rows][RPB]; the filter bank passes through first
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const PoolStrip s(blockIdx.x, tilesW, nseg, rows_per_seg, Hp);
+  stage_filter_bf16(w, lds, tid);
+  __syncthreads();
+  const int h = lane >> 5, l31 = lane & 31;
+  const int mi = wave >> 1, ni = wave & 1;
+  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
+  bf16x8s bfrag[NG];
+  load_frags(lds + (ni * 32 + l31) * CP + h * 16, bfrag);
+  // A-fragment addresses: k-group 2g + h of pixel q -> copy (q & 1), patch row stem_row_of(2g + h) + 2 ro, byte 8 (q >> 1).
+  // Row of the odd group = row of the even one + 1, except 6|7 (next channel: + PR - 6), 20|21 (the zero group: same row, any finite data)
+  // (the reads are inline asm: left to hipcc, pairs of them -- the two halves of a fragment, or the same half of two rows -- are fused into
+  //  ds_read2_b64, which runs at half rate and is banked mod 32: PMC showed 41 % conflict cycles.  Plain ds_read_b64 are conflict-free.)
+  unsigned abase[2];
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    const int q = hf * 2 * WPX + mi * WPX + l31;
+    abase[hf] = (unsigned)(uintptr_t)lds + (unsigned)((q & 1) * COPYB + 8 * (q >> 1));
+  }
+  const int hrow1 = h * RPB, hrow7 = h * (PR - 6) * RPB;
+  const bool interior = s.interior(Wo);
+  const bool vec_ok = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) && (long long)3 * H * W * 4 < (1ll << 31);
+  const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (size_t)s.n * 3 * H * W), 0, 3 * H * W * 4, 0x00020000);
+  PoolRows rows[2];                                                // per half row
+
+  for (int oh0 = s.r_first; oh0 <= s.r_last; oh0 += TH) {
+    __syncthreads();                                               // the previous chunk's patch (or the filter bank) is consumed
+    const float* img = x + (size_t)s.n * 3 * H * W;
+    const int iw0 = 2 * s.ow0 - 4;
+    if (vec_ok) {
+      // patch rows 2*oh0 - 3 .., columns 2*ow0 - 4 .. -> the two shifted bf16 copies.  ALL loads of the chunk first (a thread owns up to
+      // NIT (row, quad) items; 2 x 16 bytes each: columns 4 c4 .. + 7, the second load is the neighbour's first -- a cache hit), ONE
+      // wait, then the conversions: the per-row loop this replaces paid a memory latency per row (in-kernel ablation: 53 % of the kernel)
+      f32x4 sv[NIT], su[NIT];
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int i = it * 256 + tid;
+        const int r = (i * 993) >> 16, c4 = i - r * QPR;              // i / 66 for i < 2816
+        const int c = (r * 5042) >> 16, pr = r - c * PR;              // r / 13 for r < 42
+        const int ih = 2 * oh0 - 3 + pr, iw = iw0 + 4 * c4;
+        // (one unsigned compare per bound, folded into the offset at once: no lane masks kept across the loads)
+        unsigned ro = (unsigned)(((c * H + ih) * W + iw) * 4);
+        ro = ((it < NIT - 1 || i < NITEM) && (unsigned)ih < (unsigned)H) ? ro : 0x80000000u;
+        sv[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (unsigned)iw < (unsigned)W ? ro : 0x80000000u, 0, 0));
+        su[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (unsigned)(iw + 4) < (unsigned)W ? ro + 16u : 0x80000000u, 0, 0));
+      }
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int i = it * 256 + tid;
+        const int r = (i * 993) >> 16, c4 = i - r * QPR;
+        bf16x4s a0, a1;
+        two_copies(sv[it], su[it], a0, a1);
+        if (it < NIT - 1 || i < NITEM) {
+          *reinterpret_cast<bf16x4s*>(lds + (size_t)r * RPB + 8 * c4) = a0;
+          *reinterpret_cast<bf16x4s*>(lds + COPYB + (size_t)r * RPB + 8 * c4) = a1;
+        }
+      }
+    } else {                                                       // unaligned image / odd width: the scalar path, row by row
+      const int wv = __builtin_amdgcn_readfirstlane(wave);
+      for (int r = wv; r < 3 * PR; r += 4) {
+        const int c = r / PR, pr = r - c * PR;
+        const int ih = 2 * oh0 - 3 + pr;
+        const bool row_ok = (unsigned)ih < (unsigned)H;
+        const float* row = img + ((size_t)c * H + (row_ok ? ih : 0)) * W;
+        for (int c4 = lane; c4 < QPR; c4 += 64) {
+          const int iw = iw0 + 4 * c4;
+          f32x4 v = {0.f, 0.f, 0.f, 0.f}, u = {0.f, 0.f, 0.f, 0.f};    // patch columns 4 c4 .. + 3 and the next four
+          if (row_ok) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if ((unsigned)(iw + j) < (unsigned)W) v[j] = row[iw + j];
+              if ((unsigned)(iw + 4 + j) < (unsigned)W) u[j] = row[iw + 4 + j];
+            }
+          }
+          bf16x4s a0, a1;
+          two_copies(v, u, a0, a1);
+          *reinterpret_cast<bf16x4s*>(lds + (size_t)r * RPB + 8 * c4) = a0;
+          *reinterpret_cast<bf16x4s*>(lds + COPYB + (size_t)r * RPB + 8 * c4) = a1;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ro = 0; ro < TH; ++ro) {
+      const int oh = oh0 + ro;
+      if (oh > s.r_last) break;
+      const bool row_ok = (unsigned)oh < (unsigned)Ho;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        if (s.ow0 + hf * 2 * WPX >= Wo) break;                     // (uniform) nothing of this half exists
+        bf16x8s afrag[NG];
+        {
+          const unsigned a0 = abase[hf], a1 = a0 + (unsigned)hrow1, a7 = a0 + (unsigned)hrow7;
+          bf16x4s lo[NG], hi[NG];
+#define STEM_RD(g, base)                                                                                                            \
+          asm volatile("ds_read_b64 %0, %2 offset:%3\n\tds_read_b64 %1, %2 offset:%4"                                            \
+                       : "=&v"(lo[g]), "=&v"(hi[g])                                                                                  \
+                       : "v"(base), "n"(stem_row_of(2 * (g)) * RPB + ro * 2 * RPB), "n"(stem_row_of(2 * (g)) * RPB + ro * 2 * RPB + 8) \
+                       : "memory")
+          STEM_RD(0, a1); STEM_RD(1, a1); STEM_RD(2, a1); STEM_RD(3, a7); STEM_RD(4, a1); STEM_RD(5, a1);
+          STEM_RD(6, a1); STEM_RD(7, a1); STEM_RD(8, a1); STEM_RD(9, a1); STEM_RD(10, a0);
+#undef STEM_RD
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int g = 0; g < NG; ++g) afrag[g] = __builtin_shufflevector(lo[g], hi[g], 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        const f32x16 acc = mma_bf16_11(afrag, bfrag);
+        const int col0 = s.ow0 + hf * 2 * WPX + mi * WPX + 4 * h;  // stem column of register 0 of this lane
+        float hm[8];
+        bn_relu_hmax3(acc, sc, sh, row_ok, col0, Wo, interior, h, hm);
+        const int pr = s.completes(oh);
+        if (pr >= 0) {
+          // this wave's 16 pooled pixels x 32 channels through its transpose tile (see TPITCH): lane (l31, h) holds channel l31 of
+          // pixels 4 (c >> 1) + (c & 1) + 2 h; lane (pixel = lane >> 2, piece = lane & 3) then stores 8 channels of one pixel
+          char* const tt = lds + 2 * COPYB + (wave * 2 + hf) * TTILE;
+#pragma unroll
+          for (int c = 0; c < 8; ++c)
+            *reinterpret_cast<__bf16*>(tt + (4 * (c >> 1) + (c & 1) + 2 * h) * TPITCH + 2 * l31) = (__bf16)rows[hf].vmax3(hm, c);
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          const int px = lane >> 2, piece = lane & 3;
+          const u32x4 q = *reinterpret_cast<const u32x4*>(tt + px * TPITCH + piece * 16);
+          const int cc = s.ow0 + hf * 2 * WPX + mi * WPX + 2 * px;    // stem column of the window centre (even); pixel 0 is the left neighbour's
+          if (px != 0 && cc >= 0 && (cc >> 1) < Wp)
+            *reinterpret_cast<u32x4*>(y + ((size_t)(s.n * Hp + pr) * Wp + (cc >> 1)) * 64 + ni * 32 + piece * 8) = q;
+          asm volatile("" ::: "memory");
+        }
+        rows[hf].roll(hm);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void stem_pack_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 64 * KP) return;
+  const int ch = i / KP, k = i - ch * KP, r = k >> 3, kw = k & 7;
+  float v = 0.f;
+  if (r < 21 && kw < 7) v = w[(ch * 21 + r) * 7 + kw];
+  out[i] = (__bf16)v;
+}
+
 }  // namespace
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------
+// The maps of an H x W image: the stem map (7x7 / stride 2 / pad 3), the pooled map (3x3 / stride 2 / pad 1) and the tile counts.
+struct StemDims {
+  int Ho, Wo, Hp, Wp;
+  int tilesW, tilesH;                    // tiles of TH rows x TP pixels (stem_conv7x7, stem_conv7x7_bf16mma, stem_wgrad)
+  int stripsW;                           // pooling strips of TPS stem columns = TPS / 2 pooled columns
+  StemDims(int H, int W)
+      : Ho((H + 6 - 7) / 2 + 1), Wo((W + 6 - 7) / 2 + 1), Hp((Ho + 2 - 3) / 2 + 1), Wp((Wo + 2 - 3) / 2 + 1),
+        tilesW((Wo + TP - 1) / TP), tilesH((Ho + TH - 1) / TH), stripsW((Wp + TPS / 2 - 1) / (TPS / 2)) {}
+};
+
+// Segments of pooled rows for the pooling kernels: fewest (rounds of `resident` co-resident workgroups) x (chunks of TH stem rows
+// per workgroup), so that the grid fills whole rounds.
+struct PoolSegments { int rps, nseg; };
+static PoolSegments pool_segments(int N, int tilesW, int Hp, int resident) {
+  int best_seg = 1;
+  long long best_cost = -1;
+  for (int ns = 1; ns <= 32 && ns <= Hp; ++ns) {
+    const int rps = (Hp + ns - 1) / ns, real = (Hp + rps - 1) / rps;
+    const long long wgs = (long long)N * tilesW * real;
+    const long long cost = ((wgs + resident - 1) / resident) * ((2 * rps + 1 + TH - 1) / TH);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = real; }
+  }
+  const int rps = (Hp + best_seg - 1) / best_seg;
+  return {rps, (Hp + rps - 1) / rps};
+}
+
+// The argument checks of the four forward families; `who` is the family's message prefix.  Only the unpooled bf16-MFMA kernel asks
+// for an aligned output (y16).
+static int stem_check(const char* who, const void* x, const void* w, const void* scale, const void* shift, const void* y, bool y16,
+                      int N, int H, int W) {
+  BEVF_REQUIRE(x && w && scale && shift && y, "%s: null pointer", who);
+  if (y16)
+    BEVF_REQUIRE(bevf_aligned16(w) && bevf_aligned16(y), "%s: unaligned", who);
+  else
+    BEVF_REQUIRE(bevf_aligned16(w), "%s: packed filter bank must be 16-byte aligned", who);
+  BEVF_REQUIRE(N > 0 && H >= 1 && W >= 1, "%s: empty shape", who);
+  return BEVF_OK;
+}
+static int stem_grid(const char* who, long long grid) {
+  BEVF_REQUIRE(grid < (1ll << 31), "%s: grid too large", who);
+  return BEVF_OK;
+}
+// stage_patch may use its 16-byte loads
+static int stem_vec_ok(const float* x, int W) { return (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0; }
 
 template <typename TO>
 static int stem_entry(const float* x, const float* w, const float* scale, const float* shift, void* y, int N, int H,
                       int W, int relu, void* stream) {
-  BEVF_REQUIRE(x && w && scale && shift && y, "stem: null pointer");
-  BEVF_REQUIRE(bevf_aligned16(w), "stem: packed filter bank must be 16-byte aligned");
-  BEVF_REQUIRE(N > 0 && H >= 1 && W >= 1, "stem: empty shape");
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
-  const long long grid = (long long)N * tilesH * tilesW;
-  BEVF_REQUIRE(grid < (1ll << 31), "stem: grid too large");
+  if (const int rc = stem_check("stem", x, w, scale, shift, y, false, N, H, W)) return rc;
+  const StemDims d(H, W);
+  const long long grid = (long long)N * d.tilesH * d.tilesW;
+  if (const int rc = stem_grid("stem", grid)) return rc;
   return bevf_launch("bevf_stem_conv7x7", stem_conv7x7<TO>, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x,
-                     w, scale, shift, static_cast<TO*>(y), H, W, Ho, Wo, tilesW, tilesH,
-                     (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0, relu);
+                     w, scale, shift, static_cast<TO*>(y), H, W, d.Ho, d.Wo, d.tilesW, d.tilesH, stem_vec_ok(x, W), relu);
 }
 extern "C" int bevf_stem_conv7x7_f32(const float* x, const float* w, const float* scale, const float* shift,
                                      float* y, int N, int H, int W, int relu, void* stream) {
@@ -496,26 +961,13 @@ extern "C" int bevf_stem_conv7x7_bf16out(const float* x, const float* w, const f
 // by bevf_maxpool3x3s2_nhwc_f32
 extern "C" int bevf_stem_pool_f32(const float* x, const float* w, const float* scale, const float* shift, float* y, int N,
                                   int H, int W, void* stream) {
-  BEVF_REQUIRE(x && w && scale && shift && y, "stem_pool: null pointer");
-  BEVF_REQUIRE(bevf_aligned16(w), "stem_pool: packed filter bank must be 16-byte aligned");
-  BEVF_REQUIRE(N > 0 && H >= 1 && W >= 1, "stem_pool: empty shape");
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  const int Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-  const int tilesW = (Wp + TPS / 2 - 1) / (TPS / 2);
-  // segments of pooled rows: fewest (rounds of 512 resident workgroups) x (chunks of 4 stem rows per workgroup)
-  int best_seg = 1;
-  long long best_cost = -1;
-  for (int ns = 1; ns <= 32 && ns <= Hp; ++ns) {
-    const int rps = (Hp + ns - 1) / ns, real = (Hp + rps - 1) / rps;
-    const long long wgs = (long long)N * tilesW * real;
-    const long long cost = ((wgs + 511) / 512) * ((2 * rps + 1 + TH - 1) / TH);
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = real; }
-  }
-  const int rps = (Hp + best_seg - 1) / best_seg, nseg = (Hp + rps - 1) / rps;
-  const long long grid = (long long)N * tilesW * nseg;
-  BEVF_REQUIRE(grid < (1ll << 31), "stem_pool: grid too large");
+  if (const int rc = stem_check("stem_pool", x, w, scale, shift, y, false, N, H, W)) return rc;
+  const StemDims d(H, W);
+  const PoolSegments sg = pool_segments(N, d.stripsW, d.Hp, 512);            // 79 KB of LDS each: 2 per CU
+  const long long grid = (long long)N * d.stripsW * sg.nseg;
+  if (const int rc = stem_grid("stem_pool", grid)) return rc;
   return bevf_launch("bevf_stem_pool_f32", stem_pool7x7, dim3((unsigned)grid), dim3(256), kStemLds, static_cast<hipStream_t>(stream), x, w,
-                     scale, shift, y, H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
+                     scale, shift, y, H, W, d.Ho, d.Wo, d.Hp, d.Wp, d.stripsW, sg.nseg, sg.rps, stem_vec_ok(x, W));
 }
 
 template <typename T>
@@ -543,538 +995,13 @@ extern "C" int bevf_maxpool3x3s2_nhwc_bf16(const void* x, void* y, int N, int H,
 extern "C" int bevf_stem_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H, int W, void* stream) {
   BEVF_REQUIRE(x && dy && dw && N > 0 && H >= 1 && W >= 1, "stem_wgrad: bad arguments");
   BEVF_REQUIRE(bevf_aligned16(dy), "stem_wgrad: dy must be 16-byte aligned");
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
-  const long long tiles = (long long)N * tilesH * tilesW;
+  const StemDims d(H, W);
+  const long long tiles = (long long)N * d.tilesH * d.tilesW;
   BEVF_REQUIRE(tiles < (1ll << 31), "stem_wgrad: too many tiles");
   const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);          // 2 workgroups per CU, each over many tiles
   return bevf_launch("bevf_stem_wgrad_f32", stem_wgrad, dim3(grid), dim3(256), kStemWgradLds, static_cast<hipStream_t>(stream), x, dy, dw,
-                     N, H, W, Ho, Wo, tilesW, tilesH, (W % 4 == 0 && bevf_aligned16(x)) ? 1 : 0);
+                     N, H, W, d.Ho, d.Wo, d.tilesW, d.tilesH, stem_vec_ok(x, W));
 }
-
-// ---- bf16 stem (bf16-storage models): 7x7 stride-2 conv on v_mfma_f32_32x32x16_bf16 -----------------------------------
-// The bf16 MFMA wants 8 consecutive k per lane, which the strided patch cannot supply directly.  Per half output row
-// (64 pixels) the workgroup therefore expands the bf16 patch into an explicit column tile in LDS,
-//     col[pixel][k],  k = (c*7 + kh)*8 + kw   (kw = 7 and k >= 168 are zero columns; 176 = 11 MFMA k-groups),
-// with four aligned dword reads + three v_alignbit per (pixel, c, kh) item and one 16-byte write, then runs 11 MFMAs
-// per wave on aligned 16-byte fragments.  The expansion is vector-ALU / LDS work that the fp32 stem could not afford
-// (there every VALU instruction queues behind a 64-cycle MFMA); the bf16 MFMA is 16x faster per flop, so even with the
-// expansion the stem drops from ~24 % to a few % of the bf16 step.
-namespace {
-
-constexpr int KP = 176;                  // padded K (bf16 elements)
-constexpr int CP = 368;                  // row pitch in bytes of the column / weight tiles (176*2 + 16: conflict-free b128)
-constexpr int HP = 64;                   // pixels per expansion (half a tile row)
-
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4s __attribute__((ext_vector_type(4)));
-
-template <typename TO>
-__global__ __launch_bounds__(256) void stem_conv7x7_bf16mma(const float* __restrict__ x, const __bf16* __restrict__ w,
-                                                             const float* __restrict__ scale, const float* __restrict__ shift,
-                                                             TO* __restrict__ y, int H, int W, int Ho, int Wo, int tilesW,
-                                                             int tilesH, int relu) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  // The filter bank only passes through LDS (each wave keeps its fragments in registers), so it shares the column
-  // tile's storage: 44 KB per workgroup, 3 workgroups per CU.
-  char* const col = reinterpret_cast<char*>(smem);                 // [HP][CP]   bf16 column tile
-  char* const wt = col;                                            // [64][CP]   bf16 filter, k contiguous per channel (transient)
-  char* const patch = col + HP * CP;                               // [3][PR][PW] bf16
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = blockIdx.x % tilesW;
-  const int th = (blockIdx.x / tilesW) % tilesH;
-  const int n = blockIdx.x / (tilesW * tilesH);
-  const int ow0 = tw * TP, oh0 = th * TH;
-
-  // filter bank [64][176] bf16 -> LDS rows of pitch CP
-  for (int i = tid; i < 64 * (KP / 8); i += 256) {
-    const int ch = i / (KP / 8), q = i - ch * (KP / 8);
-    *reinterpret_cast<u32x4*>(wt + ch * CP + q * 16) = *reinterpret_cast<const u32x4*>(w + (size_t)ch * KP + q * 8);
-  }
-  // patch: fp32 image rows -> bf16 (patch row (c, pr) <-> image row 2*oh0 - 3 + pr, patch col <-> iw = 2*ow0 - 4 + col);
-  // one patch row per wave and pass, 16-byte loads that the descriptor zero-fills outside the image row
-  {
-    const float* img = x + (size_t)n * 3 * H * W;
-    const int iw0 = 2 * ow0 - 4;
-    const int wv = __builtin_amdgcn_readfirstlane(wave);
-    const bool vec_ok = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
-    for (int r = wv; r < 3 * PR; r += 4) {
-      const int c = r / PR, pr = r - c * PR;
-      const int ih = 2 * oh0 - 3 + pr;
-      const bool row_ok = (unsigned)ih < (unsigned)H;                      // wave-uniform
-      const float* row = img + ((size_t)c * H + (row_ok ? ih : 0)) * W;
-      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, row_ok ? W * 4 : 0, 0x00020000);
-      for (int c4 = lane; c4 < PW / 4; c4 += 64) {
-        const int iw = iw0 + 4 * c4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec_ok) {
-          v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, iw >= 0 ? (unsigned)(iw * 4) : 0x80000000u, 0, 0));
-        } else if (row_ok) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if ((unsigned)(iw + j) < (unsigned)W) v[j] = row[iw + j];
-        }
-        bf16x4s b;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = (__bf16)v[j];
-        *reinterpret_cast<bf16x4s*>(patch + ((size_t)r * PW + 4 * c4) * 2) = b;
-      }
-    }
-  }
-  __syncthreads();
-
-  const int h = lane >> 5, l31 = lane & 31;
-  const int mi = wave >> 1, ni = wave & 1;                         // wave tile: 32 pixels x 32 channels of the half row
-  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
-  const char* const a_rd = col + (mi * 32 + l31) * CP + h * 16;
-  const char* const b_rd = wt + (ni * 32 + l31) * CP + h * 16;
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  constexpr int NG = KP / 16;
-  bf16x8s bfrag[NG];                                               // the wave's filter fragments: read once per tile
-#pragma unroll
-  for (int g = 0; g < NG; ++g) bfrag[g] = *reinterpret_cast<const bf16x8s*>(b_rd + g * 32);
-  __syncthreads();                                                 // filter bank consumed: its storage becomes the column tile
-  if (tid < HP) *reinterpret_cast<u32x4*>(col + tid * CP + 168 * 2) = u32x4{0u, 0u, 0u, 0u};   // zero columns 168..175, once
-  // expansion roles: item i = tid + 256*j <-> (pixel p = i & 63, patch row r = i >> 6); p and the r-step are fixed per thread
-  const int xp = tid & (HP - 1), xr0 = tid >> 6;                   // r = xr0 + 4*j, j < 6 (r < 21)
-
-  for (int ro = 0; ro < TH; ++ro) {
-    const int oh = oh0 + ro;
-    if (oh >= Ho) break;
-    for (int hf = 0; hf < TP / HP; ++hf) {
-      if (ow0 + hf * HP >= Wo) break;
-      // ---- expand: all window reads first, then the shifts and the 16-byte writes -----------------------------------
-      {
-        unsigned d[6][4];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          const int r = xr0 + 4 * j;
-          if (r < 21) {
-            const int c = r / 7, kh = r - c * 7;
-            const unsigned* src = reinterpret_cast<const unsigned*>(patch + ((size_t)(c * PR + 2 * ro + kh) * PW + 2 * (hf * HP + xp)) * 2);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) d[j][q] = src[q];
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          const int r = xr0 + 4 * j;
-          if (r < 21) {
-            u32x4 o;
-            o[0] = __builtin_amdgcn_alignbit(d[j][1], d[j][0], 16);
-            o[1] = __builtin_amdgcn_alignbit(d[j][2], d[j][1], 16);
-            o[2] = __builtin_amdgcn_alignbit(d[j][3], d[j][2], 16);
-            o[3] = d[j][3] >> 16;                                  // kw = 6, then the zero column kw = 7
-            *reinterpret_cast<u32x4*>(col + xp * CP + r * 16) = o;
-          }
-        }
-      }
-      __syncthreads();
-      // ---- 11 k-groups of 16: fragments first, then the MFMAs back to back --------------------------------------------
-      bf16x8s afrag[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) afrag[g] = *reinterpret_cast<const bf16x8s*>(a_rd + g * 32);
-      f32x16 acc;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[g], bfrag[g], g == 0 ? zero : acc, 0, 0, 0);
-      // ---- epilogue: rows i = pixel, column j = channel ------------------------------------------------------
-      const int px0 = ow0 + hf * HP + mi * 32;
-      const int left = Wo - px0;
-      TO* const ybase = y + ((size_t)(n * Ho + oh) * Wo + px0) * 64 + ni * 32;
-      const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-          ybase, 0, left > 0 ? ((left > 32 ? 32 : left) * 64 - ni * 32) * (int)sizeof(TO) : 0, 0x00020000);
-      const unsigned lane_off = (unsigned)((4 * h * 64 + l31) * (int)sizeof(TO));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ioff = ((r & 3) + 8 * (r >> 2)) * 64 * (int)sizeof(TO);
-        float v = fmaf(acc[r], sc, sh);
-        if (relu) v = fmaxf(v, 0.f);
-        if constexpr (sizeof(TO) == 4)
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, lane_off + ioff, 0, 0);
-        else
-          __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), ry, lane_off + ioff, 0, 0);
-      }
-      __syncthreads();                                             // column tile free for the next expansion
-    }
-  }
-}
-
-constexpr size_t kStemBf16Lds = (size_t)HP * CP + (size_t)3 * PR * PW * 2;
-
-// ---- bf16 stem + 3x3/s2 max-pool in one kernel (bf16-storage inference): the streaming structure of stem_pool7x7 on the
-// bf16 MFMA path above.  A workgroup owns a strip of 120 new stem columns and a segment of pooled rows; per stem row it runs
-// two half rows of 62 pixels (the column tile still has 64 rows; wave (mi, ni) takes pixels 30 mi .. 30 mi + 31 of the
-// half and channels 32 ni ..), so the four 32-pixel wave tiles of a row start 30 pixels apart and every pooling window
-// lies inside one wave's tile; vertical state (the horizontal maxima of the last two stem rows) stays in registers.
-// max commutes with the (monotonic) bf16 rounding and a missing neighbour counts as 0 after the ReLU, so the result is
-// bit-identical to bevf_stem_conv7x7_bf16mma followed by bevf_maxpool3x3s2_nhwc_bf16 -- without the 2.2 GB bf16 stem map.
-__global__ __launch_bounds__(256) void stem_pool7x7_bf16mma(const float* __restrict__ x, const __bf16* __restrict__ w,
-                                                             const float* __restrict__ scale, const float* __restrict__ shift,
-                                                             __bf16* __restrict__ y, int H, int W, int Ho, int Wo, int Hp, int Wp,
-                                                             int tilesW, int nseg, int rows_per_seg) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* const col = reinterpret_cast<char*>(smem);                 // [HP][CP]   bf16 column tile
-  char* const wt = col;                                            // [64][CP]   bf16 filter (transient)
-  char* const patch = col + HP * CP;                               // [3][PR][PW] bf16
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = blockIdx.x % tilesW;
-  const int seg = (blockIdx.x / tilesW) % nseg;
-  const int n = blockIdx.x / (tilesW * nseg);
-  const int ow0 = tw * TPS - 2;
-  const int p0 = seg * rows_per_seg, p1 = p0 + rows_per_seg < Hp ? p0 + rows_per_seg : Hp;
-  const int r_first = 2 * p0 - 1, r_last = 2 * (p1 - 1) + 1;       // stem rows this segment needs
-  for (int i = tid; i < 64 * (KP / 8); i += 256) {
-    const int ch = i / (KP / 8), q = i - ch * (KP / 8);
-    *reinterpret_cast<u32x4*>(wt + ch * CP + q * 16) = *reinterpret_cast<const u32x4*>(w + (size_t)ch * KP + q * 8);
-  }
-  __syncthreads();
-  const int h = lane >> 5, l31 = lane & 31;
-  const int mi = wave >> 1, ni = wave & 1;
-  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
-  const char* const a_rd = col + (mi * WPX + l31) * CP + h * 16;
-  const char* const b_rd = wt + (ni * 32 + l31) * CP + h * 16;
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  constexpr int NG = KP / 16;
-  bf16x8s bfrag[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) bfrag[g] = *reinterpret_cast<const bf16x8s*>(b_rd + g * 32);
-  __syncthreads();                                                 // filter bank consumed: its storage becomes the column tile
-  if (tid < HP) *reinterpret_cast<u32x4*>(col + tid * CP + 168 * 2) = u32x4{0u, 0u, 0u, 0u};
-  const int xp = tid & (HP - 1), xr0 = tid >> 6;
-  const bool vec_ok = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
-  float prev1[2][8], prev2[2][8];                                  // [half][centre]: horizontal maxima of the last two stem rows
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { prev1[a][i] = 0.f; prev2[a][i] = 0.f; }
-
-  for (int oh0 = r_first; oh0 <= r_last; oh0 += TH) {
-    __syncthreads();                                               // the previous chunk's patch is fully consumed
-    {                                                              // patch rows 2*oh0 - 3 .., columns 2*ow0 - 4 .. as bf16
-      const float* img = x + (size_t)n * 3 * H * W;
-      const int iw0 = 2 * ow0 - 4;
-      const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int r = wv; r < 3 * PR; r += 4) {
-        const int c = r / PR, pr = r - c * PR;
-        const int ih = 2 * oh0 - 3 + pr;
-        const bool row_ok = (unsigned)ih < (unsigned)H;
-        const float* row = img + ((size_t)c * H + (row_ok ? ih : 0)) * W;
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row), 0, row_ok ? W * 4 : 0, 0x00020000);
-        for (int c4 = lane; c4 < PW / 4; c4 += 64) {
-          const int iw = iw0 + 4 * c4;
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          if (vec_ok) {
-            v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, iw >= 0 ? (unsigned)(iw * 4) : 0x80000000u, 0, 0));
-          } else if (row_ok) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if ((unsigned)(iw + j) < (unsigned)W) v[j] = row[iw + j];
-          }
-          bf16x4s b;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) b[j] = (__bf16)v[j];
-          *reinterpret_cast<bf16x4s*>(patch + ((size_t)r * PW + 4 * c4) * 2) = b;
-        }
-      }
-    }
-    __syncthreads();
-    for (int ro = 0; ro < TH; ++ro) {
-      const int oh = oh0 + ro;
-      if (oh > r_last) break;
-      const bool row_ok = (unsigned)oh < (unsigned)Ho;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        if (ow0 + hf * 2 * WPX >= Wo) break;                       // (uniform) nothing of this half exists
-        {
-          unsigned d[6][4];
-#pragma unroll
-          for (int j = 0; j < 6; ++j) {
-            const int r = xr0 + 4 * j;
-            if (r < 21) {
-              const int c = r / 7, kh = r - c * 7;
-              const unsigned* src = reinterpret_cast<const unsigned*>(patch + ((size_t)(c * PR + 2 * ro + kh) * PW + 2 * (hf * 2 * WPX + xp)) * 2);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) d[j][q] = src[q];
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 6; ++j) {
-            const int r = xr0 + 4 * j;
-            if (r < 21) {
-              u32x4 o;
-              o[0] = __builtin_amdgcn_alignbit(d[j][1], d[j][0], 16);
-              o[1] = __builtin_amdgcn_alignbit(d[j][2], d[j][1], 16);
-              o[2] = __builtin_amdgcn_alignbit(d[j][3], d[j][2], 16);
-              o[3] = d[j][3] >> 16;
-              *reinterpret_cast<u32x4*>(col + xp * CP + r * 16) = o;
-            }
-          }
-        }
-        __syncthreads();
-        bf16x8s afrag[NG];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) afrag[g] = *reinterpret_cast<const bf16x8s*>(a_rd + g * 32);
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[g], bfrag[g], g == 0 ? zero : acc, 0, 0, 0);
-        // BatchNorm + ReLU as the unfused kernel stores them (before its bf16 rounding); missing rows / columns count as 0
-        const int col0 = ow0 + hf * 2 * WPX + mi * WPX + 4 * h;    // stem column of register 0 of this lane
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const bool ok = row_ok && (unsigned)(col0 + (r & 3) + 8 * (r >> 2)) < (unsigned)Wo;
-          v[r] = ok ? fmaxf(fmaf(acc[r], sc, sh), 0.f) : 0.f;
-        }
-        float hm[8], xl[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) xl[g] = __shfl_xor(v[4 * g + 3], 32);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float l0 = h ? xl[g] : (g > 0 ? xl[g - 1] : 0.f);
-          hm[2 * g] = fmaxf(fmaxf(l0, v[4 * g]), v[4 * g + 1]);
-          hm[2 * g + 1] = fmaxf(fmaxf(v[4 * g + 1], v[4 * g + 2]), v[4 * g + 3]);
-        }
-        if (oh & 1) {                                              // stem row 2p+1 completes pooled row p (uniform branch)
-          const int pr = (oh - 1) >> 1;
-          if (pr >= p0 && pr < p1) {
-            __bf16* const yrow = y + ((size_t)(n * Hp + pr) * Wp) * 64 + ni * 32 + l31;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              const int rc = 2 * c;
-              const int cc = col0 + (rc & 3) + 8 * (rc >> 2);      // stem column of the window centre (even)
-              const bool own = (h != 0 || c != 0) && cc >= 0 && (cc >> 1) < Wp;
-              if (own) yrow[(size_t)(cc >> 1) * 64] = (__bf16)fmaxf(fmaxf(prev2[hf][c], prev1[hf][c]), hm[c]);
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { prev2[hf][i] = prev1[hf][i]; prev1[hf][i] = hm[i]; }
-        __syncthreads();                                           // column tile free for the next expansion
-      }
-    }
-  }
-}
-
-// ---- round 3: the same fused bf16 stem + max-pool WITHOUT the column-tile expansion ------------------------------------------
-// stem_pool7x7_bf16mma spends its time expanding: per half row every thread makes ~5 x (4 ds_read_b32 + 3 v_alignbit + ds_write_b128)
-// and two barriers frame 11 MFMAs per wave -- PMC: matrix pipe 13 % busy, 55 % of the wave cycles parked, the LDS array saturated by
-// three co-resident workgroups.  Here the A fragment of a pixel is read STRAIGHT from the staged patch: the 8 k of a group
-// (c, kh) are the 8 consecutive input pixels 2q+1 .. 2q+8 of one patch row (q = strip pixel; the 8th meets the filter's zero
-// column), an odd element offset.  The patch is therefore kept as TWO bf16 copies shifted by 1 and by 3 elements: pixel q reads copy
-// q & 1 at byte 8 (q >> 1) -- two aligned ds_read_b64 per fragment, address = lane base + immediate, no VALU, no barrier.  With the
-// copies 128 B (mod 256) apart the 32 lanes of a ds_read_b64 group cover all 64 banks once.  Staging makes both copies from two
-// aligned 16-byte global loads per lane (columns 4m .. 4m+7: the second is the neighbour's first, an L1 hit), three v_cvt_pk and
-// two ds_write_b64.  Barriers: two per chunk of four stem rows (was 18).  Same fragments, same MFMA order, same epilogue ->
-// bit-identical to stem_pool7x7_bf16mma for finite images (the kw = 7 product is pixel x 0 instead of 0 x 0).
-constexpr int RPB = PW * 2;                                        // bytes per patch row of one copy (264 bf16)
-constexpr int COPYB = ((3 * PR * RPB + 255) / 256) * 256 + 128;    // copy stride: == 128 (mod 256)
-// The pooled row leaves through a per-wave LDS transpose: a lane holds ONE channel of 8 pooled pixels (2-byte stores, 8 per lane and
-// half row: in-kernel ablation put 40 % of the kernel on them); written as bf16 to [16 pixels][32 channels] and read back as 16-byte
-// pieces, a wave stores its 16 x 64 bytes with ONE b128 store per lane.  Wave-local: no barrier.
-constexpr int TPITCH = 80;                                         // bytes per pixel of a transpose tile (64 + 16: the two lane halves hit different banks)
-constexpr int TTILE = 16 * TPITCH;                                 // one (wave, half row) tile
-constexpr size_t kStemBf16V2Lds = (size_t)2 * COPYB + (size_t)4 * 2 * TTILE;
-constexpr int QPR = PW / 4;                                        // 16-byte quads per patch row (66)
-constexpr int NITEM = 3 * PR * QPR, NIT = (NITEM + 255) / 256;     // staging items (row, quad) per chunk: 2574 = 10 x 256 + 14
-__host__ __device__ constexpr int stem_row_of(int r) { return r >= 21 ? (2 * PR + 6) : (r / 7) * PR + (r % 7); }   // k-group -> patch row (group 21: zero filter)
-
-__global__ __launch_bounds__(256) void stem_pool7x7_bf16v2(const float* __restrict__ x, const __bf16* __restrict__ w,
-                                                            const float* __restrict__ scale, const float* __restrict__ shift,
-                                                            __bf16* __restrict__ y, int H, int W, int Ho, int Wo, int Hp, int Wp,
-                                                            int tilesW, int nseg, int rows_per_seg) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* const lds = reinterpret_cast<char*>(smem);                 // [2 copies][3 * PR rows][RPB]; the filter bank passes through first
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tw = blockIdx.x % tilesW;
-  const int seg = (blockIdx.x / tilesW) % nseg;
-  const int n = blockIdx.x / (tilesW * nseg);
-  const int ow0 = tw * TPS - 2;
-  const int p0 = seg * rows_per_seg, p1 = p0 + rows_per_seg < Hp ? p0 + rows_per_seg : Hp;
-  const int r_first = 2 * p0 - 1, r_last = 2 * (p1 - 1) + 1;       // stem rows this segment needs
-  for (int i = tid; i < 64 * (KP / 8); i += 256) {
-    const int ch = i / (KP / 8), q = i - ch * (KP / 8);
-    *reinterpret_cast<u32x4*>(lds + ch * CP + q * 16) = *reinterpret_cast<const u32x4*>(w + (size_t)ch * KP + q * 8);
-  }
-  __syncthreads();
-  const int h = lane >> 5, l31 = lane & 31;
-  const int mi = wave >> 1, ni = wave & 1;
-  const float sc = scale[ni * 32 + l31], sh = shift[ni * 32 + l31];
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  constexpr int NG = KP / 16;
-  bf16x8s bfrag[NG];
-  {
-    const char* const b_rd = lds + (ni * 32 + l31) * CP + h * 16;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) bfrag[g] = *reinterpret_cast<const bf16x8s*>(b_rd + g * 32);
-  }
-  // A-fragment addresses: k-group 2g + h of pixel q -> copy (q & 1), patch row stem_row_of(2g + h) + 2 ro, byte 8 (q >> 1).
-  // Row of the odd group = row of the even one + 1, except 6|7 (next channel: + PR - 6), 20|21 (the zero group: same row, any finite data)
-  // (the reads are inline asm: left to hipcc, pairs of them -- the two halves of a fragment, or the same half of two rows -- are fused into
-  //  ds_read2_b64, which runs at half rate and is banked mod 32: PMC showed 41 % conflict cycles.  Plain ds_read_b64 are conflict-free.)
-  unsigned abase[2];
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    const int q = hf * 2 * WPX + mi * WPX + l31;
-    abase[hf] = (unsigned)(uintptr_t)lds + (unsigned)((q & 1) * COPYB + 8 * (q >> 1));
-  }
-  const int hrow1 = h * RPB, hrow7 = h * (PR - 6) * RPB;
-  const bool all_cols = ow0 >= 0 && ow0 + 3 * WPX + 32 <= Wo;      // every stem column the four wave tiles touch exists
-  const bool vec_ok = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) && (long long)3 * H * W * 4 < (1ll << 31);
-  const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (size_t)n * 3 * H * W), 0, 3 * H * W * 4, 0x00020000);
-  float prev1[2][8], prev2[2][8];                                  // [half][centre]: horizontal maxima of the last two stem rows
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { prev1[a][i] = 0.f; prev2[a][i] = 0.f; }
-
-  for (int oh0 = r_first; oh0 <= r_last; oh0 += TH) {
-    __syncthreads();                                               // the previous chunk's patch (or the filter bank) is consumed
-    const float* img = x + (size_t)n * 3 * H * W;
-    const int iw0 = 2 * ow0 - 4;
-    if (vec_ok) {
-      // patch rows 2*oh0 - 3 .., columns 2*ow0 - 4 .. -> the two shifted bf16 copies.  ALL loads of the chunk first (a thread owns up to
-      // NIT (row, quad) items; 2 x 16 bytes each: columns 4 c4 .. + 7, the second load is the neighbour's first -- a cache hit), ONE
-      // wait, then the conversions: the per-row loop this replaces paid a memory latency per row (in-kernel ablation: 53 % of the kernel)
-      f32x4 sv[NIT], su[NIT];
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int i = it * 256 + tid;
-        const int r = (i * 993) >> 16, c4 = i - r * QPR;              // i / 66 for i < 2816
-        const int c = (r * 5042) >> 16, pr = r - c * PR;              // r / 13 for r < 42
-        const int ih = 2 * oh0 - 3 + pr, iw = iw0 + 4 * c4;
-        // (one unsigned compare per bound, folded into the offset at once: no lane masks kept across the loads)
-        unsigned ro = (unsigned)(((c * H + ih) * W + iw) * 4);
-        ro = ((it < NIT - 1 || i < NITEM) && (unsigned)ih < (unsigned)H) ? ro : 0x80000000u;
-        sv[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (unsigned)iw < (unsigned)W ? ro : 0x80000000u, 0, 0));
-        su[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rimg, (unsigned)(iw + 4) < (unsigned)W ? ro + 16u : 0x80000000u, 0, 0));
-      }
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int i = it * 256 + tid;
-        const int r = (i * 993) >> 16, c4 = i - r * QPR;
-        const f32x4 v = sv[it], u = su[it];
-        // copy 0 holds patch column e + 1 at element e, copy 1 column e + 3: elements 4 c4 .. 4 c4 + 3 of both
-        bf16x4s a0, a1;
-        a0[0] = (__bf16)v[1]; a0[1] = (__bf16)v[2]; a0[2] = (__bf16)v[3]; a0[3] = (__bf16)u[0];
-        a1[0] = a0[2]; a1[1] = a0[3]; a1[2] = (__bf16)u[1]; a1[3] = (__bf16)u[2];
-        if (it < NIT - 1 || i < NITEM) {
-          *reinterpret_cast<bf16x4s*>(lds + (size_t)r * RPB + 8 * c4) = a0;
-          *reinterpret_cast<bf16x4s*>(lds + COPYB + (size_t)r * RPB + 8 * c4) = a1;
-        }
-      }
-    } else {                                                       // unaligned image / odd width: the scalar path, row by row
-      const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int r = wv; r < 3 * PR; r += 4) {
-        const int c = r / PR, pr = r - c * PR;
-        const int ih = 2 * oh0 - 3 + pr;
-        const bool row_ok = (unsigned)ih < (unsigned)H;
-        const float* row = img + ((size_t)c * H + (row_ok ? ih : 0)) * W;
-        for (int c4 = lane; c4 < QPR; c4 += 64) {
-          const int iw = iw0 + 4 * c4;
-          f32x4 v = {0.f, 0.f, 0.f, 0.f}, u = {0.f, 0.f, 0.f, 0.f};    // patch columns 4 c4 .. + 3 and the next four
-          if (row_ok) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if ((unsigned)(iw + j) < (unsigned)W) v[j] = row[iw + j];
-              if ((unsigned)(iw + 4 + j) < (unsigned)W) u[j] = row[iw + 4 + j];
-            }
-          }
-          bf16x4s a0, a1;
-          a0[0] = (__bf16)v[1]; a0[1] = (__bf16)v[2]; a0[2] = (__bf16)v[3]; a0[3] = (__bf16)u[0];
-          a1[0] = a0[2]; a1[1] = a0[3]; a1[2] = (__bf16)u[1]; a1[3] = (__bf16)u[2];
-          *reinterpret_cast<bf16x4s*>(lds + (size_t)r * RPB + 8 * c4) = a0;
-          *reinterpret_cast<bf16x4s*>(lds + COPYB + (size_t)r * RPB + 8 * c4) = a1;
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ro = 0; ro < TH; ++ro) {
-      const int oh = oh0 + ro;
-      if (oh > r_last) break;
-      const bool row_ok = (unsigned)oh < (unsigned)Ho;
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        if (ow0 + hf * 2 * WPX >= Wo) break;                       // (uniform) nothing of this half exists
-        typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-        bf16x8s afrag[NG];
-        {
-          const unsigned a0 = abase[hf], a1 = a0 + (unsigned)hrow1, a7 = a0 + (unsigned)hrow7;
-          bf16x4v lo[NG], hi[NG];
-#define STEM_RD(g, base)                                                                                                            \
-          asm volatile("ds_read_b64 %0, %2 offset:%3\n\tds_read_b64 %1, %2 offset:%4"                                            \
-                       : "=&v"(lo[g]), "=&v"(hi[g])                                                                                  \
-                       : "v"(base), "n"(stem_row_of(2 * (g)) * RPB + ro * 2 * RPB), "n"(stem_row_of(2 * (g)) * RPB + ro * 2 * RPB + 8) \
-                       : "memory")
-          STEM_RD(0, a1); STEM_RD(1, a1); STEM_RD(2, a1); STEM_RD(3, a7); STEM_RD(4, a1); STEM_RD(5, a1);
-          STEM_RD(6, a1); STEM_RD(7, a1); STEM_RD(8, a1); STEM_RD(9, a1); STEM_RD(10, a0);
-#undef STEM_RD
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int g = 0; g < NG; ++g) afrag[g] = __builtin_shufflevector(lo[g], hi[g], 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[g], bfrag[g], g == 0 ? zero : acc, 0, 0, 0);
-        // BatchNorm + ReLU as the unfused kernel stores them (before its bf16 rounding); missing rows / columns count as 0
-        const int col0 = ow0 + hf * 2 * WPX + mi * WPX + 4 * h;    // stem column of register 0 of this lane
-        float v[16];
-        if (row_ok && all_cols) {                                  // (uniform) interior strip: no per-element predicate
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = fmaxf(fmaf(acc[r], sc, sh), 0.f);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const bool ok = row_ok && (unsigned)(col0 + (r & 3) + 8 * (r >> 2)) < (unsigned)Wo;
-            v[r] = ok ? fmaxf(fmaf(acc[r], sc, sh), 0.f) : 0.f;
-          }
-        }
-        float hm[8], xl[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) xl[g] = __shfl_xor(v[4 * g + 3], 32);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float l0 = h ? xl[g] : (g > 0 ? xl[g - 1] : 0.f);
-          hm[2 * g] = fmaxf(fmaxf(l0, v[4 * g]), v[4 * g + 1]);
-          hm[2 * g + 1] = fmaxf(fmaxf(v[4 * g + 1], v[4 * g + 2]), v[4 * g + 3]);
-        }
-        if (oh & 1) {                                              // stem row 2p+1 completes pooled row p (uniform branch)
-          const int pr = (oh - 1) >> 1;
-          if (pr >= p0 && pr < p1) {
-            // this wave's 16 pooled pixels x 32 channels through its transpose tile (see TPITCH): lane (l31, h) holds channel l31 of
-            // pixels 4 (c >> 1) + (c & 1) + 2 h; lane (pixel = lane >> 2, piece = lane & 3) then stores 8 channels of one pixel
-            char* const tt = lds + 2 * COPYB + (wave * 2 + hf) * TTILE;
-#pragma unroll
-            for (int c = 0; c < 8; ++c)
-              *reinterpret_cast<__bf16*>(tt + (4 * (c >> 1) + (c & 1) + 2 * h) * TPITCH + 2 * l31) =
-                  (__bf16)fmaxf(fmaxf(prev2[hf][c], prev1[hf][c]), hm[c]);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const int px = lane >> 2, piece = lane & 3;
-            const u32x4 q = *reinterpret_cast<const u32x4*>(tt + px * TPITCH + piece * 16);
-            const int cc = ow0 + hf * 2 * WPX + mi * WPX + 2 * px;      // stem column of the window centre (even); pixel 0 is the left neighbour's
-            if (px != 0 && cc >= 0 && (cc >> 1) < Wp)
-              *reinterpret_cast<u32x4*>(y + ((size_t)(n * Hp + pr) * Wp + (cc >> 1)) * 64 + ni * 32 + piece * 8) = q;
-            asm volatile("" ::: "memory");
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { prev2[hf][i] = prev1[hf][i]; prev1[hf][i] = hm[i]; }
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void stem_pack_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 64 * KP) return;
-  const int ch = i / KP, k = i - ch * KP, r = k >> 3, kw = k & 7;
-  float v = 0.f;
-  if (r < 21 && kw < 7) v = w[(ch * 21 + r) * 7 + kw];
-  out[i] = (__bf16)v;
-}
-
-}  // namespace
 
 // Packs the fp32 OIHW stem filter (64,3,7,7) into the bf16 [64][176] bank of the bf16 stem: k = (c*7+kh)*8 + kw.
 extern "C" int bevf_stem_pack_bf16(const float* w_oihw, void* packed, void* stream) {
@@ -1086,43 +1013,27 @@ extern "C" int bevf_stem_pack_bf16(const float* w_oihw, void* packed, void* stre
 
 extern "C" int bevf_stem_conv7x7_bf16mma(const float* x, const void* w_packed, const float* scale, const float* shift, void* y,
                                          int N, int H, int W, int relu, void* stream) {
-  BEVF_REQUIRE(x && w_packed && scale && shift && y, "stem bf16: null pointer");
-  BEVF_REQUIRE(bevf_aligned16(w_packed) && bevf_aligned16(y), "stem bf16: unaligned");
-  BEVF_REQUIRE(N > 0 && H >= 1 && W >= 1, "stem bf16: empty shape");
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  const int tilesW = (Wo + TP - 1) / TP, tilesH = (Ho + TH - 1) / TH;
-  const long long grid = (long long)N * tilesH * tilesW;
-  BEVF_REQUIRE(grid < (1ll << 31), "stem bf16: grid too large");
+  if (const int rc = stem_check("stem bf16", x, w_packed, scale, shift, y, true, N, H, W)) return rc;
+  const StemDims d(H, W);
+  const long long grid = (long long)N * d.tilesH * d.tilesW;
+  if (const int rc = stem_grid("stem bf16", grid)) return rc;
   return bevf_launch("bevf_stem_conv7x7_bf16mma", stem_conv7x7_bf16mma<__bf16>, dim3((unsigned)grid), dim3(256), kStemBf16Lds,
                      static_cast<hipStream_t>(stream), x, static_cast<const __bf16*>(w_packed), scale, shift,
-                     static_cast<__bf16*>(y), H, W, Ho, Wo, tilesW, tilesH, relu);
+                     static_cast<__bf16*>(y), H, W, d.Ho, d.Wo, d.tilesW, d.tilesH, relu);
 }
 
 // bf16 stem + max-pool fused (fp32 image in, bf16 pooled NHWC out [N][Hp][Wp][64]); bit-identical to
 // bevf_stem_conv7x7_bf16mma (relu) followed by bevf_maxpool3x3s2_nhwc_bf16
 extern "C" int bevf_stem_pool_bf16mma(const float* x, const void* w_packed, const float* scale, const float* shift, void* y, int N,
                                       int H, int W, void* stream) {
-  BEVF_REQUIRE(x && w_packed && scale && shift && y, "stem_pool bf16: null pointer");
-  BEVF_REQUIRE(bevf_aligned16(w_packed), "stem_pool bf16: packed filter bank must be 16-byte aligned");
-  BEVF_REQUIRE(N > 0 && H >= 1 && W >= 1, "stem_pool bf16: empty shape");
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  const int Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-  const int tilesW = (Wp + TPS / 2 - 1) / (TPS / 2);
-  // segments of pooled rows: fewest (rounds of 768 resident workgroups: 44 KB of LDS each) x (chunks of 4 stem rows per workgroup)
-  int best_seg = 1;
-  long long best_cost = -1;
-  for (int ns = 1; ns <= 32 && ns <= Hp; ++ns) {
-    const int rps = (Hp + ns - 1) / ns, real = (Hp + rps - 1) / rps;
-    const long long wgs = (long long)N * tilesW * real;
-    const long long cost = ((wgs + 767) / 768) * ((2 * rps + 1 + TH - 1) / TH);
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_seg = real; }
-  }
-  const int rps = (Hp + best_seg - 1) / best_seg, nseg = (Hp + rps - 1) / rps;
-  const long long grid = (long long)N * tilesW * nseg;
-  BEVF_REQUIRE(grid < (1ll << 31), "stem_pool bf16: grid too large");
-  // BEVF_STEM_BF16_EXPAND=1: the round-2 kernel (column tile expanded in LDS), kept for A/B; default: fragments straight from the patch
+  if (const int rc = stem_check("stem_pool bf16", x, w_packed, scale, shift, y, false, N, H, W)) return rc;
+  const StemDims d(H, W);
+  const PoolSegments sg = pool_segments(N, d.stripsW, d.Hp, 768);            // 44 KB of LDS each: 3 per CU
+  const long long grid = (long long)N * d.stripsW * sg.nseg;
+  if (const int rc = stem_grid("stem_pool bf16", grid)) return rc;
+  // BEVF_STEM_BF16_EXPAND=1: the kernel that expands a column tile in LDS, kept for A/B; default: fragments straight from the patch
   static const bool expand = getenv("BEVF_STEM_BF16_EXPAND") != nullptr;
   return bevf_launch("bevf_stem_pool_bf16mma", expand ? stem_pool7x7_bf16mma : stem_pool7x7_bf16v2, dim3((unsigned)grid), dim3(256),
                      expand ? kStemBf16Lds : kStemBf16V2Lds, static_cast<hipStream_t>(stream), x, static_cast<const __bf16*>(w_packed), scale,
-                     shift, static_cast<__bf16*>(y), H, W, Ho, Wo, Hp, Wp, tilesW, nseg, rps);
+                     shift, static_cast<__bf16*>(y), H, W, d.Ho, d.Wo, d.Hp, d.Wp, d.stripsW, sg.nseg, sg.rps);
 }

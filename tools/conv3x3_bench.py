@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """A/B of the bf16 3x3 / stride 1 layers: bevf_conv3x3_bf16 (csrc/conv3x3_bf16.hip) against the implicit-GEMM bf16 kernel it
 replaces (bevf_conv2d_nhwc_bf16), interleaved rounds in one process, random post-ReLU-like data, on the layer shapes of
-BASELINE configs 3 (B = 8) and 5 (B = 2).  usage: conv3x3_bench.py [names] [rounds]"""
+BASELINE configs 3 (B = 8) and 5 (B = 2).  usage: conv3x3_bench.py [names] [rounds]   (BEVF_AB_LIB=<other .so> for an A/B against another
+build of the library)"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from bevfusion_multimodal_3d_object_detection_amd import _lib as L
+if os.environ.get("BEVF_AB_LIB"): L.LIB_PATH = os.environ["BEVF_AB_LIB"]
 
 SHAPES = {  # name: (N, H, W, Cin, Cout, residual)
     "layer1": (48, 225, 400, 64, 64, True),

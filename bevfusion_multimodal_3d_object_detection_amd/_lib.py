@@ -229,6 +229,15 @@ SIGNATURES = {
     "bevf_csr_lift_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
                               + [C.c_int] * 2 + [C.c_void_p]),
+    "bevf_frustum_table_sort_wave_rows": (C.c_int, []),
+    "bevf_frustum_table_work_elems": (C.c_size_t, [C.c_int] * 7),
+    "bevf_frustum_table_build_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_int] * 2 + [C.c_float] * 2
+                                     + [C.c_int, C.c_double, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 5),
+    "bevf_frustum_pool_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_frustum_pool_bwd_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                            C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                            C.c_size_t] + [C.c_int] * 2 + [C.c_void_p]),
 }
 
 
@@ -1359,3 +1368,63 @@ def csr_lift_bwd(t_row_ptr, t_cell, t_bin, t_w, npix: int, P: int, D: int, x, x_
     _call("bevf_csr_lift_bwd_f32", _pc(t_row_ptr, torch.int32), _pc(t_cell, torch.int32) if nnz else None,
           _pc(t_bin, torch.int32) if nnz else None, _pc(t_w) if nnz else None, npix, D, _p(x), x_bs, x_cs, _p(pd), pd_bs, _p(dy),
           dy_bs, dy_cs, _p(dx), dx_bs, dx_cs, _p(dpd), dpd_bs, B, C)
+
+
+def frustum_table_sort_wave_rows() -> int:
+    """Longest row that frustum_table_build sorts with one wave; longer rows are sorted by a whole workgroup (the sort's only
+    row-length threshold)."""
+    return int(lib().bevf_frustum_table_sort_wave_rows())
+
+
+def frustum_table_work_elems(B: int, ncam: int, bev_h: int, bev_w: int, D: int, Hc: int, Wc: int) -> int:
+    """int32 elements of frustum_table_build's work buffer."""
+    return int(lib().bevf_frustum_table_work_elems(B, ncam, bev_h, bev_w, D, Hc, Wc))
+
+
+def frustum_table_build(calib, B: int, ncam: int, grid: Sequence[float], bev_h: int, bev_w: int, z_range: Sequence[float], D: int,
+                        depth_min: float, depth_max: float, image_size: Sequence[int], Hc: int, Wc: int, cell_of, row_ptr, col2,
+                        work) -> None:
+    """The frustum tables of B frames from calib [B][ncam][4][4] fp64 on the device (bevf_frustum_table_build_f64): cell_of
+    [B][ncols * D], row_ptr [B][P + 1], col2 [B][ncols * D] with every row ascending.  grid = (x0, y0, vx, vy) of
+    encoders.pillar_grid, z_range = (z0, z1), image_size = (H, W)."""
+    _depth_bins("frustum_table_build", D)
+    P, cap = bev_h * bev_w, ncam * Hc * Wc * D
+    _need("frustum_table_build", calib=(calib, B * ncam * 16), cell_of=(cell_of, B * cap), row_ptr=(row_ptr, B * (P + 1)),
+          col2=(col2, B * cap), work=(work, frustum_table_work_elems(B, ncam, bev_h, bev_w, D, Hc, Wc)))
+    _call("bevf_frustum_table_build_f64", _pc(calib, torch.float64), B, ncam, *(float(v) for v in grid), bev_h, bev_w,
+          float(z_range[0]), float(z_range[1]), D, float(depth_min), float(depth_max), int(image_size[0]), int(image_size[1]), Hc, Wc,
+          _pc(cell_of, torch.int32), _pc(row_ptr, torch.int32), _pc(col2, torch.int32), _pc(work, torch.int32))
+
+
+def frustum_pool(row_ptr, col2, tables: int, cap: int, nrows: int, ncols: int, D: int, x, x_bs: int, x_cs: int, pd, pd_bs: int, y,
+                 y_bs: int, y_cs: int, B: int, C: int) -> None:
+    """y[b][r][0:C] = sum_e pd[b][col2[e]] * x[b][col2[e] // D][0:C] over row r of frame b's table (bevf_frustum_pool_f32).  tables
+    = B: row_ptr [B][nrows + 1], col2 [B][cap]; tables = 1: one table shared by all frames (stride 0)."""
+    _depth_bins("frustum_pool", D)
+    if tables not in (1, B) or cap <= 0:
+        raise BevfError(f"frustum_pool: {tables} tables for {B} frames (1 or B), capacity {cap}")
+    _need("frustum_pool", row_ptr=(row_ptr, tables * (nrows + 1)), col2=(col2, tables * cap),
+          x=(x, (B - 1) * x_bs + _strided(ncols, C, x_cs)), pd=(pd, (B - 1) * pd_bs + ncols * D),
+          y=(y, (B - 1) * y_bs + _strided(nrows, C, y_cs)))
+    if x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("frustum_pool: x and y share storage")
+    shared = tables == 1 and B > 1
+    _call("bevf_frustum_pool_f32", _pc(row_ptr, torch.int32), 0 if shared else nrows + 1, _pc(col2, torch.int32), 0 if shared else cap,
+          nrows, D, _p(x), x_bs, x_cs, _p(pd), pd_bs, _p(y), y_bs, y_cs, B, C)
+
+
+def frustum_pool_bwd(cell_of, tables: int, npix: int, P: int, D: int, x, x_bs: int, x_cs: int, pd, pd_bs: int, dy, dy_bs: int,
+                     dy_cs: int, dx, dx_bs: int, dx_cs: int, dpd, dpd_bs: int, B: int, C: int) -> None:
+    """The pool's dense backward (bevf_frustum_pool_bwd_f32): dx [b][pix][0:C] and dpd [b][pix][0:D], every element written once;
+    cell_of [tables][npix * D] with tables = B, or 1 for a table shared by all frames.  cell_of < P by construction."""
+    _depth_bins("frustum_pool_bwd", D)
+    if tables not in (1, B):
+        raise BevfError(f"frustum_pool_bwd: {tables} tables for {B} frames (1 or B)")
+    _need("frustum_pool_bwd", cell_of=(cell_of, tables * npix * D), x=(x, (B - 1) * x_bs + _strided(npix, C, x_cs)),
+          pd=(pd, (B - 1) * pd_bs + npix * D), dy=(dy, (B - 1) * dy_bs + _strided(P, C, dy_cs)),
+          dx=(dx, (B - 1) * dx_bs + _strided(npix, C, dx_cs)), dpd=(dpd, (B - 1) * dpd_bs + npix * D))
+    for name, t in (("x", x), ("dy", dy)):
+        if t.untyped_storage().data_ptr() == dx.untyped_storage().data_ptr():
+            raise BevfError(f"frustum_pool_bwd: {name} and dx share storage")
+    _call("bevf_frustum_pool_bwd_f32", _pc(cell_of, torch.int32), 0 if tables == 1 and B > 1 else npix * D, npix, D, _p(x), x_bs, x_cs,
+          _p(pd), pd_bs, _p(dy), dy_bs, dy_cs, _p(dx), dx_bs, dx_cs, _p(dpd), dpd_bs, B, C)

@@ -17,7 +17,8 @@ This module reads that section and applies the BEVFusion-style pair -- one world
   image is bit-equal to `preprocess.preprocess_camera_images`.
 
 Random numbers are drawn on the host from a `numpy.random.Generator` (a few dozen scalars per step); the radar noise is `torch.randn`
-on the device.  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' camera branch.  No CPU fallback.
+on the device.  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' and 'frustum' camera branches.  No
+CPU fallback.
 """
 from __future__ import annotations
 
@@ -421,7 +422,9 @@ def augmented_calib(base, params: AugmentParams, image_size: Optional[Tuple[int,
     """The fp64 (B, ncam, 4, 4) `camera_calib=` tensor of the augmented batch: rows 0-2 = A . (K . E[0:3]) . T^-1, row 3 =
     E[2] . T^-1 -- `camera_rig.calib_matrices` of the rig with K' = A . K and cam_to_bev' = T . cam_to_bev.  base: a CameraRig (every
     frame), a sequence of B rigs, or a calib_matrices array / tensor (then image_size = the (H, W) its intrinsics refer to is
-    needed; default the default rig's).  Returns a torch tensor (on base's device when base is a tensor)."""
+    needed; default the default rig's).  Returns a torch tensor (on base's device when base is a tensor).  The last row of every
+    image map A is (0, 0, 1), so row 2 of the result equals its depth row 3 -- what the 'frustum' branch relies on: its frustum
+    points are then bev_aug[b] applied to the base rig's."""
     dev = None
     if isinstance(base, CR.CameraRig):
         base = [base] * params.B

@@ -21,7 +21,7 @@ import numpy as np
 
 # the reference's camera order (ref src/train_detect.py:134-135): the order of the camera axis of the image input
 CAM_ORDER = ("CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_FRONT_LEFT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_BACK_RIGHT")
-VIEW_TRANSFORMS = ("mean", "project", "lift")
+VIEW_TRANSFORMS = ("mean", "project", "lift", "frustum")
 DEFAULT_NUM_HEIGHTS = 8
 DEFAULT_MIN_DEPTH = 0.1
 DEFAULT_DEPTH_BINS, DEFAULT_DEPTH_MIN, DEFAULT_DEPTH_MAX = 32, 1.0, 65.0      # the 'lift' branch's uniform depth bins (metres)
@@ -142,7 +142,8 @@ def default_rig() -> CameraRig:
 def calib_matrices(rigs: Sequence[CameraRig]) -> np.ndarray:
     """fp64 [B, ncam, 4, 4] for a sequence of B rigs (one per frame; same image_size and camera count): per camera, with
     E = cam_to_bev^-1, rows 0-2 = K . E[0:3] and row 3 = E[2] -- a BEV point p = (x, y, z, 1) has depth row3 . p and pixel
-    (u, v) = (row0 . p, row1 . p) / (row2 . p).  The `camera_calib=` input of the 'project' branch (device table build)."""
+    (u, v) = (row0 . p, row1 . p) / (row2 . p).  The `camera_calib=` input of the 'project' and 'frustum' branches (device table
+    builds).  Row 2 equals row 3 because the last row of K is (0, 0, 1); the 'frustum' branch relies on that (frustum_points)."""
     rigs = list(rigs)
     if not rigs or not all(isinstance(r, CameraRig) for r in rigs):
         raise ValueError("calib_matrices: expected a non-empty sequence of camera_rig.CameraRig")
@@ -186,7 +187,7 @@ def jittered_rig(seed: int, rig: Optional[CameraRig] = None) -> CameraRig:
 
 
 def view_transform_kind(camera_view_transform: Optional[str] = None, config: Optional[Dict] = None) -> str:
-    """'lift', 'project' or 'mean' from the keyword, else `model.bev_fusion.camera_view_transform` of the config, else 'mean'
+    """'frustum', 'lift', 'project' or 'mean' from the keyword, else `model.bev_fusion.camera_view_transform` of the config, else 'mean'
     (any letter case); anything else raises."""
     t = camera_view_transform
     if t is None and config is not None:
@@ -195,7 +196,7 @@ def view_transform_kind(camera_view_transform: Optional[str] = None, config: Opt
         return "mean"
     k = str(t).strip().lower()
     if k not in VIEW_TRANSFORMS:
-        raise ValueError(f"camera_view_transform must be 'mean', 'project' or 'lift', got {t!r}")
+        raise ValueError(f"camera_view_transform must be 'mean', 'project' or 'lift' (or 'frustum'), got {t!r}")
     return k
 
 
@@ -212,7 +213,7 @@ def camera_bev_settings(config: Optional[Dict] = None) -> Tuple[int, float, Came
 
 
 def check_depth_settings(bins, depth_min, depth_max, min_depth: float = DEFAULT_MIN_DEPTH) -> Tuple[int, float, float]:
-    """(D, depth_min, depth_max) of the 'lift' branch's uniform bins, checked: D an integer in 1..64, 0 < min_depth <= depth_min <
+    """(D, depth_min, depth_max) of the 'lift' / 'frustum' branches' uniform bins, checked: D an integer in 1..64, 0 < min_depth <= depth_min <
     depth_max; ValueError otherwise."""
     if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= MAX_DEPTH_BINS:
         raise ValueError(f"camera_bev.depth: bins must be an integer in 1..{MAX_DEPTH_BINS}, got {bins!r}")
@@ -447,3 +448,83 @@ def apply_lift_table_fp64(t: LiftTable, feats: np.ndarray, pd: np.ndarray) -> np
     for b in range(B):
         np.add.at(out[b], rows, feats[b][pix] * (t.w64 * pd[b].reshape(-1)[t.col2])[:, None])
     return out
+
+
+# ---- the frustum table (lift-splat) ---------------------------------------------------------------------------------------------
+
+@dataclass
+class FrustumTable:
+    """The lift-splat map of camera_view_transform 'frustum': every (feature pixel, depth bin) col2 = pixel * D + bin lands in at
+    most one BEV cell.  cell_of int32 [ncols * D] (-1: outside the grid or the z range), and the same map as CSR by cell: row_ptr
+    int32 [P + 1], col2 int32, every row in ascending col2.  No weights: each entry counts 1.  points: the fp64 frustum points
+    [ncols * D][3] (host checks)."""
+    P: int
+    ncols: int
+    D: int
+    cell_of: np.ndarray
+    row_ptr: np.ndarray
+    col2: np.ndarray
+    points: np.ndarray
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col2.shape[0])
+
+
+def frustum_points(calib: np.ndarray, image_size, Hc: int, Wc: int, depth_bins: int, depth_min: float, depth_max: float) -> np.ndarray:
+    """fp64 [B][ncam * Hc * Wc * D][3]: the BEV-frame point of every (camera, feature pixel (x, y), depth bin d), index
+    (cam * Hc * Wc + y * Wc + x) * D + d, from calib [B][ncam][4][4] (calib_matrices / augment.augmented_calib): with rows 0-2 =
+    [A | t], the point of image position u = (x + 1/2) W / Wc - 1/2, v = (y + 1/2) H / Hc - 1/2 (the inverse of the 'project'
+    branch's u_f, v_f) at the bin's centre depth z_d = depth_min + (d + 1/2) (depth_max - depth_min) / D is
+    p = A^-1 (z_d (u, v, 1)^T - t).  This needs the calibration's third row to be its depth row (row 2 == row 3), which both
+    producers keep: the last row of K and of every image map is (0, 0, 1)."""
+    calib = np.asarray(calib, dtype=np.float64)
+    B, ncam = calib.shape[:2]
+    H, W = image_size
+    u = (np.arange(Wc, dtype=np.float64) + 0.5) * W / Wc - 0.5
+    v = (np.arange(Hc, dtype=np.float64) + 0.5) * H / Hc - 0.5
+    z = depth_min + (np.arange(depth_bins, dtype=np.float64) + 0.5) * (depth_max - depth_min) / depth_bins
+    ray = np.empty((Hc, Wc, depth_bins, 3), dtype=np.float64)
+    ray[..., 0] = u[None, :, None] * z
+    ray[..., 1] = v[:, None, None] * z
+    ray[..., 2] = z
+    ray = ray.reshape(-1, 3)
+    out = np.empty((B, ncam, ray.shape[0], 3), dtype=np.float64)
+    for b in range(B):
+        for c in range(ncam):
+            out[b, c] = (ray - calib[b, c, :3, 3]) @ np.linalg.inv(calib[b, c, :3, :3]).T
+    return out.reshape(B, -1, 3)
+
+
+def frustum_cells(points: np.ndarray, pc_range, bev_h: int, bev_w: int) -> np.ndarray:
+    """int32 cell i * bev_w + j of every point [..., 3], -1 when invalid: j = floor((p_x - x0) / vx), i = floor((p_y - y0) / vy)
+    with the fp32 grid values of encoders.pillar_grid taken in fp64; valid when 0 <= j < bev_w, 0 <= i < bev_h and z0 <= p_z < z1
+    (the fp32 z limits)."""
+    from .encoders import pillar_grid
+    x0, y0, vx, vy, _ = pillar_grid(pc_range, bev_h, bev_w)
+    z0, z1 = float(np.float32(pc_range[2])), float(np.float32(pc_range[5]))
+    with np.errstate(invalid="ignore"):
+        fj = np.floor((points[..., 0] - np.float64(x0)) / np.float64(vx))
+        fi = np.floor((points[..., 1] - np.float64(y0)) / np.float64(vy))
+        valid = (fj >= 0) & (fj < bev_w) & (fi >= 0) & (fi < bev_h) & (points[..., 2] >= z0) & (points[..., 2] < z1)
+    cell = np.where(valid, fi, 0).astype(np.int64) * bev_w + np.where(valid, fj, 0).astype(np.int64)
+    return np.where(valid, cell, -1).astype(np.int32)
+
+
+def build_frustum_table(rig: CameraRig, Hc: int, Wc: int, pc_range, bev_h: int, bev_w: int, depth_bins: int = DEFAULT_DEPTH_BINS,
+                        depth_min: float = DEFAULT_DEPTH_MIN, depth_max: float = DEFAULT_DEPTH_MAX) -> FrustumTable:
+    """The lift-splat table of rig's cameras (feature maps Hc x Wc each, D uniform depth bins) on the bev_h x bev_w grid of
+    pc_range, in fp64 from calib_matrices([rig]) -- what bevf_frustum_table_build_f64 builds per frame on the device
+    (frustum_points, frustum_cells)."""
+    D, depth_min, depth_max = check_depth_settings(depth_bins, depth_min, depth_max, min(DEFAULT_MIN_DEPTH, float(depth_min)))
+    P, ncols = bev_h * bev_w, rig.num_cameras * Hc * Wc
+    if ncols * D >= 2 ** 31:
+        raise ValueError(f"frustum table: {ncols} pixels x {D} bins do not fit int32 columns")
+    pts = frustum_points(calib_matrices([rig]), rig.image_size, Hc, Wc, D, depth_min, depth_max)[0]
+    cell_of = frustum_cells(pts, pc_range, bev_h, bev_w)
+    c2 = np.nonzero(cell_of >= 0)[0]
+    order = np.argsort(cell_of[c2], kind="stable")                                # by cell, ascending col2 inside a cell
+    row_ptr = np.zeros(P + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cell_of[c2], minlength=P), out=row_ptr[1:])
+    return FrustumTable(P, ncols, D, cell_of, row_ptr.astype(np.int32), c2[order].astype(np.int32), pts)
+

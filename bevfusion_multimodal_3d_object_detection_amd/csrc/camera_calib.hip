@@ -12,6 +12,7 @@
 // Frame b's entries live at [b * cap, b * cap + row_ptr[b][nrows]) of col / w, cap = the caller's per-frame capacity
 // (>= P * num_heights * ncam * 4, the worst case); only the used part is touched.  Frame offsets are 64-bit.
 #include "common.h"
+#include "scan_counts.h"
 
 namespace {
 
@@ -108,33 +109,6 @@ __global__ __launch_bounds__(64) void table_cells(const double* __restrict__ cal
     kept += __popcll(__ballot(key >= 0));
   }
   if (lane == 0) cnt[(long long)b * g.P + p] = kept;
-}
-
-// cnt [B][n] -> rp [B][n + 1], the exclusive prefix sums of each frame; one 1024-thread block per frame.
-__global__ __launch_bounds__(1024) void scan_counts(const int32_t* __restrict__ cnt, int n, int32_t* __restrict__ rp) {
-  __shared__ int part[1024];
-  const int t = (int)threadIdx.x;
-  const int32_t* c = cnt + (long long)blockIdx.x * n;
-  int32_t* r = rp + (long long)blockIdx.x * (n + 1);
-  const int chunk = (n + 1023) / 1024;
-  const long long lo64 = (long long)t * chunk;
-  const int lo = lo64 < n ? (int)lo64 : n, hi = lo + chunk < n ? lo + chunk : n;
-  int s = 0;
-  for (int k = lo; k < hi; ++k) s += c[k];
-  part[t] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int v = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int run = part[t] - s;
-  for (int k = lo; k < hi; ++k) {
-    r[k] = run;
-    run += c[k];
-  }
-  if (t == 1023) r[n] = part[t];
 }
 
 // One wave per (frame, cell): the cell's slots -> its CSR row.

@@ -94,3 +94,29 @@ __device__ __forceinline__ void store16(T* p, const float (&f)[vec16<T>::N]) {
     *reinterpret_cast<bf16x8_t*>(p) = v;
   }
 }
+
+// ---- helpers of the CSR pool / lift kernels (camera_lift.hip, camera_frustum.hip) ---------------------------------
+// n / d for 0 <= n < 2^31 by multiply-high (mul == 0: d == 1); on wave-uniform operands this stays on the scalar unit
+__device__ __forceinline__ int div_by(int n, unsigned mul, unsigned sh) {
+  return mul ? (int)(__umulhi((unsigned)n, mul) >> sh) : n;
+}
+static inline void div_make(int d, unsigned* mul, unsigned* sh) {
+  *mul = 0;
+  *sh = 0;
+  if (d <= 1) return;
+  int s = 0;
+  while ((1ll << s) < d) ++s;
+  *mul = (unsigned)(((1ull << (31 + s)) + (unsigned long long)d - 1) / (unsigned long long)d);
+  *sh = (unsigned)(s - 1);
+}
+
+// Sum / max over the L lanes (a power of two, aligned) that hold one row: xor butterfly, widest stride first.  IEEE addition is
+// commutative, so both lanes of a pair compute the same bits and every lane of the group ends with the same value.
+template <bool MAX>
+__device__ __forceinline__ float group_reduce(float v, int L) {
+  for (int m = L >> 1; m > 0; m >>= 1) {
+    const float o = __shfl_xor(v, m, 64);
+    v = MAX ? fmaxf(v, o) : v + o;
+  }
+  return v;
+}

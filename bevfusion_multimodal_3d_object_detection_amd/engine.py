@@ -705,6 +705,87 @@ def frame_camera_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int
     return eng._frame_tables
 
 
+class FrustumTables:
+    """The lift-splat tables of the 'frustum' branch (camera_rig.FrustumTable) on the device, built there from a [B][ncam][4][4] fp64
+    calibration tensor (bevf_frustum_table_build_f64): cell_of [B][ncols * D] for the backward, row_ptr [B][P + 1] / col2
+    [B][ncols * D] for the forward -- the capacity is exact, there are no weights.  Per-frame tables (own = False) live in grow-only
+    buffers of the fusion's engine: no host synchronisation and no allocation once they exist, so build and pool run inside a graph
+    capture; `version` counts the builds as FrameCameraTables does.  The module rig's table (own = True) is the same build with
+    B = 1 into tensors of its own, cached beside the other rig tables and applied to every frame with stride 0."""
+
+    def __init__(self, eng: "_Engine", own: bool = False):
+        self.eng, self.own = eng, own
+        self.version = 0
+
+    def _buf(self, name: str, numel: int, dev) -> torch.Tensor:
+        return torch.empty(numel, dtype=torch.int32, device=dev) if self.own else self.eng.buf(name, numel, torch.int32)
+
+    def build(self, calib: torch.Tensor, image_size, B: int, ncam: int, Hc: int, Wc: int) -> None:
+        import numpy as np
+        from .encoders import pillar_grid
+        m = self.eng.module
+        self.D, dmin, dmax = m.cam_depth
+        self.tables, self.P, self.ncols = B, m.bev_h * m.bev_w, ncam * Hc * Wc
+        self.cap = cap = self.ncols * self.D
+        dev = calib.device
+        self.cell_of = self._buf("ft_cell_of", B * cap, dev)
+        self.row_ptr = self._buf("ft_row_ptr", B * (self.P + 1), dev)
+        self.col2 = self._buf("ft_col2", B * cap, dev)
+        work = self._buf("ft_work", L.frustum_table_work_elems(B, ncam, m.bev_h, m.bev_w, self.D, Hc, Wc), dev)
+        x0, y0, vx, vy, _ = pillar_grid(m.pc_range, m.bev_h, m.bev_w)
+        z = (float(np.float32(m.pc_range[2])), float(np.float32(m.pc_range[5])))
+        L.frustum_table_build(calib, B, ncam, (x0, y0, vx, vy), m.bev_h, m.bev_w, z, self.D, dmin, dmax, image_size, Hc, Wc,
+                              self.cell_of, self.row_ptr, self.col2, work)
+        self.version += 1
+
+    def invalidate(self) -> None:
+        """The buffers are about to be rewritten by launches this object does not see (a graph replay of a captured build)."""
+        self.version += 1
+
+    def pool(self, x, pd, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
+        """y[b][cell][0:C] (row stride y_cs) = sum over the cell's (pix, d) of pd[b][pix][d] x[b][pix][0:C]: x NHWC features
+        [B][ncols][C], pd the depth distribution [B][ncols][D]."""
+        L.frustum_pool(self.row_ptr, self.col2, self.tables, self.cap, self.P, self.ncols, self.D, x, self.ncols * C, C, pd,
+                       self.ncols * self.D, y, self.P * (y_cs or C), y_cs or C, B, C)
+
+    def pool_backward(self, x, pd, dy, dx, dpd, B: int, C: int) -> None:
+        """dx [B][ncols][C] and dpd [B][ncols][D] from dy [B][P][C]: every element of both written once."""
+        L.frustum_pool_bwd(self.cell_of, self.tables, self.ncols, self.P, self.D, x, self.ncols * C, C, pd, self.ncols * self.D, dy,
+                           self.P * C, C, dx, self.ncols * C, C, dpd, self.ncols * self.D, B, C)
+
+
+def camera_frustum_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> FrustumTables:
+    """The frustum table of FlexibleBEVFusion `fus`'s own rig for ncam cameras of Hc x Wc features: built on the device with B = 1
+    on first use (outside a graph capture) and cached on the fusion's engine, next to the other rig tables, until set_camera_rig."""
+    _check_rig_cameras(fus, ncam)
+    rig, eng = fus.camera_rig, fus._eng()
+    key = ("frustum", rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_depth, str(dev))
+    tab = eng._camera_tables.get(key)
+    if tab is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.BevfError("BEV fusion: the camera frustum table is built on first use, which cannot happen inside a graph "
+                              "capture -- run the forward once before capturing")
+        from . import camera_rig as CR
+        tab = FrustumTables(eng, own=True)
+        tab.build(torch.from_numpy(CR.calib_matrices([rig])).to(dev), rig.image_size, 1, ncam, Hc, Wc)
+        eng._camera_tables[key] = tab
+    return tab
+
+
+def frame_frustum_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev) -> FrustumTables:
+    """The per-frame frustum tables of FlexibleBEVFusion `fus` for camera_calib = (fp64 [B, ncam, 4, 4] tensor, image_size) as
+    FlexibleBEVFusion.camera_calib_tensor returns it, built now on the current stream."""
+    calib, image_size = camera_calib
+    if tuple(calib.shape) != (B, ncam, 4, 4):
+        raise L.BevfError(f"BEV fusion: camera_calib is {tuple(calib.shape)} but the camera features are {B} frames of {ncam} cameras")
+    _check_rig_cameras(fus, ncam)
+    eng = fus._eng()
+    if eng._frustum_tables is None:
+        eng._frustum_tables = FrustumTables(eng)
+    eng._frustum_tables.build(calib.to(dev).contiguous(), image_size, B, ncam, Hc, Wc)
+    return eng._frustum_tables
+
+
 def concat_slots(fus: nn.Module, branches, feats, text: str, B: Optional[int] = None):
     """-> ((branch, input) of every modality that has both, in slot order [camera, LiDAR, radar]; channels of the concatenated map,
     checked against bev_fusion's first conv; frames B, the first input's leading dimension unless given).  text: the mismatch
@@ -787,20 +868,49 @@ class CameraLiftBranch(_CameraBranch):
         self.dn = _finish_pack(w.permute(0, 2, 3, 1).contiguous().view(-1), torch.ones(self.Dp, device=w.device), b, Cc, self.Dp,
                                1, 1, 0, False, split_ok=False, wino_ok=False)
 
+    def depth_distribution(self, cam, N: int, Hc: int, Wc: int) -> torch.Tensor:
+        """Pd [N * Hc * Wc][D] = softmax over the depth bins of depth_net's logits, for N feature maps."""
+        rows = N * Hc * Wc
+        logits = self.eng.buf("lift_logits", rows * self.Dp)
+        _run_conv(self.dn, cam, logits, N, Hc, Wc)
+        pd = self.eng.buf("lift_pd", rows * self.D)
+        with _span("cam_lift_softmax", nbytes=4.0 * rows * (self.Dp + self.D)):
+            L.softmax_rows(logits, self.Dp, pd, self.D, rows, self.D)
+        return pd
+
     def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
         _, ncam, Hc, Wc = geom
         buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
         m.check_lift_supported(camera_calib)
         tab = camera_lift_table(m, ncam, Hc, Wc, cam.device)
         rows = B * ncam * Hc * Wc
-        logits = buf("lift_logits", rows * self.Dp)
-        _run_conv(self.dn, cam, logits, B * ncam, Hc, Wc)
-        pd = buf("lift_pd", rows * self.D)
-        with _span("cam_lift_softmax", nbytes=4.0 * rows * (self.Dp + self.D)):
-            L.softmax_rows(logits, self.Dp, pd, self.D, rows, self.D)
+        pd = self.depth_distribution(cam, B * ncam, Hc, Wc)
         proj = buf("cam_proj", B * Sh * Sw * Cc)
         with _span("cam_lift", nbytes=4.0 * B * (Cc * (ncam * Hc * Wc + Sh * Sw) + rows * self.D // B)):
             tab.lift(cam, pd, proj, B, Cc)
+        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
+        _run_conv(self.c1, proj, t1, B, Sh, Sw)
+        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+
+
+class CameraFrustumBranch(CameraLiftBranch):
+    """Lift-splat: depth_net and softmax as in 'lift', then the pool over the frustum table -- the module rig's,
+    built on the device once and shared by every frame, or per-frame tables built here from camera_calib into the engine's buffers
+    -- and camera_proj on the BEV grid, its second conv into the concat slice.  fp32."""
+
+    def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
+        _, ncam, Hc, Wc = geom
+        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
+        m.check_frustum_supported()
+        if camera_calib is None:
+            tab = camera_frustum_table(m, ncam, Hc, Wc, cam.device)
+        else:
+            with _span("cam_frustum_table"):
+                tab = frame_frustum_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
+        pd = self.depth_distribution(cam, B * ncam, Hc, Wc)
+        proj = buf("cam_proj", B * Sh * Sw * Cc)
+        with _span("cam_frustum_pool", nbytes=4.0 * B * (Cc * (tab.ncols + Sh * Sw) + tab.ncols * self.D)):
+            tab.pool(cam, pd, proj, B, Cc)
         t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
         _run_conv(self.c1, proj, t1, B, Sh, Sw)
         _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
@@ -889,13 +999,14 @@ class RadarBranch(_FusionBranch):
 
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
-    BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, lift=CameraLiftBranch, pointnet=LidarVectorBranch,
-                    pillars=LidarPillarsBranch)
+    BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, lift=CameraLiftBranch, frustum=CameraFrustumBranch,
+                    pointnet=LidarVectorBranch, pillars=LidarPillarsBranch)
 
     def __init__(self, module: nn.Module):
         super().__init__(module)
         self._camera_tables: Dict[tuple, CameraTable] = {}
         self._frame_tables: Optional[FrameCameraTables] = None
+        self._frustum_tables: Optional[FrustumTables] = None
         m = module
         self.branches = [self.BRANCHES[m.camera_view_transform](self) if m.use_camera else None,
                          self.BRANCHES[m.lidar_kind](self) if m.use_lidar else None, RadarBranch(self) if m.use_radar else None]
@@ -904,8 +1015,10 @@ class FusionEngine(_Engine):
         self._camera_tables.clear()
 
     def invalidate_frame_tables(self) -> None:
-        """A graph replay is about to rebuild the per-frame tables (FrameCameraTables.invalidate)."""
-        self._frame_tables.invalidate()
+        """A graph replay is about to rebuild the per-frame tables (FrameCameraTables.invalidate, FrustumTables.invalidate)."""
+        for tables in (self._frame_tables, self._frustum_tables):
+            if tables is not None:
+                tables.invalidate()
 
     def pack(self) -> None:
         m = self.module
@@ -918,7 +1031,7 @@ class FusionEngine(_Engine):
             lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor], camera_calib=None) -> Tuple[torch.Tensor, int]:
         """cam: NHWC encoder features [B*ncam][Hc][Wc][C] with cam_geom = (B, ncam, Hc, Wc); lidar (B,1024), or with a
         PointPillars branch the NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype; radar (B,256).  camera_calib
-        ('project' branch): (fp64 [B, ncam, 4, 4], image_size) for per-frame tables built here, None = the module rig's table.
+        ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size) for per-frame tables built here, None = the module rig's table.
         Returns the fused NHWC map [B][S_h*S_w][bev_channels] and B."""
         self.ensure_packed()
         m = self.module

@@ -47,6 +47,12 @@ class FlexibleBEVFusion(nn.Module):
     deciding where along its ray a feature lands -- depth_net = Conv2d(camera_channels, D, 1) (this mode's only extra parameters),
     softmax over the D uniform depth bins of model.bev_fusion.camera_bev.depth, and every sample weighted by the probability of the
     bin its depth falls into; camera_proj on the BEV grid as in 'project'.  fp32 storage and the module's static rig only.
+    Extension (opt-in, camera_view_transform 'frustum'): lift-splat (Philion & Fidler 2020) -- the same depth_net
+    and softmax, but every (feature pixel, depth bin) is a point of its camera's frustum at the bin's centre depth, unprojected
+    through the calibration into the BEV cell it falls in, and a cell is the plain sum of Pd * feature over its points; camera_proj
+    on the BEV grid.  The frustum is a function of the calibration, so `camera_calib=` works as in 'project' (and takes what
+    augment.augment_batch returns); the module's rig serves every frame otherwise.  The calibration's third row must be its depth
+    row, as camera_rig.calib_matrices and augment.augmented_calib make it.  camera_bev.num_heights is unused.  fp32 storage only.
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -60,12 +66,13 @@ class FlexibleBEVFusion(nn.Module):
         config = _cfg(config, config_path)
         default_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
         self.lidar_kind = lidar_encoder_kind(lidar_encoder_type, config)
-        # camera branch: 'mean' (the reference's camera average + resize), 'project' (camera rig -> BEV grid) or 'lift' (+ learned depth)
+        # camera branch: 'mean' (the reference's camera average + resize), 'project' (camera rig -> BEV grid), 'lift' (+ learned depth)
+        # or 'frustum' (lift-splat: learned depth, push to the cell of the frustum point)
         self.camera_view_transform = CR.view_transform_kind(camera_view_transform, config)
         self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.DEFAULT_NUM_HEIGHTS, CR.DEFAULT_MIN_DEPTH, None
-        if self.camera_view_transform in ("project", "lift"):
+        if self.camera_view_transform in ("project", "lift", "frustum"):
             self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.camera_bev_settings(config)
-        if self.camera_view_transform == "lift":             # (depth bins D, depth_min, depth_max) of the learned depth distribution
+        if self.camera_view_transform in ("lift", "frustum"):   # (depth bins D, depth_min, depth_max) of the learned depth distribution
             self.cam_depth = CR.camera_lift_settings(config, self.cam_min_depth)
         pillars = self.lidar_kind == "pillars"
         if config is not None:
@@ -101,7 +108,7 @@ class FlexibleBEVFusion(nn.Module):
         bevc = self.bev_channels
         if self.use_camera:
             self.camera_proj = nn.Sequential(*_cbr(camera_channels, 512, 3), *_cbr(512, bevc, 1))
-            if self.camera_view_transform == "lift":         # per-pixel depth logits; exists in 'lift' mode only (state-dict keys)
+            if self.camera_view_transform in ("lift", "frustum"):   # per-pixel depth logits; these modes only (state-dict keys)
                 self.depth_net = nn.Conv2d(camera_channels, self.cam_depth[0], 1)
         if self.use_lidar and pillars:
             self.lidar_bev = nn.Sequential(*_cbr(lidar_channels, 128, 3), *_cbr(128, bevc, 3))
@@ -126,13 +133,13 @@ class FlexibleBEVFusion(nn.Module):
 
     @property
     def camera_rig(self) -> CR.CameraRig:
-        """The rig of the 'project' / 'lift' camera branch (camera_rig.default_rig() unless set)."""
+        """The rig of the 'project' / 'lift' / 'frustum' camera branch (camera_rig.default_rig() unless set)."""
         if self._camera_rig is None:
             self._camera_rig = CR.default_rig()
         return self._camera_rig
 
     def set_camera_rig(self, rig: "CR.CameraRig") -> None:
-        """Replace the camera rig of the 'project' / 'lift' branch; its projection tables are rebuilt on next use (outside a graph capture:
+        """Replace the camera rig of the 'project' / 'lift' / 'frustum' branch; its projection tables are rebuilt on next use (outside a graph capture:
         re-capture a GraphedDetector after a rig change).  The rig is fixed for every frame until the next call."""
         if not isinstance(rig, CR.CameraRig):
             raise TypeError(f"set_camera_rig: expected a camera_rig.CameraRig, got {type(rig).__name__}")
@@ -147,7 +154,7 @@ class FlexibleBEVFusion(nn.Module):
         if camera_calib is None:
             return None
         self.check_lift_supported(camera_calib)
-        if self.camera_view_transform != "project":
+        if self.camera_view_transform not in ("project", "frustum"):
             raise E.L.BevfError("camera_calib needs camera_view_transform='project': the 'mean' camera branch uses no calibration")
         if not B:                                                        # no camera input: nothing to calibrate
             return None
@@ -175,15 +182,22 @@ class FlexibleBEVFusion(nn.Module):
             raise E.L.BevfError(f"{self.depth_net.weight.dtype} storage with camera_view_transform='lift' is not supported: the "
                                 "learned-depth lift kernels are fp32 only (bf16 models: camera_view_transform='project' or 'mean')")
 
+    def check_frustum_supported(self) -> None:
+        """The 'frustum' branch runs in fp32 storage only; raises BevfError otherwise."""
+        if self.camera_view_transform == "frustum" and self.use_camera and self.depth_net.weight.dtype != torch.float32:
+            raise E.L.BevfError(f"{self.depth_net.weight.dtype} storage with camera_view_transform='frustum' is not supported: the "
+                                "lift-splat kernels are fp32 only (bf16 models: camera_view_transform='project' or 'mean')")
+
     def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib=None):
         """Internal fast path on NHWC camera features (no layout change); camera_calib as camera_calib_tensor returns it."""
         return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib)
 
     def forward(self, camera_features: Optional[torch.Tensor] = None, lidar_features: Optional[torch.Tensor] = None,
                 radar_features: Optional[torch.Tensor] = None, camera_calib=None) -> torch.Tensor:
-        """camera_calib ('project' branch only): per-frame calibration -- a sequence of B camera_rig.CameraRig or the float64
-        (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame."""
+        """camera_calib ('project' and 'frustum' branches): per-frame calibration -- a sequence of B camera_rig.CameraRig or the
+        float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame."""
         self.check_lift_supported(camera_calib)
+        self.check_frustum_supported()
         if camera_calib is not None:
             cf = camera_features if self.use_camera else None
             camera_calib = self.camera_calib_tensor(camera_calib, 0 if cf is None else cf.shape[0],
@@ -399,12 +413,13 @@ class FlexibleMultiModal3DDetector(nn.Module):
 
     def forward(self, camera_imgs: Optional[torch.Tensor] = None, lidar_points: Optional[torch.Tensor] = None,
                 radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None) -> Dict[str, torch.Tensor]:
-        """camera_calib (camera_view_transform='project' only): per-frame camera calibration -- a sequence of B
+        """camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame."""
         camera_calib = self.camera_calib_tensor(camera_imgs, camera_calib)
         if hasattr(self.fusion, "check_lift_supported"):
             self.fusion.check_lift_supported()
+            self.fusion.check_frustum_supported()
         if self.training and (torch.is_grad_enabled() or _any_bn_training(self)):
             # under no_grad a train-mode model still normalises with batch statistics and updates the running buffers, as torch does
             from . import training                      # train-mode BN + tape + hand-written backward (training.py)
@@ -495,8 +510,9 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
-    camera_view_transform: 'project' selects the camera -> BEV projection branch, 'mean' the reference's camera average (None: the
-    config's model.bev_fusion.camera_view_transform, else 'mean')."""
+    camera_view_transform: 'project' selects the camera -> BEV projection branch, 'lift' its learned-depth variant, 'frustum' the
+    lift-splat branch, 'mean' the reference's camera average (None: the config's model.bev_fusion.camera_view_transform, else
+    'mean')."""
     config = _cfg(config, config_path)
     if config is not None and modality_config is None:
         modality_config = config.get("model", {}).get("modality_config", "all")

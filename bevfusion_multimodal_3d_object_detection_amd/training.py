@@ -1114,6 +1114,52 @@ class CameraLiftBranchTape(_FusionBranchTape):
         return dcam
 
 
+class CameraFrustumBranchTape(_FusionBranchTape):
+    """Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net -> softmax over the depth bins -> the lift-splat pool over the
+    frustum table (the module rig's, or per-frame tables built here from calib = (fp64 [B, ncam, 4, 4], image_size)) -> camera_proj
+    on the grid, the slot copy.  Keeps x and Pd; the backward is the dense pool backward (dx and dPd in one pass over cell_of), the
+    softmax backward and depth_net's gradients, whose data gradient takes dx as its residual input.  Per-frame tables live in the
+    fusion engine's buffers: the tape keeps the calibration and the build's version and rebuilds them in its backward if another
+    forward has replaced them since (CameraProjectBranchTape)."""
+
+    def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
+        _, ncam, Hc, Wc = geom
+        fus, dev = self.fus, cam.device
+        fus.check_frustum_supported()
+        Cc = fus.camera_proj[0].weight.shape[1]
+        self.geom, self.calib = (ncam, Hc, Wc, Cc), None
+        if calib is None:
+            self.table = tab = E.camera_frustum_table(fus, ncam, Hc, Wc, dev)
+        else:
+            self.table = tab = E.frame_frustum_tables(fus, calib, B, ncam, Hc, Wc, dev)
+            self.calib, self.version = (calib[0].to(dev).clone(), calib[1]), tab.version
+        self.Dp = E.depth_net_width(tab.D)
+        rows = B * tab.ncols
+        self.padded = _PaddedDepthNet(fus.depth_net, self.Dp)
+        self.dn = ConvBNLayer(self.padded, None, relu=False)
+        logits, _, _ = self.dn.forward(cam, B * ncam, Hc, Wc)
+        self.x, self.pd = cam, _new(rows * tab.D, dev)
+        L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
+        proj = _new(B * self.H * self.W * Cc, dev)
+        tab.pool(cam, self.pd, proj, B, Cc)
+        self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
+
+    def backward(self, dconcat, sink):
+        dproj = self._pair_from_slot(dconcat, sink)
+        B, (ncam, Hc, Wc, Cc), dev = self.B, self.geom, dconcat.device
+        if self.calib is not None and self.table.version != self.version:
+            self.table = E.frame_frustum_tables(self.fus, self.calib, B, ncam, Hc, Wc, dev)
+            self.version = self.table.version
+        tab = self.table
+        rows = B * tab.ncols
+        dx, dpd = _new(rows * Cc, dev), _new(rows * tab.D, dev)
+        tab.pool_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # every element of both written once
+        dlogit = _new(rows * self.Dp, dev)
+        L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
+        dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
+        return dcam
+
+
 class LidarVectorBranchTape(_FusionBranchTape):
     """Input the PointNet vector (B*C_l): lidar_init to the start_size^2 canvas, conv, x2 bilinear, conv, resize to the grid."""
 
@@ -1178,7 +1224,7 @@ class FusionTape:
     callback, after radar and LiDAR have contributed theirs."""
 
     BRANCHES = dict(mean=CameraMeanBranchTape, project=CameraProjectBranchTape, lift=CameraLiftBranchTape,
-                    pointnet=LidarVectorBranchTape, pillars=LidarPillarsBranchTape)
+                    frustum=CameraFrustumBranchTape, pointnet=LidarVectorBranchTape, pillars=LidarPillarsBranchTape)
 
     def __init__(self, fus):
         self.fus = fus
@@ -1186,7 +1232,7 @@ class FusionTape:
                          self.BRANCHES[fus.lidar_kind](fus) if fus.use_lidar else None, RadarBranchTape(fus) if fus.use_radar else None]
 
     def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None):
-        """camera_calib ('project' branch): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape."""
+        """camera_calib ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape."""
         fus = self.fus
         self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
         feats = (cam_feat, lid_feat, rad_feat)

@@ -482,6 +482,55 @@ int bevf_csr_lift_bwd_f32(const int32_t* t_row_ptr, const int32_t* t_cell, const
                           size_t dy_bs, int dy_cs, float* dx, size_t dx_bs, int dx_cs, float* dpd, size_t dpd_bs, int B,
                           int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Lift-splat camera -> BEV view transform (csrc/camera_frustum.hip): the opt-in camera branch
+ * `model.bev_fusion.camera_view_transform: frustum` (Philion & Fidler 2020, BEVFusion's bev_pool).  None of
+ * these has a counterpart in the reference (it has no view transform at all).  fp32 features, fp64 geometry, stream-ordered,
+ * capture-safe (nothing allocated, no host synchronisation), every output element written exactly once, two launches give
+ * the same bits.  D = depth bins, 1 <= D <= 64; ncols = ncam * Hc * Wc feature pixels, pix = cam * Hc * Wc + y * Wc + x,
+ * col2 = pix * D + d; P = bev_h * bev_w cells, cell = i * bev_w + j.
+ *
+ * bevf_frustum_table_build_f64.  calib [B][ncam][4][4] fp64 as camera_rig.calib_matrices / augment.augmented_calib make it:
+ * rows 0-2 = [A | t], row 3 the depth row.  THE THIRD ROW MUST EQUAL THE DEPTH ROW (both producers keep it so: the last row
+ * of K and of every image map is (0, 0, 1)); the entry point relies on it and does not read row 3.  Feature pixel (x, y)
+ * sits at the image point u = (x + 1/2) img_w / Wc - 1/2, v = (y + 1/2) img_h / Hc - 1/2; bin d has the centre depth
+ * z_d = depth_min + (d + 1/2) (depth_max - depth_min) / D; the frustum point is p = A^-1 (z_d (u, v, 1)^T - t), with A^-1
+ * taken once per (frame, camera); j = floor((p_x - x0) / vx), i = floor((p_y - y0) / vy) with x0, y0, vx, vy =
+ * encoders.pillar_grid's fp32 values; the point is valid when 0 <= j < bev_w, 0 <= i < bev_h and z0 <= p_z < z1.  Output, per
+ * frame b: cell_of [B][ncols * D] (the cell of col2, -1 when invalid); row_ptr [B][P + 1] (offsets within the frame) and the
+ * frame's entries at col2 [b * ncols * D ...], EVERY ROW IN ASCENDING col2; the capacity per frame is exactly ncols * D and
+ * there are no weights (each is 1).  Integer atomics count the rows and hand out cursor positions; every row is then sorted
+ * from LDS -- one wave per row up to bevf_frustum_table_sort_wave_rows() entries, the whole workgroup streaming the row
+ * through LDS beyond (time grows with the square of the row length) -- so the order does not depend on them.  work:
+ * bevf_frustum_table_work_elems(...) int32 elements, 8-byte aligned.  No reference counterpart.
+ *
+ * bevf_frustum_pool_f32.  y[b][r][0:C] = sum over e in [row_ptr[b][r], row_ptr[b][r+1]) of pd[b][col2[b][e]] *
+ * x[b][col2[b][e] / D][0:C]: one wave per (cell, frame), fp32 accumulation in table order, several entries in flight.
+ * Frame b reads row_ptr + b * rp_stride and col2 + b * e_stride; BOTH STRIDES MAY BE 0: one table shared by all frames (the
+ * static rig).  pd [b] at pd + b * pd_bs holds [pixel][D] densely.  Same strides, slice output and zero rows as
+ * bevf_csr_gather_f32.  Needs C % 4 == 0, C <= 1024, B <= 65535, 16-byte aligned x / y and 16-byte multiples for their strides,
+ * col2 < pixels * D.  No reference counterpart.
+ *
+ * bevf_frustum_pool_bwd_f32.  Dense, no transposed table: one wave per (pixel, frame) keeps x[b][pix] and walks the pixel's D
+ * bins through cell_of (frame b at cell_of + b * c_stride, c_stride may be 0):
+ *     dpd[b][pix][d]  = <x[b][pix][0:C], dy[b][cell][0:C]> for a valid bin (reduced over the wave by bevf_csr_lift_bwd_f32's
+ *                       fixed butterfly), exactly 0 for an invalid one
+ *     dx[b][pix][0:C] = sum over the valid d, ascending, of pd[b][pix][d] * dy[b][cell][0:C]
+ * Both written once for every pixel.  cell_of < the rows of dy.  No reference counterpart.
+ * ------------------------------------------------------------------------------------------ */
+int bevf_frustum_table_sort_wave_rows(void);
+size_t bevf_frustum_table_work_elems(int B, int ncam, int bev_h, int bev_w, int D, int Hc, int Wc);
+int bevf_frustum_table_build_f64(const double* calib, int B, int ncam, float x0, float y0, float vx, float vy, int bev_h,
+                                 int bev_w, float z0, float z1, int D, double depth_min, double depth_max, int img_h,
+                                 int img_w, int Hc, int Wc, int32_t* cell_of, int32_t* row_ptr, int32_t* col2, void* work,
+                                 void* stream);
+int bevf_frustum_pool_f32(const int32_t* row_ptr, size_t rp_stride, const int32_t* col2, size_t e_stride, int nrows, int D,
+                          const float* x, size_t x_bs, int x_cs, const float* pd, size_t pd_bs, float* y, size_t y_bs,
+                          int y_cs, int B, int C, void* stream);
+int bevf_frustum_pool_bwd_f32(const int32_t* cell_of, size_t c_stride, int npix, int D, const float* x, size_t x_bs, int x_cs,
+                              const float* pd, size_t pd_bs, const float* dy, size_t dy_bs, int dy_cs, float* dx,
+                              size_t dx_bs, int dx_cs, float* dpd, size_t dpd_bs, int B, int C, void* stream);
+
 /* ==========================================================================================
  * bf16 storage, fp32 accumulate (BASELINE configs 3 and 5).  Same layouts and geometry as the fp32 entry
  * points, element type bfloat16 wherever a pointer is typed void*: the convolution runs on

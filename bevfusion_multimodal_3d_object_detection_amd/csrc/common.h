@@ -64,6 +64,22 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
+// ---- division by a launch constant (implicit-GEMM convolutions: pixel -> image, row, column; CSR lift kernels) ----
+// n / d for 0 <= n < 2^31 by multiply-high: q = umulhi(n, mul) >> sh with mul = ceil(2^(31+s)/d), s = ceil(log2 d), sh = s-1 (exact for
+// every such n because the rounding error e < d <= 2^s); mul == 0 means d == 1.  On wave-uniform operands this stays on the scalar unit.
+__device__ __forceinline__ int div_by(int n, unsigned mul, unsigned sh) {
+  return mul ? (int)(__umulhi((unsigned)n, mul) >> sh) : n;
+}
+static inline void div_make(int d, unsigned* mul, unsigned* sh) {
+  *mul = 0;
+  *sh = 0;
+  if (d <= 1) return;
+  int s = 0;
+  while ((1ll << s) < d) ++s;
+  *mul = (unsigned)(((1ull << (31 + s)) + (unsigned long long)d - 1) / (unsigned long long)d);
+  *sh = (unsigned)(s - 1);
+}
+
 // ---- 16-byte channel vectors of either storage type (fp32: 4 channels, bf16: 8 channels) ----------------------
 template <typename T> struct vec16 { static constexpr int N = 16 / (int)sizeof(T); };
 template <typename T>
@@ -96,20 +112,6 @@ __device__ __forceinline__ void store16(T* p, const float (&f)[vec16<T>::N]) {
 }
 
 // ---- helpers of the CSR pool / lift kernels (camera_lift.hip, camera_frustum.hip) ---------------------------------
-// n / d for 0 <= n < 2^31 by multiply-high (mul == 0: d == 1); on wave-uniform operands this stays on the scalar unit
-__device__ __forceinline__ int div_by(int n, unsigned mul, unsigned sh) {
-  return mul ? (int)(__umulhi((unsigned)n, mul) >> sh) : n;
-}
-static inline void div_make(int d, unsigned* mul, unsigned* sh) {
-  *mul = 0;
-  *sh = 0;
-  if (d <= 1) return;
-  int s = 0;
-  while ((1ll << s) < d) ++s;
-  *mul = (unsigned)(((1ull << (31 + s)) + (unsigned long long)d - 1) / (unsigned long long)d);
-  *sh = (unsigned)(s - 1);
-}
-
 // Sum / max over the L lanes (a power of two, aligned) that hold one row: xor butterfly, widest stride first.  IEEE addition is
 // commutative, so both lanes of a pair compute the same bits and every lane of the group ends with the same value.
 template <bool MAX>

@@ -1,5 +1,7 @@
-// Pieces shared by the implicit-GEMM convolution kernels (conv_igemm.hip: exact fp32 / bf16; conv_split.hip: fp32
-// through three bf16 planes): launch arguments, buffer-load helper, multiply-high division, and the epilogue.
+// Pieces shared by the implicit-GEMM convolution kernels: launch arguments, buffer descriptor / load helpers, the A-operand walker
+// (pixel rows under a moving filter tap) and the epilogue.  Users: conv_igemm.hip (exact fp32 / bf16) and conv_split.hip (fp32 through
+// three bf16 planes) take all of it, except that conv_igemm.hip keeps the walker's text in place; conv_wgrad.hip the descriptor / load helpers; conv_wino.hip, conv_wino_wgrad.hip and conv3x3_bf16.hip
+// the vector types, kOob and the 16-byte buffer load.
 #pragma once
 #include "common.h"
 
@@ -34,22 +36,15 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr unsigned kOob = 0x80000000u;   // >= num_records of every descriptor below: the load returns 0
 
+// Raw buffer descriptor over `bytes` bytes at p.  A lane offset >= bytes reads as 0 and drops a store; the default covers every tensor
+// here (all stay below 2 GiB), so kOob as an OFFSET is always out of range.
+template <typename P>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const P* p, unsigned bytes = kOob) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<P*>(p), 0, (int)bytes, 0x00020000);
+}
 __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
   return __builtin_bit_cast(f32x4, v);
-}
-
-// Division of a dividend < 2^31 by a launch constant: q = umulhi(n, mul) >> sh with mul = ceil(2^(31+s)/d),
-// s = ceil(log2 d), sh = s-1 (exact for every n < 2^31 because the rounding error e < d <= 2^s); mul = 0 means d = 1.
-__device__ __forceinline__ int fastdiv(int n, unsigned mul, unsigned sh) {
-  return mul ? (int)(__umulhi((unsigned)n, mul) >> sh) : n;
-}
-static void fastdiv_make(int d, unsigned* mul, unsigned* sh) {
-  if (d <= 1) { *mul = 0; *sh = 0; return; }
-  int s = 0;
-  while ((1ll << s) < d) ++s;
-  *mul = (unsigned)(((1ull << (31 + s)) + (unsigned long long)d - 1) / (unsigned long long)d);
-  *sh = (unsigned)(s - 1);
 }
 
 // bevf_conv_desc -> ConvArgs for the implicit-GEMM entry points: the rules they share, reported as "<who>: ...", then the fill
@@ -78,9 +73,80 @@ static int conv_args_from_desc(const bevf_conv_desc* d, const char* who, int x_e
   a.relu = d->relu; a.rows_per_group = d->rows_per_group;
   a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.tilesM = a.tilesN = 0;
   a.m_split = 0; a.nbig = 0; a.tilesN_big = 0;
-  fastdiv_make(d->Ho * d->Wo, &a.div_hw_mul, &a.div_hw_sh);
-  fastdiv_make(d->Wo, &a.div_w_mul, &a.div_w_sh);
+  div_make(d->Ho * d->Wo, &a.div_hw_mul, &a.div_hw_sh);
+  div_make(d->Wo, &a.div_w_mul, &a.div_w_sh);
   return BEVF_OK;
+}
+
+// A operand of the implicit GEMM: the thread's 16-byte chunk `chunk` of the tile rows row0 + 32*j (j < AP), walked over K = (kh, kw, c0).
+// ES = bytes per activation element; a K step is 8 chunks = 128 / ES channels of ONE filter tap.  Nothing here costs vector-ALU work per
+// K step: voff[j] is the byte offset of the row's pixel under tap (pad, pad), fixed for the tile; the tap moves the descriptor's scalar
+// base, the channel chunk is the scalar offset, and eff[j] = voff[j] or kOob (the hardware's zero = the padding) changes only when the
+// tap does.  Rows past m_hi have voff = kOob and coordinates far outside every image.  (kh, kw, c0) is the state of the NEXT load().
+// conv_igemm.hip's conv_tile holds a copy of this text (why: DESIGN 3.1, "Deviation"): a fix here belongs there too.
+template <int ES, int AP>
+struct ConvAWalker {
+  static constexpr int EPC = 16 / ES, BKE = 8 * EPC;      // elements per chunk / per K step
+  unsigned voff[AP], eff[AP];
+  int ih0[AP], iw0[AP];
+  int kh, kw, c0;
+
+  __device__ __forceinline__ void init(const ConvArgs& p, const int row0, const int m_hi, const int chunk) {
+    const int HoWo = p.Ho * p.Wo;
+#pragma unroll
+    for (int j = 0; j < AP; ++j) {
+      const int m = row0 + 32 * j;
+      if (m < m_hi) {
+        const int n = div_by(m, p.div_hw_mul, p.div_hw_sh), r = m - n * HoWo;
+        const int oh = div_by(r, p.div_w_mul, p.div_w_sh), ow = r - oh * p.Wo;
+        voff[j] = (unsigned)((((n * p.H + oh * p.stride) * p.W + ow * p.stride) * p.x_cs + chunk * EPC) * ES);
+        ih0[j] = oh * p.stride - p.pad;
+        iw0[j] = ow * p.stride - p.pad;
+      } else {
+        voff[j] = kOob;
+        ih0[j] = -(1 << 24);
+        iw0[j] = -(1 << 24);
+      }
+    }
+    kh = kw = c0 = 0;
+    set_tap(p);
+  }
+  __device__ __forceinline__ void set_tap(const ConvArgs& p) {     // VALU work only when the filter tap changes
+#pragma unroll
+    for (int j = 0; j < AP; ++j) {
+      const int ih = ih0[j] + kh, iw = iw0[j] + kw;
+      eff[j] = ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) ? voff[j] : kOob;
+    }
+  }
+  __device__ __forceinline__ void load(const ConvArgs& p, f32x4 (&ra)[AP]) const {
+    const char* base = static_cast<const char*>(p.x) + ((long)(kh - p.pad) * p.W + (kw - p.pad)) * p.x_cs * ES;
+    const __amdgpu_buffer_rsrc_t rsrcA = buf_rsrc(base);
+#pragma unroll
+    for (int j = 0; j < AP; ++j) ra[j] = buf_load16(rsrcA, eff[j], (unsigned)(c0 * ES));
+  }
+  __device__ __forceinline__ void advance(const ConvArgs& p) {     // to the next K step: chunk -> tap walk
+    c0 += BKE;
+    if (c0 == p.Cin) {
+      c0 = 0;
+      if (++kw == p.KW) { kw = 0; ++kh; }
+      set_tap(p);
+    }
+  }
+};
+
+// The two pieces of finishing arithmetic that the three store paths of conv_epilogue share.  scale / shift of output channel n (folded
+// BatchNorm or bias; null pointers = 1 and 0):
+__device__ __forceinline__ void conv_scale_shift(const ConvArgs& p, const int n, float& sc, float& sh) {
+  sc = p.scale ? p.scale[n] : 1.f;
+  sh = p.shift ? p.shift[n] : 0.f;
+}
+// and one accumulator value -> output value: folded BN, then the residual, then ReLU.  The flags are compile-time constants in the
+// full-tile variants and wave-uniform values elsewhere; after inlining both cost what the hand-written forms did.
+__device__ __forceinline__ float conv_finish(const float acc, const float sc, const float sh, const bool has_res, const float rv,
+                                             const bool relu) {
+  float t = fmaf(acc, sc, sh);
+  if (has_res) t += rv;
+  return relu ? fmaxf(t, 0.f) : t;
 }
 
 // Epilogue of one workgroup tile.  acc[mi][ni] is the 32x32 MFMA tile (mi, ni) of this wave: C[i][j] with
@@ -100,20 +166,18 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
   if (!p.colmax && m0 + BM <= m_hi && n0 + BN <= p.Cout) {
     // full tile: buffer stores whose row offset is the instruction's SCALAR offset (SALU arithmetic) and whose
     // lane offset is computed once; residual / ReLU chosen once -- 2-3 VALU instructions per output element
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-        static_cast<T*>(p.y) + (size_t)m_base * p.y_cs + n_base, 0, (int)kOob, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<T*>(static_cast<const T*>(p.res)) + (size_t)m_base * p.res_cs + n_base, 0, (int)kOob, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ry = buf_rsrc(static_cast<const T*>(p.y) + (size_t)m_base * p.y_cs + n_base);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(static_cast<const T*>(p.res) + (size_t)m_base * p.res_cs + n_base);
     const unsigned y_lane = (unsigned)((4 * h * p.y_cs + l31) * ES);
     const unsigned r_lane = (unsigned)((4 * h * p.res_cs + l31) * ES);
     auto run = [&](auto has_res, auto do_relu) {
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) {
-        const float sc = p.scale ? p.scale[n_base + ni * 32 + l31] : 1.f;
-        const float sh = p.shift ? p.shift[n_base + ni * 32 + l31] : 0.f;
+        float sc, sh;
+        conv_scale_shift(p, n_base + ni * 32 + l31, sc, sh);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
-          float rv[16];
+          float rv[16] = {};
           if constexpr (decltype(has_res)::value) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -128,9 +192,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            float t = fmaf(acc[mi][ni][r], sc, sh);
-            if constexpr (decltype(has_res)::value) t += rv[r];
-            if constexpr (decltype(do_relu)::value) t = fmaxf(t, 0.f);
+            const float t = conv_finish(acc[mi][ni][r], sc, sh, decltype(has_res)::value, rv[r], decltype(do_relu)::value);
             const unsigned so = (unsigned)(((mi * 32 + (r & 3) + 8 * (r >> 2)) * p.y_cs + ni * 32) * ES);
             if constexpr (kF32)
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, t), ry, y_lane, so, 0);
@@ -153,10 +215,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
         char* const ws = scratch + (wm * (BN / WN) + wn) * (32 * PITCH);
         float scv[NI], shv[NI];
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-          scv[ni] = p.scale ? p.scale[n_base + ni * 32 + l31] : 1.f;
-          shv[ni] = p.shift ? p.shift[n_base + ni * 32 + l31] : 0.f;
-        }
+        for (int ni = 0; ni < NI; ++ni) conv_scale_shift(p, n_base + ni * 32 + l31, scv[ni], shv[ni]);
         const bool relu = p.relu != 0;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
@@ -164,8 +223,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
           for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              float t = fmaf(acc[mi][ni][r], scv[ni], shv[ni]);
-              t = relu ? fmaxf(t, 0.f) : t;
+              const float t = conv_finish(acc[mi][ni][r], scv[ni], shv[ni], false, 0.f, relu);
               *reinterpret_cast<__bf16*>(ws + ((r & 3) + 8 * (r >> 2) + 4 * h) * PITCH + (ni * 32 + l31) * 2) = (__bf16)t;
             }
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -195,8 +253,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
     const int n = n_base + ni * 32 + l31;
     const bool nok = n < p.Cout;
     const int nc = nok ? n : p.Cout - 1;
-    const float sc = p.scale ? p.scale[nc] : 1.f;
-    const float sh = p.shift ? p.shift[nc] : 0.f;
+    float sc, sh;
+    conv_scale_shift(p, nc, sc, sh);
     float vmax = 0.f;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
@@ -215,10 +273,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x16 (&acc)[W
       }
       float v[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float t = fmaf(acc[mi][ni][r], sc, sh) + rv[r];
-        v[r] = p.relu ? fmaxf(t, 0.f) : t;
-      }
+      for (int r = 0; r < 16; ++r) v[r] = conv_finish(acc[mi][ni][r], sc, sh, true, rv[r], p.relu != 0);   // rv = +0 without a residual
       if (p.y) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

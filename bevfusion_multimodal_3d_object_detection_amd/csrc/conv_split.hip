@@ -1,6 +1,6 @@
 // fp32 implicit-GEMM convolution through three bf16 planes ("f32x3"), gfx950.
 //
-// Same GEMM view, tiling, prologue and epilogue as conv_igemm.hip, but the multiply runs on
+// Same GEMM view, tiling, A-operand addressing (ConvAWalker) and epilogue (conv_common.h) as conv_igemm.hip, but the multiply runs on
 // v_mfma_f32_32x32x16_bf16 (16x the rate of v_mfma_f32_32x32x2_f32): every fp32 operand is split exactly into
 //     x = hi + mid + lo,   hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)      (|residual| <~ 2^-25 |x|)
 // and a product a*b is accumulated in fp32 as the six partial products that matter,
@@ -70,26 +70,10 @@ __global__ __launch_bounds__(256) void conv_split(const ConvArgs p) {
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int m0 = tm * BM, n0 = tn * BN;
 
-  // ---- A staging: thread owns fp32 chunk `chunk` (k = 4*chunk..+3) of rows srow + 32*j ----------------------
+  // ---- A staging: thread owns fp32 chunk `chunk` (k = 4*chunk..+3) of rows srow + 32*j, through the walker of conv_common.h -------
   const int chunk = tid & 7, srow = tid >> 3;
-  unsigned a_voff[AP], a_eff[AP];
-  int a_ih0[AP], a_iw0[AP];
-  const int HoWo = p.Ho * p.Wo;
-#pragma unroll
-  for (int j = 0; j < AP; ++j) {
-    const int m = m0 + srow + 32 * j;
-    if (m < m_hi) {
-      const int n = fastdiv(m, p.div_hw_mul, p.div_hw_sh), r = m - n * HoWo;
-      const int oh = fastdiv(r, p.div_w_mul, p.div_w_sh), ow = r - oh * p.Wo;
-      a_voff[j] = (unsigned)((((n * p.H + oh * p.stride) * p.W + ow * p.stride) * p.x_cs + chunk * 4) * 4);
-      a_ih0[j] = oh * p.stride - p.pad;
-      a_iw0[j] = ow * p.stride - p.pad;
-    } else {
-      a_voff[j] = kOob;
-      a_ih0[j] = -(1 << 24);
-      a_iw0[j] = -(1 << 24);
-    }
-  }
+  ConvAWalker<4, AP> aw;
+  aw.init(p, m0 + srow, m_hi, chunk);
   // ---- B staging: thread owns 16-B chunk q (8 bf16) of rows brow + 64*j of each plane -----------------------
   const int bq = tid & 3, brow = tid >> 2;
   unsigned b_voff[BPJ];
@@ -100,41 +84,17 @@ __global__ __launch_bounds__(256) void conv_split(const ConvArgs p) {
   }
   const size_t plane_elems = (size_t)p.Cout * p.K;
   const __bf16* const wb = static_cast<const __bf16*>(p.w);
-  const __amdgpu_buffer_rsrc_t rsrcB0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(wb), 0, (int)kOob, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcB1 =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(wb + plane_elems), 0, (int)kOob, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrcB2 =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(wb + 2 * plane_elems), 0, (int)kOob, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcB0 = buf_rsrc(wb), rsrcB1 = buf_rsrc(wb + plane_elems), rsrcB2 = buf_rsrc(wb + 2 * plane_elems);
 
-  int kh = 0, kw = 0, c0 = 0;
-  auto set_tap = [&]() {
-#pragma unroll
-    for (int j = 0; j < AP; ++j) {
-      const int ih = a_ih0[j] + kh, iw = a_iw0[j] + kw;
-      a_eff[j] = ((unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) ? a_voff[j] : kOob;
-    }
-  };
   f32x4 ra[AP];
   u32x4 rb[3][BPJ];
-  auto load_tile = [&](int kstep) {
-    const char* base = static_cast<const char*>(p.x) + ((long)(kh - p.pad) * p.W + (kw - p.pad)) * p.x_cs * 4;
-    const __amdgpu_buffer_rsrc_t rsrcA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, (int)kOob, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < AP; ++j) ra[j] = buf_load16(rsrcA, a_eff[j], (unsigned)(c0 * 4));
+  auto load_tile = [&](int kstep) {                 // K step `kstep`, which the walker stands on
+    aw.load(p, ra);
 #pragma unroll
     for (int j = 0; j < BPJ; ++j) {
       rb[0][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrcB0, b_voff[j], (unsigned)kstep * 64u, 0);
       rb[1][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrcB1, b_voff[j], (unsigned)kstep * 64u, 0);
       rb[2][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrcB2, b_voff[j], (unsigned)kstep * 64u, 0);
-    }
-  };
-  auto advance = [&]() {
-    c0 += BK;
-    if (c0 == p.Cin) {
-      c0 = 0;
-      if (++kw == p.KW) { kw = 0; ++kh; }
-      set_tap();
     }
   };
 
@@ -194,12 +154,11 @@ __global__ __launch_bounds__(256) void conv_split(const ConvArgs p) {
 
   // ---- K loop: single LDS buffer, the next step's operands are in flight in registers during the MFMAs ----
   const int KT = p.K / BK;
-  set_tap();
   load_tile(0);
   store_tile();
   __syncthreads();
   if (KT > 1) {
-    advance();
+    aw.advance(p);
     load_tile(1);
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(256) void conv_split(const ConvArgs p) {
     store_tile();
     __syncthreads();
     if (kt + 1 < KT) {
-      advance();
+      aw.advance(p);
       load_tile(kt + 1);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -223,8 +182,7 @@ int launch_split(ConvArgs a, hipStream_t st) {
   a.tilesM = (a.M + BM - 1) / BM;
   a.tilesN = (a.Cout + BN - 1) / BN;
   constexpr size_t lds_bytes = size_t(3) * (BM + BN) * 64;
-  hipLaunchKernelGGL((conv_split<BM, BN, WM, WN>), dim3(a.tilesM * a.tilesN), dim3(256), lds_bytes, st, a);
-  return bevf_check_launch("bevf_conv2d_nhwc_f32x3");
+  return bevf_launch("bevf_conv2d_nhwc_f32x3", conv_split<BM, BN, WM, WN>, dim3(a.tilesM * a.tilesN), dim3(256), lds_bytes, st, a);
 }
 
 }  // namespace

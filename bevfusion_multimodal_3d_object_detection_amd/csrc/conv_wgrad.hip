@@ -11,20 +11,14 @@
 // so the loop has NO per-step address arithmetic on the vector ALU (which v_mfma_f32_32x32x2_f32 shares): the table
 // and the dY rows are read through buffer descriptors whose base the scalar unit advances each step, the per-lane
 // offsets are loop constants, and the only VALU work per staged row is one add (tap offset + channel offset).
-#include "common.h"
+#include "conv_common.h"
 
 #include <type_traits>
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned kOob = 0x80000000u;
 constexpr int PS = 32;   // pixels per step
-
-__device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
-}
 
 // taptab[m][t] = byte offset of x[n][ih][iw][0] for output pixel m under filter tap t, or kOob when the tap falls into
 // the padding (the buffer load then returns zeros); rows m in [M, Mpad) are all kOob (Mpad = M rounded up to PS)
@@ -90,21 +84,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_f32(const WgradArgs p) {
 #pragma unroll
   for (int q = 0; q < BP; ++q) t_voff[q] = b_ok ? (unsigned)(((b_row + q * BROWS) * p.T + tap) * 4) : kOob;
   const unsigned ci_bytes = (unsigned)(ci * 4);
-  const __amdgpu_buffer_rsrc_t rsrcB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)kOob, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrcB = buf_rsrc(p.x);
 
   f32x4 ra[AP], rb[BP];
   unsigned tabv[BP];
   auto load_tab = [&](int step) {
-    const __amdgpu_buffer_rsrc_t rsrcT = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<int*>(p.taptab) + (size_t)(step0 + step) * PS * p.T, 0, (int)kOob, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcT = buf_rsrc(p.taptab + (size_t)(step0 + step) * PS * p.T);
 #pragma unroll
     for (int q = 0; q < BP; ++q) tabv[q] = __builtin_amdgcn_raw_buffer_load_b32(rsrcT, t_voff[q], 0, 0);
   };
   auto load_tiles = [&](int step) {
     const int row0 = (step0 + step) * PS;
-    const __amdgpu_buffer_rsrc_t rsrcA = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.dy) + (size_t)row0 * p.dy_cs, 0, (int)(((size_t)(p.M - row0 - 1) * p.dy_cs + p.Cout) * 4),
-        0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcA =
+        buf_rsrc(p.dy + (size_t)row0 * p.dy_cs, (unsigned)(((size_t)(p.M - row0 - 1) * p.dy_cs + p.Cout) * 4));
 #pragma unroll
     for (int q = 0; q < AP; ++q) ra[q] = buf_load16(rsrcA, a_voff[q], 0);
 #pragma unroll
@@ -214,8 +206,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
   if (splits > steps) splits = steps;
   a.steps_per_split = (steps + splits - 1) / splits;
   splits = (steps + a.steps_per_split - 1) / a.steps_per_split;
-  hipLaunchKernelGGL((conv_wgrad_f32<BI, BJ, WI, WJ>), dim3(a.tilesI * a.tilesJ * splits), dim3(256), lds_bytes, st, a);
-  return bevf_check_launch("bevf_conv2d_wgrad_f32");
+  return bevf_launch("bevf_conv2d_wgrad_f32", conv_wgrad_f32<BI, BJ, WI, WJ>, dim3(a.tilesI * a.tilesJ * splits), dim3(256), lds_bytes, st, a);
 }
 
 }  // namespace

@@ -1,11 +1,13 @@
 // Pieces shared by the implicit-GEMM convolution kernels: launch arguments, buffer descriptor / load helpers, the A-operand walker
 // (pixel rows under a moving filter tap) and the epilogue.  Users: conv_igemm.hip (exact fp32 / bf16) and conv_split.hip (fp32 through
-// three bf16 planes) take all of it, except that conv_igemm.hip keeps the walker's text in place; conv_wgrad.hip the descriptor / load helpers; conv_wino.hip, conv_wino_wgrad.hip and conv3x3_bf16.hip
-// the vector types, kOob and the 16-byte buffer load.
+// three bf16 planes) take all of it, except that conv_igemm.hip keeps the walker's text in place; conv_wgrad.hip the descriptor / load helpers; conv3x3_bf16.hip
+// the vector types, kOob and the 16-byte buffer load; conv_wino.hip and conv_wino_wgrad.hip (through wino_common.h) those, the descriptor
+// helper and static_for.
 #pragma once
 #include "common.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -45,6 +47,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const P* p, unsigned 
 __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
   return __builtin_bit_cast(f32x4, v);
+}
+
+// Compile-time index loop: f(ic<0>{}), ..., f(ic<N - 1>{}) in order -- for bodies whose index has to be a constant expression
+// (which register array element, which MFMA gap), where `#pragma unroll` only makes it a constant after the fact.
+template <int C> using ic = std::integral_constant<int, C>;
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(ic<I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
 }
 
 // bevf_conv_desc -> ConvArgs for the implicit-GEMM entry points: the rules they share, reported as "<who>: ...", then the fill

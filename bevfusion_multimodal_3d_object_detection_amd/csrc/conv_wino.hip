@@ -22,23 +22,9 @@
 // (one small piece per gap, sched_barrier after each) and issues in the shadow of the MFMA executing.  The MFMAs are
 // inline asm with "+a" accumulators: with the builtin, hipcc's allocator moved accumulators between AGPRs and VGPRs
 // inside the loop (44-296 v_accvgpr moves per group); pinned, the loop has none and no spills.
-#include "conv_common.h"
-
-#include <type_traits>
+#include "wino_common.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// a - b on two floats at once (same rounding as two v_sub_f32)
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-  f32x2 d;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-
-#define MFMA(acc_, a_, b_) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc_) : "v"(a_), "v"(b_))
-#define MFMA0(acc_, a_, b_) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=a"(acc_) : "v"(a_), "v"(b_))
 
 struct WinoArgs {
   const float* x;      // NHWC, channel stride x_cs
@@ -103,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   // ---- patch staging by LDS-DMA (buffer_load ... lds: an out-of-range lane writes zeros -- the pad ring, the pad slot of
   //      every pixel, the slots past the patch): instruction (4 j + wave), j < 12, fills 64 consecutive 16-byte slots;
   //      slot s = pixel s / 9, piece s % 9 (8 = pad) --------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (int)kOob, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsx = buf_rsrc(p.x);
   // n / rb: image and in-image row of the block's first pixel row; hw: rows after which a row index wraps into the next image
   // The 12 slot offsets of a wave are what stands between the workgroup's start and its last HBM request (one wave per SIMD: ~5 cycles
   // per dependent instruction, ~2.5 k cycles in all -- as much as the wait that follows, tools/wino_stamps.py): 24-bit multiplies (every
@@ -127,14 +113,20 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
       n = n0;
     }
   };
+  // stacked rows: a row index at or past hw lies in the NEXT image -- made in-image here; -> whether it wrapped.  Whoever wraps then tests
+  // image < N, row < H, column < W in its own terms
+  auto wrap_row = [](int& row, int hw) {
+    const bool wr = row >= hw;
+    row -= wr ? hw : 0;
+    return wr;
+  };
   // byte offset in x of pixel pix (< 1024) of the patch that starts at row r0 of image n0, column ix0; ok: the pixel exists (inside the
   // image, not in a dead row, image < N) -- whoever uses the offset sends every other lane to kOob
   auto pixel_off = [&](unsigned pix, int n0, int r0, int hw, int ix0, bool& ok) {
     const unsigned py = __umul24(pix, GEO ? 6554u : 3641u) >> 16, px = pix - __umul24(py, (unsigned)PWP);   // pix / 10 (or / 18) for pix < 1024
     int iy = r0 + (int)py;
     const int ix = ix0 + (int)px;
-    const bool wr = iy >= hw;
-    iy -= wr ? hw : 0;
+    const bool wr = wrap_row(iy, hw);
     ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && (unsigned)(n0 + (wr ? 1 : 0)) < (unsigned)p.N;
     const unsigned row = (unsigned)(n0 * p.H) + (wr ? (unsigned)p.H : 0u) + (unsigned)iy;       // image row index over the batch
     return __umul24(__umul24(row, (unsigned)p.W) + (unsigned)ix, (unsigned)(p.x_cs * 4));
@@ -167,13 +159,13 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   // RES: in a tile's LAST chunk the "next chunk" slots have nothing to fetch; two of them (group 0's first two) then touch one 16-byte
   // piece of every 128-byte line of this wave's residual pixels -- the data lands in the idle patch buffer and is never read, but the
   // lines are in L2 when the epilogue asks for them ~3 groups later (the epilogue waited 4.7k cycles for HBM here: tools/wino_stamps.py)
-  const __amdgpu_buffer_rsrc_t rsr_pf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : p.x), 0, (int)kOob, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsr_pf = buf_rsrc(RES ? p.res : p.x);
   bool pf_res = false;                                              // group 0's part of the patch comes through rsr_pf
 
   // ---- B staging by LDS-DMA: group image = 32 pieces of 1 KiB; wave w issues pieces 8w .. 8w+7 ----------------------
   // (buffer form: the per-lane part of the address is one constant VGPR, the image / piece offset a scalar -- the global
   //  form cost a 64-bit vector add per piece, and the fp32 MFMA shares the vector ALU)
-  const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, (int)kOob, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsu = buf_rsrc(p.u);
   const unsigned u_lane = (unsigned)((wave * 8 * 256 + lane * 4) * 4);
   auto dma_piece = [&](unsigned img, int buf, int i) {              // img: byte offset of the group image in p.u
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsu, (__attribute__((address_space(3))) void*)(bbuf + buf * BG_FLOATS + wave * 8 * 256 + i * 256),
@@ -187,28 +179,28 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   const int b_lane = kq * 64 + t * 4;                              // floats within a [4 kq][16 n][2 nb][2 cin] block: lane * 16 bytes, linear
 
   f32x4 acc[16][4];
-#ifndef WINO_ONE_CLUSTER
-#define WINO_ONE_CLUSTER 1
-#endif
-  // A fragments: two sets (WINO_ONE_CLUSTER: group g multiplies from set g & 1 while the WHOLE input transform of group g + 1 is written
-  // into the other set in ONE MFMA gap -- a lone VALU instruction between fp32 MFMAs costs ~15 cycles, the ones right behind it ~3
-  // (probe), so 32 packed adds cost ~120 cycles as one cluster and ~250 as the twelve they used to be)
-  f32x2 vv[WINO_ONE_CLUSTER ? 2 : 1][16], dn[16];
-  f32x2 (&v)[16] = vv[0];
-  auto load_patch = [&](int buf, int gl, int q) {                  // row q of the 4x4 patch -> dn[4q..4q+3]
-    const float* pa = patch + buf * PATCH_FLOATS + a_lane + gl * 8;
+  // A fragments: two sets -- group g multiplies from set g & 1 while the WHOLE input transform of group g + 1 is written into the other
+  // set in ONE MFMA gap: a lone VALU instruction between fp32 MFMAs costs ~15 cycles, the ones right behind it ~3 (probe),
+  // so 32 packed adds cost ~120 cycles as one cluster and ~250 as the twelve they used to be
+  f32x2 vv[2][16], dn[16];
+  // columns c, c + 1 of row q of the 4x4 patch at pa -> dn[4q + c], dn[4q + c + 1]: 2 x ds_read_b64
+  auto load_patch = [&](const float* pa, int q, int c) {
+    dn[4 * q + c] = *reinterpret_cast<const f32x2*>(pa + (q * PWP + c) * PITCH);
+    dn[4 * q + c + 1] = *reinterpret_cast<const f32x2*>(pa + (q * PWP + c + 1) * PITCH);
+  };
+  auto transform_into = [&](f32x2 (&v)[16]) {                       // B^T d B: dn (consumed) -> v
 #pragma unroll
-    for (int c = 0; c < 4; ++c) dn[4 * q + c] = *reinterpret_cast<const f32x2*>(pa + (q * PWP + c) * PITCH);
-  };
-  auto rows_col = [&](int c) {                                      // B^T d, column c (in place)
-    const f32x2 t0 = dn[0 + c] - dn[8 + c], t1 = dn[4 + c] + dn[8 + c], t2 = dn[8 + c] - dn[4 + c], t3 = dn[4 + c] - dn[12 + c];
-    dn[0 + c] = t0; dn[4 + c] = t1; dn[8 + c] = t2; dn[12 + c] = t3;
-  };
-  auto cols_row = [&](int r) {                                      // (B^T d) B, row r -> v[4r..4r+3]
-    v[4 * r + 0] = dn[4 * r + 0] - dn[4 * r + 2];
-    v[4 * r + 1] = dn[4 * r + 1] + dn[4 * r + 2];
-    v[4 * r + 2] = dn[4 * r + 2] - dn[4 * r + 1];
-    v[4 * r + 3] = dn[4 * r + 1] - dn[4 * r + 3];
+    for (int c = 0; c < 4; ++c) {                                   // B^T d, column c (in place)
+      const f32x2 t0 = dn[0 + c] - dn[8 + c], t1 = dn[4 + c] + dn[8 + c], t2 = dn[8 + c] - dn[4 + c], t3 = dn[4 + c] - dn[12 + c];
+      dn[0 + c] = t0; dn[4 + c] = t1; dn[8 + c] = t2; dn[12 + c] = t3;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                                   // (B^T d) B, row r -> v[4r..4r+3]
+      v[4 * r + 0] = dn[4 * r + 0] - dn[4 * r + 2];
+      v[4 * r + 1] = dn[4 * r + 1] + dn[4 * r + 2];
+      v[4 * r + 2] = dn[4 * r + 2] - dn[4 * r + 1];
+      v[4 * r + 3] = dn[4 * r + 1] - dn[4 * r + 3];
+    }
   };
 
   // ---- prologue: first tile's patch chunk 0, B group 0, A fragments of group 0 -----------------------------------------
@@ -234,11 +226,11 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   //  which nothing reads before group 3; the first group's end, vmcnt(4) behind twelve younger loads, covers them)
   asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
-  for (int q = 0; q < 4; ++q) load_patch(0, 0, q);
-#pragma unroll
-  for (int c = 0; c < 4; ++c) rows_col(c);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) cols_row(r);
+  for (int q = 0; q < 4; ++q) {
+    load_patch(patch + a_lane, q, 0);
+    load_patch(patch + a_lane, q, 2);
+  }
+  transform_into(vv[0]);
   int pbuf = 0;                                                     // patch buffer holding the current chunk
   stamp_at(1, t_issued);
   stamp(2);
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
     for (int f = 0; f < 16; ++f) {
       f32x4 (&bc)[2] = (f & 1) ? b1 : b0;
       f32x4 (&bn)[2] = (f & 1) ? b0 : b1;
-      const f32x2 a = vv[WINO_ONE_CLUSTER ? (gl & 1) : 0][f];
+      const f32x2 a = vv[gl & 1][f];
       // 8 MFMAs; after each one a small piece of the other work, pinned in place, so that every non-MFMA instruction
       // issues in the shadow of an executing MFMA (one wave per SIMD: nothing else would fill the gap)
 #pragma unroll
@@ -271,36 +263,11 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
         else MFMA(acc[f][nb], a[j], bc[nb >> 1][(nb & 1) * 2 + j]);
         if (k == 0 && f < 15) bn[0] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2) * 256);
         if (k == 1 && f < 15) bn[1] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2 + 1) * 256);
-        if (f < 4) {                                                // patch row f of the next group: 4 x b64
-          if (k == 2) { dn[4 * f + 0] = *reinterpret_cast<const f32x2*>(pa + (f * PWP + 0) * PITCH);
-                        dn[4 * f + 1] = *reinterpret_cast<const f32x2*>(pa + (f * PWP + 1) * PITCH); }
-          if (k == 3) { dn[4 * f + 2] = *reinterpret_cast<const f32x2*>(pa + (f * PWP + 2) * PITCH);
-                        dn[4 * f + 3] = *reinterpret_cast<const f32x2*>(pa + (f * PWP + 3) * PITCH); }
-        } else if (WINO_ONE_CLUSTER) {
-          if (f == 5 && k == 2) {                                   // patch rows landed (read at f < 4): B^T d B, all of it
-            f32x2 (&vn)[16] = vv[WINO_ONE_CLUSTER ? ((gl + 1) & 1) : 0];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const f32x2 t0 = dn[0 + c] - dn[8 + c], t1 = dn[4 + c] + dn[8 + c];
-              const f32x2 t2 = dn[8 + c] - dn[4 + c], t3 = dn[4 + c] - dn[12 + c];
-              dn[0 + c] = t0; dn[4 + c] = t1; dn[8 + c] = t2; dn[12 + c] = t3;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              vn[4 * r + 0] = dn[4 * r + 0] - dn[4 * r + 2]; vn[4 * r + 1] = dn[4 * r + 1] + dn[4 * r + 2];
-              vn[4 * r + 2] = dn[4 * r + 2] - dn[4 * r + 1]; vn[4 * r + 3] = dn[4 * r + 1] - dn[4 * r + 3];
-            }
-          }
-        } else if (f < 8) {                                         // B^T d, column c = f - 4: four f32x2 ops
-          const int c = f - 4;
-          if (k == 2) { const f32x2 t0 = dn[0 + c] - dn[8 + c], t1 = dn[4 + c] + dn[8 + c];
-                        const f32x2 t2 = dn[8 + c] - dn[4 + c], t3 = dn[4 + c] - dn[12 + c];
-                        dn[0 + c] = t0; dn[4 + c] = t1; dn[8 + c] = t2; dn[12 + c] = t3; }
-        } else if (f & 1) {                                         // (B^T d) B, row r: v[4r..4r+3] are dead by now
-          const int r = (f - 9) >> 1;
-          if (k == 2) { v[4 * r + 0] = dn[4 * r + 0] - dn[4 * r + 2]; v[4 * r + 1] = dn[4 * r + 1] + dn[4 * r + 2]; }
-          if (k == 3) { v[4 * r + 2] = dn[4 * r + 2] - dn[4 * r + 1]; v[4 * r + 3] = dn[4 * r + 1] - dn[4 * r + 3]; }
+        if (f < 4) {                                                // patch row f of the next group: 4 x b64 over two gaps
+          if (k == 2) load_patch(pa, f, 0);
+          if (k == 3) load_patch(pa, f, 2);
         }
+        if (f == 5 && k == 2) transform_into(vv[(gl + 1) & 1]);       // patch rows landed (read at f < 4): B^T d B, all of it
         // staging: the next group's filter image first, then this group's part of a later patch chunk (see above)
         if (f == 0 && bnext) dma_piece(bimg, (gl + 1) & 1, k);
         if (f == 1 && k >= 4 && gl != 2) {
@@ -319,10 +286,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
     if constexpr (gl == 3) asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(gl == 2 ? 0 : 4) : "memory");
   };
-  using G0 = std::integral_constant<int, 0>;
-  using G1 = std::integral_constant<int, 1>;
-  using G2 = std::integral_constant<int, 2>;
-  using G3 = std::integral_constant<int, 3>;
 
   {                                                                 // one tile per workgroup
     using T = std::true_type;
@@ -343,8 +306,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
             const int line = s2 * 64 + lane, pw = line >> 1;        // this wave's 64 pixels x two 128-byte halves of their 64 channels
             const int prow = GEO ? (pw >> 3) : (pw >> 4), pcol = GEO ? (pw & 7) : (pw & 15);
             int ry = rb + (GEO ? 8 : 4) * wave + prow;
-            const bool wr = ry >= hw;
-            ry -= wr ? hw : 0;
+            const bool wr = wrap_row(ry, hw);
             const int rn = n + (wr ? 1 : 0), rx = BWP * bx + pcol;
             const bool ok = rn < p.N && ry < p.H && rx < p.W && ct * 64 + (line & 1) * 32 < p.Cout;
             // (the group adds soff to every address of this part: taken off here; an offset below soff wraps out of range and that
@@ -357,10 +319,10 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) pvl[j] = kOob;
       }
-      if (chunk == 0) group(G0{}, T{}, soff, ug + 1 * gb, true); else group(G0{}, F{}, soff, ug + 1 * gb, true);
-      group(G1{}, F{}, soff, ug + 2 * gb, true);
-      group(G2{}, F{}, soff, ug + 3 * gb, true);
-      group(G3{}, F{}, soff + 128, ug + 4 * gb, !lastc);
+      if (chunk == 0) group(ic<0>{}, T{}, soff, ug + 1 * gb, true); else group(ic<0>{}, F{}, soff, ug + 1 * gb, true);
+      group(ic<1>{}, F{}, soff, ug + 2 * gb, true);
+      group(ic<2>{}, F{}, soff, ug + 3 * gb, true);
+      group(ic<3>{}, F{}, soff + 128, ug + 4 * gb, !lastc);
       pbuf ^= 1;
     }
 
@@ -375,13 +337,12 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
       // two stacked images): its base offset is out of range and every access through it is dropped by the buffer hardware
       int oy = rb + (GEO ? 8 * wave + 2 * kq : 4 * wave + 2 * (kq >> 1));
       const int ox = GEO ? 8 * bx : 16 * bx + 8 * (kq & 1);
-      const bool wr = oy >= hw;
-      oy -= wr ? hw : 0;
+      const bool wr = wrap_row(oy, hw);
       const int nl = n + (wr ? 1 : 0);
       const bool rok[2] = {nl < p.N && oy < p.H, nl < p.N && oy + 1 < p.H};
       const bool interior = BWP * bx + BWP <= p.W && ct * 64 + 64 <= p.Cout;
-      const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)kOob, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, (int)kOob, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsy = buf_rsrc(p.y);
+      const __amdgpu_buffer_rsrc_t rsr = buf_rsrc(p.res);
       const unsigned y_lane = (unsigned)((((nl * p.H + oy) * p.W + ox) * p.y_cs + ct * 64 + t) * 4);
       const unsigned r_lane = (unsigned)((((nl * p.H + oy) * p.W + ox) * p.res_cs + ct * 64 + t) * 4);
       const unsigned yb[2] = {rok[0] ? y_lane : kOob, rok[1] ? y_lane + (unsigned)(p.W * p.y_cs * 4) : kOob};
@@ -409,8 +370,8 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
         };
         float rv[2][16];                                             // residual: two channel blocks in flight
         float lx[BNB ? 2 : 1][16], ly[BNB == 2 ? 2 : 1][16];         // BNB: the BatchNorm layer's raw input / its output
-        const __amdgpu_buffer_rsrc_t rbx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bnb_x), 0, (int)kOob, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rby = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bnb_y), 0, (int)kOob, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rbx = buf_rsrc(p.bnb_x);
+        const __amdgpu_buffer_rsrc_t rby = buf_rsrc(p.bnb_y);
         auto fetch = [&](int nb, int set) {                          // BNB: one channel block's operands, a block ahead of their use
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
@@ -423,6 +384,8 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
                                rsr, vo(nb, q, rbs), soff_of(nb, q, p.res_cs), 0));
           }
         };
+        // (the same residual load as in fetch, which interleaves it with its own loads: sharing the text, as a call behind fetch's loop or
+        //  as a one-element helper, re-allocated the BNB + RES instantiations from their first instruction -- DESIGN 3.1b, "Deviations")
         auto res_fetch = [&](int nb, int set) {
 #pragma unroll
           for (int q = 0; q < 16; ++q)
@@ -463,7 +426,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
               const f32x2 m0 = {acc[0 + nu][nb][2 * hh], acc[0 + nu][nb][2 * hh + 1]}, m1 = {acc[4 + nu][nb][2 * hh], acc[4 + nu][nb][2 * hh + 1]};
               const f32x2 m2 = {acc[8 + nu][nb][2 * hh], acc[8 + nu][nb][2 * hh + 1]}, m3 = {acc[12 + nu][nb][2 * hh], acc[12 + nu][nb][2 * hh + 1]};
               sr[0][nu][hh] = m0 + m1 + m2;
-              sr[1][nu][hh] = pk_sub(pk_sub(m1, m2), m3);
+              sr[1][nu][hh] = pk_sub<false>(pk_sub<false>(m1, m2), m3);
             }
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
@@ -471,7 +434,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
               yh[0][hh] = sr[i][0][hh] + sr[i][1][hh] + sr[i][2][hh];
-              yh[1][hh] = pk_sub(pk_sub(sr[i][1][hh], sr[i][2][hh]), sr[i][3][hh]);
+              yh[1][hh] = pk_sub<false>(pk_sub<false>(sr[i][1][hh], sr[i][2][hh]), sr[i][3][hh]);
             }
             const f32x2 sc2 = {sc[nb], sc[nb]}, sh2 = {sh[nb], sh[nb]};
             f32x2 of[2][2];                                          // folded BatchNorm on pairs (v_pk_fma_f32)
@@ -588,9 +551,8 @@ extern "C" int bevf_wino_filter_transform_f32(const float* w_ohwi, float* u, int
   BEVF_REQUIRE(Cout > 0 && Cin > 0 && Cin % 32 == 0, "wino_filter_transform: Cin=%d must be a positive multiple of 32", Cin);
   const int nct = (Cout + 63) / 64;
   const long long total = (long long)nct * 64 * Cin;
-  hipLaunchKernelGGL(wino_filter_transform, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     w_ohwi, u, Cout, Cin, nct);
-  return bevf_check_launch("bevf_wino_filter_transform_f32");
+  return bevf_launch("bevf_wino_filter_transform_f32", wino_filter_transform, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), w_ohwi, u, Cout, Cin, nct);
 }
 
 extern "C" int bevf_conv3x3_wino_f32(const bevf_conv_desc* d, void* stream) {

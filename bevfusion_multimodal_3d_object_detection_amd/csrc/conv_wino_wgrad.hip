@@ -26,21 +26,16 @@
 //     v_add per step, no division, no compare, no select;
 //   * the transforms are packed-fp32 inline asm (v_pk_fma_f32 / v_pk_add_f32 with neg modifiers): 24 per step;
 //   * everything else (table / data loads, loop control) is VMEM / SALU.
-// Per k-step a wave issues 64 MFMAs (2048 cycles of the matrix pipe) against 36 VALU instructions, each pinned in its
-// own MFMA gap (asm volatile keeps program order; sched_barrier binds the loads).  Operands are computed one step
-// ahead, pixels are loaded two steps ahead, table entries three.
+// Per k-step a wave issues 64 MFMAs (2048 cycles of the matrix pipe) against 36 VALU instructions, pinned as two
+// clusters in two MFMA gaps (asm volatile keeps program order; sched_barrier binds the loads, one per gap).  Operands
+// are computed one step ahead, pixels are loaded two steps ahead, table entries three.
 // The tile range is split over 256 / (block pairs) workgroups; each writes its partial [16 f][64][64] block to a
 // workspace, summed in a fixed order (deterministic, unlike the atomics of conv_wgrad.hip) by the two kernels below,
 // which also apply G^T . G and write (or accumulate into) dW [Cout][3][3][Cin].
-#include "conv_common.h"
-
-#include <type_traits>
+#include "wino_common.h"
 
 namespace {
 
-#define MFMA(acc_, a_, b_) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc_) : "v"(a_), "v"(b_))
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // packed fp32 VALU as volatile asm: stays where it is written between the (volatile asm) MFMAs
@@ -52,11 +47,6 @@ __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
 __device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) {
   f32x2 d;
   asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-  return d;
-}
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
-  f32x2 d;
-  asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
 __device__ __forceinline__ unsigned v_add(int a, int b) {
@@ -118,8 +108,6 @@ __global__ __launch_bounds__(256) void wino_wgrad_table(int* __restrict__ tab, i
   for (int i = 0; i < TE / 4; ++i) dst[i] = i32x4{e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]};
 }
 
-template <int C> using ic = std::integral_constant<int, C>;
-
 __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
   const int lane = threadIdx.x & 63, k = lane >> 4, q = lane & 15;
   const int fr = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -135,10 +123,9 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
   const float sBs = fr == 1 ? 1.f : -1.f, cBs = fr == 1 ? 1.f : -1.f;
   const f32x2 sB = {sBs, sBs}, cB = {cBs, cBs};
   const int selA = rA * 16, selB = rB * 16, selY = fr == 0 ? 80 : (fr == 3 ? 96 : 64);      // byte offsets inside a table entry
-  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + ci0), 0, (int)kOob, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dy + co0), 0, (int)kOob, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rst =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(p.tab), 0, 4 * (p.steps + 4) * TE_BYTES, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsx = buf_rsrc(p.x + ci0);
+  const __amdgpu_buffer_rsrc_t rsy = buf_rsrc(p.dy + co0);
+  const __amdgpu_buffer_rsrc_t rst = buf_rsrc(p.tab, (unsigned)(4 * (p.steps + 4) * TE_BYTES));
   const int q16 = q * 16, ktab = k * TE_BYTES;
 
   f32x4 acc[4][4][4];                                 // [fc][co block][ci block]
@@ -158,29 +145,20 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
     const int so = s * 4 * TE_BYTES + (which == 0 ? selA : which == 1 ? selB : selY);
     tab[set][which] = __builtin_bit_cast(i32x4, buf_load16(rst, ktab, so));
   };
-#ifndef WGRAD_CLUSTER
-#define WGRAD_CLUSTER 1
-#endif
   // A lone VALU instruction between two fp32 MFMAs costs ~15 cycles, the ones right behind it ~3 (probe in conv_wino.hip / DESIGN 3.1b):
   // the twelve address adds of a step are ONE cluster (px_addr, then twelve plain loads in the following gaps), the 24 transform
   // instructions another -- 2 interruptions per 64 MFMAs instead of 36.
   int pxa[12];
-  auto px_addr = [&](auto tsetc) {
+  auto px_addr = [&](auto tsetc) {                    // addresses of the pixels of table set tset: 0..3 row A, 4..7 row B, 8..11 dY
     constexpr int ts = decltype(tsetc)::value;
 #pragma unroll
     for (int i = 0; i < 12; ++i) pxa[i] = v_add(tab[ts][i >> 2][i & 3], q16);
   };
-  auto load_px = [&](auto setc, auto tsetc, auto ic_) {   // pixel i of table set tset: 0..3 row A, 4..7 row B, 8..11 dY
-    constexpr int set = decltype(setc)::value, ts = decltype(tsetc)::value, i = decltype(ic_)::value;
-    if constexpr (WGRAD_CLUSTER) {
-      if constexpr (i < 4) rx[set][0][i] = buf_load16(rsx, pxa[i], 0);
-      else if constexpr (i < 8) rx[set][1][i - 4] = buf_load16(rsx, pxa[i], 0);
-      else ry[set][(i - 8) >> 1][(i - 8) & 1] = buf_load16(rsy, pxa[i], 0);
-    } else {
-      if constexpr (i < 4) rx[set][0][i] = buf_load16(rsx, v_add(tab[ts][0][i], q16), 0);
-      else if constexpr (i < 8) rx[set][1][i - 4] = buf_load16(rsx, v_add(tab[ts][1][i - 4], q16), 0);
-      else ry[set][(i - 8) >> 1][(i - 8) & 1] = buf_load16(rsy, v_add(tab[ts][2][i - 8], q16), 0);
-    }
+  auto load_px = [&](auto setc, auto ic_) {           // pixel i of px_addr's twelve
+    constexpr int set = decltype(setc)::value, i = decltype(ic_)::value;
+    if constexpr (i < 4) rx[set][0][i] = buf_load16(rsx, pxa[i], 0);
+    else if constexpr (i < 8) rx[set][1][i - 4] = buf_load16(rsx, pxa[i], 0);
+    else ry[set][(i - 8) >> 1][(i - 8) & 1] = buf_load16(rsy, pxa[i], 0);
   };
   auto xform = [&](auto setc, auto jc) {              // transform step j of raw set -> operand set, one packed instruction each
     constexpr int set = decltype(setc)::value, j = decltype(jc)::value;
@@ -189,32 +167,25 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
       v_[c][h] = pk_fma(sB, h ? hi2(rx[set][1][c]) : lo2(rx[set][1][c]), h ? hi2(rx[set][0][c]) : lo2(rx[set][0][c]));
     } else if constexpr (j < 16) {                    // columns: v0 - v2, v1 + v2, v2 - v1, v1 - v3
       constexpr int fc = (j - 8) >> 1, h = j & 1;
-      if constexpr (fc == 0) bo[set][0][h] = pk_sub(v_[0][h], v_[2][h]);
+      if constexpr (fc == 0) bo[set][0][h] = pk_sub<true>(v_[0][h], v_[2][h]);
       if constexpr (fc == 1) bo[set][1][h] = pk_add(v_[1][h], v_[2][h]);
-      if constexpr (fc == 2) bo[set][2][h] = pk_sub(v_[2][h], v_[1][h]);
-      if constexpr (fc == 3) bo[set][3][h] = pk_sub(v_[1][h], v_[3][h]);
+      if constexpr (fc == 2) bo[set][2][h] = pk_sub<true>(v_[2][h], v_[1][h]);
+      if constexpr (fc == 3) bo[set][3][h] = pk_sub<true>(v_[1][h], v_[3][h]);
     } else if constexpr (j < 20) {                    // rows of A dY: r[c] = dy[0][c] + cB dy[1][c]
       constexpr int c = (j - 16) >> 1, h = j & 1;
       rr[set][c][h] = pk_fma(cB, h ? hi2(ry[set][1][c]) : lo2(ry[set][1][c]), h ? hi2(ry[set][0][c]) : lo2(ry[set][0][c]));
     } else {                                          // columns: r0, r0 + r1, r0 - r1, (-) r1
       constexpr int h = j & 1;
       if constexpr (j < 22) a1[set][h] = pk_add(rr[set][0][h], rr[set][1][h]);
-      else a2[set][h] = pk_sub(rr[set][0][h], rr[set][1][h]);
+      else a2[set][h] = pk_sub<true>(rr[set][0][h], rr[set][1][h]);
     }
   };
-  auto xform_all = [&](auto setc) {
-    xform(setc, ic<0>{}); xform(setc, ic<1>{}); xform(setc, ic<2>{}); xform(setc, ic<3>{}); xform(setc, ic<4>{}); xform(setc, ic<5>{});
-    xform(setc, ic<6>{}); xform(setc, ic<7>{}); xform(setc, ic<8>{}); xform(setc, ic<9>{}); xform(setc, ic<10>{}); xform(setc, ic<11>{});
-    xform(setc, ic<12>{}); xform(setc, ic<13>{}); xform(setc, ic<14>{}); xform(setc, ic<15>{}); xform(setc, ic<16>{}); xform(setc, ic<17>{});
-    xform(setc, ic<18>{}); xform(setc, ic<19>{}); xform(setc, ic<20>{}); xform(setc, ic<21>{}); xform(setc, ic<22>{}); xform(setc, ic<23>{});
-  };
+  auto xform_all = [&](auto setc) { static_for<24>([&](auto j) { xform(setc, j); }); };
   auto load_px_all = [&](auto setc, auto ts) {
-    if constexpr (WGRAD_CLUSTER) px_addr(ts);
-    load_px(setc, ts, ic<0>{}); load_px(setc, ts, ic<1>{}); load_px(setc, ts, ic<2>{}); load_px(setc, ts, ic<3>{});
-    load_px(setc, ts, ic<4>{}); load_px(setc, ts, ic<5>{}); load_px(setc, ts, ic<6>{}); load_px(setc, ts, ic<7>{});
-    load_px(setc, ts, ic<8>{}); load_px(setc, ts, ic<9>{}); load_px(setc, ts, ic<10>{}); load_px(setc, ts, ic<11>{});
+    px_addr(ts);
+    static_for<12>([&](auto i) { load_px(setc, i); });
   };
-  auto load_tab_all = [&](auto setc, int s) { load_tab(setc, s, ic<0>{}); load_tab(setc, s, ic<1>{}); load_tab(setc, s, ic<2>{}); };
+  auto load_tab_all = [&](auto setc, int s) { static_for<3>([&](auto w) { load_tab(setc, s, w); }); };
 
   // ---- one k-step: 64 MFMAs on operand set CUR; in their gaps the table entries of step s+3 (into table set CUR), the
   //      pixels of step s+2 (entries in table set CUR^1, fetched during step s-1) into raw set CUR, and the transform of
@@ -234,50 +205,10 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
           const float a = fc == 0 ? rr[cur][0][cb >> 1][cb & 1] : fc == 1 ? a1[cur][cb >> 1][cb & 1]
                         : fc == 2 ? a2[cur][cb >> 1][cb & 1] : rr[cur][1][cb >> 1][cb & 1];
           MFMA(acc[fc][cb][ib], a, bo[cur][fc][ib >> 1][ib & 1]);
-          if (m == 0) load_tab(CS, s + 3, ic<0>{});
-          if (m == 1) load_tab(CS, s + 3, ic<1>{});
-          if (m == 2) load_tab(CS, s + 3, ic<2>{});
-          if (m == 3 && WGRAD_CLUSTER) px_addr(NS);
-          if (m == 3) load_px(CS, NS, ic<0>{});
-          if (m == 4) load_px(CS, NS, ic<1>{});
-          if (m == 5) load_px(CS, NS, ic<2>{});
-          if (m == 6) load_px(CS, NS, ic<3>{});
-          if (m == 7) load_px(CS, NS, ic<4>{});
-          if (m == 8) load_px(CS, NS, ic<5>{});
-          if (m == 9) load_px(CS, NS, ic<6>{});
-          if (m == 10) load_px(CS, NS, ic<7>{});
-          if (m == 11) load_px(CS, NS, ic<8>{});
-          if (m == 12) load_px(CS, NS, ic<9>{});
-          if (m == 13) load_px(CS, NS, ic<10>{});
-          if (m == 14) load_px(CS, NS, ic<11>{});
-          if (WGRAD_CLUSTER) {
-            if (m == 38) xform_all(NS);
-          } else {
-            if (m == 38) xform(NS, ic<0>{});
-            if (m == 39) xform(NS, ic<1>{});
-            if (m == 40) xform(NS, ic<2>{});
-            if (m == 41) xform(NS, ic<3>{});
-            if (m == 42) xform(NS, ic<4>{});
-            if (m == 43) xform(NS, ic<5>{});
-            if (m == 44) xform(NS, ic<6>{});
-            if (m == 45) xform(NS, ic<7>{});
-            if (m == 46) xform(NS, ic<8>{});
-            if (m == 47) xform(NS, ic<9>{});
-            if (m == 48) xform(NS, ic<10>{});
-            if (m == 49) xform(NS, ic<11>{});
-            if (m == 50) xform(NS, ic<12>{});
-            if (m == 51) xform(NS, ic<13>{});
-            if (m == 52) xform(NS, ic<14>{});
-            if (m == 53) xform(NS, ic<15>{});
-            if (m == 54) xform(NS, ic<16>{});
-            if (m == 55) xform(NS, ic<17>{});
-            if (m == 56) xform(NS, ic<18>{});
-            if (m == 57) xform(NS, ic<19>{});
-            if (m == 58) xform(NS, ic<20>{});
-            if (m == 59) xform(NS, ic<21>{});
-            if (m == 60) xform(NS, ic<22>{});
-            if (m == 61) xform(NS, ic<23>{});
-          }
+          static_for<3>([&](auto w) { if (m == w) load_tab(CS, s + 3, w); });
+          if (m == 3) px_addr(NS);
+          static_for<12>([&](auto i) { if (m == 3 + i) load_px(CS, i); });
+          if (m == 38) xform_all(NS);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -320,19 +251,23 @@ __global__ __launch_bounds__(256, 1) void wino_wgrad_f32(const WwArgs p) {
 //   dW[co][a][b][ci] (+)= sum_{f,g} G[f][a] G[g][b] U[4f+g][co][ci],   G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 constexpr int FOLD = 16;
 
+// src[0], src[stride], ... : n <= FOLD partials, all loads in flight together, added in index order
+__device__ __forceinline__ f32x4 sum_partials(const f32x4* __restrict__ src, size_t stride, int n) {
+  f32x4 v[FOLD];
+#pragma unroll
+  for (int i = 0; i < FOLD; ++i) v[i] = i < n ? src[i * stride] : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 s = v[0];
+#pragma unroll
+  for (int i = 1; i < FOLD; ++i) s += v[i];
+  return s;
+}
+
 __global__ __launch_bounds__(256) void wino_wgrad_fold(const f32x4* __restrict__ part, f32x4* __restrict__ out, int splits,
                                                         int elems4) {
   const int e = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
   if (e >= elems4) return;
   const int s0 = g * FOLD, n = splits - s0 < FOLD ? splits - s0 : FOLD;
-  const f32x4* src = part + (size_t)s0 * elems4 + e;
-  f32x4 v[FOLD];
-#pragma unroll
-  for (int i = 0; i < FOLD; ++i) v[i] = i < n ? src[(size_t)i * elems4] : f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 s = v[0];
-#pragma unroll
-  for (int i = 1; i < FOLD; ++i) s += v[i];
-  out[(size_t)g * elems4 + e] = s;
+  out[(size_t)g * elems4 + e] = sum_partials(part + (size_t)s0 * elems4 + e, (size_t)elems4, n);
 }
 
 // block = one co x 64 ci; thread (f = tid>>4, c4 = tid&15) sums frequency f of 4 channels over the partials, then 144
@@ -345,13 +280,7 @@ __global__ __launch_bounds__(256) void wino_wgrad_final(const float* __restrict_
   const int co = blockIdx.x / nci, ci0 = (blockIdx.x - co * nci) * 64;
   const size_t fstride = (size_t)Cout * Cin;
   const float* src = part + (size_t)f * fstride + (size_t)co * Cin + ci0 + 4 * c4;
-  f32x4 v[FOLD];
-#pragma unroll
-  for (int i = 0; i < FOLD; ++i) v[i] = i < splits ? *reinterpret_cast<const f32x4*>(src + (size_t)i * 16 * fstride) : f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 s = v[0];
-#pragma unroll
-  for (int i = 1; i < FOLD; ++i) s += v[i];
-  us[f][c4] = s;
+  us[f][c4] = sum_partials(reinterpret_cast<const f32x4*>(src), 4 * fstride, splits);   // split i: 16 frequencies further
   __syncthreads();
   if (tid < 144) {
     const int tap = tid >> 4, a = tap / 3, b = tap - 3 * a;        // c4 = tid & 15 as above
@@ -421,9 +350,8 @@ extern "C" int bevf_wino_wgrad_table(int32_t* tab, int N, int H, int W, int x_cs
                "wino wgrad table: x / dy buffers must stay below 2 GiB (32-bit buffer offsets)");
   BEVF_REQUIRE(bevf_aligned16(tab), "wino wgrad table: unaligned");
   const int Tpad = 4 * (pl.steps + 4);
-  hipLaunchKernelGGL(wino_wgrad_table, dim3((Tpad + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), tab, H, W,
-                     pl.tilesX, pl.tilesY, pl.T, Tpad, x_cs * 4, dy_cs * 4);
-  return bevf_check_launch("bevf_wino_wgrad_table");
+  return bevf_launch("bevf_wino_wgrad_table", wino_wgrad_table, dim3((Tpad + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     tab, H, W, pl.tilesX, pl.tilesY, pl.T, Tpad, x_cs * 4, dy_cs * 4);
 }
 
 extern "C" int bevf_conv3x3_wgrad_wino_f32(const bevf_wgrad_desc* d, float* workspace, int accumulate, void* stream) {
@@ -444,19 +372,19 @@ extern "C" int bevf_conv3x3_wgrad_wino_f32(const bevf_wgrad_desc* d, float* work
   a.Cin = d->Cin; a.Cout = d->Cout;
   a.steps = pl.steps; a.steps_per_split = pl.steps_per_split; a.nci = pl.nci; a.nco = pl.nco;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(wino_wgrad_f32, dim3(pl.splits * pl.nci * pl.nco), dim3(256), 0, st, a);
-  int rc = bevf_check_launch("bevf_conv3x3_wgrad_wino_f32");
+  int rc = bevf_launch("bevf_conv3x3_wgrad_wino_f32", wino_wgrad_f32, dim3(pl.splits * pl.nci * pl.nco), dim3(256), 0, st, a);
   if (rc != BEVF_OK) return rc;
   const float* sums = workspace;
   int nsum = pl.splits;
   if (pl.splits > FOLD) {                              // partials [splits] -> group sums [groups] behind them in the workspace
     const int groups = (pl.splits + FOLD - 1) / FOLD, elems4 = 4 * d->Cout * d->Cin;
     float* folded = workspace + (size_t)pl.splits * 16 * d->Cout * d->Cin;
-    hipLaunchKernelGGL(wino_wgrad_fold, dim3((elems4 + 255) / 256, groups), dim3(256), 0, st,
-                       reinterpret_cast<const f32x4*>(workspace), reinterpret_cast<f32x4*>(folded), pl.splits, elems4);
+    rc = bevf_launch("bevf_conv3x3_wgrad_wino_f32 (fold)", wino_wgrad_fold, dim3((elems4 + 255) / 256, groups), dim3(256), 0, st,
+                     reinterpret_cast<const f32x4*>(workspace), reinterpret_cast<f32x4*>(folded), pl.splits, elems4);
+    if (rc != BEVF_OK) return rc;
     sums = folded;
     nsum = groups;
   }
-  hipLaunchKernelGGL(wino_wgrad_final, dim3(d->Cout * pl.nci), dim3(256), 0, st, sums, d->dw, nsum, d->Cout, d->Cin, accumulate);
-  return bevf_check_launch("bevf_conv3x3_wgrad_wino_f32 (reduce)");
+  return bevf_launch("bevf_conv3x3_wgrad_wino_f32 (reduce)", wino_wgrad_final, dim3(d->Cout * pl.nci), dim3(256), 0, st, sums, d->dw, nsum,
+                     d->Cout, d->Cin, accumulate);
 }

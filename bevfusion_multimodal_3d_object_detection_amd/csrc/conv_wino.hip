@@ -20,9 +20,18 @@
 //     bank-conflict-free.
 // With one wave per SIMD nothing else fills an issue gap, so every non-MFMA instruction is pinned BETWEEN two MFMAs
 // (one small piece per gap, sched_barrier after each) and issues in the shadow of the MFMA executing.  The MFMAs are
-// inline asm with "+a" accumulators: with the builtin, hipcc's allocator moved accumulators between AGPRs and VGPRs
-// inside the loop (44-296 v_accvgpr moves per group); pinned, the loop has none and no spills.
+// inline asm that names its accumulator registers literally (wino_common.h: mfma_named; accumulator (f, nb) = a[16 f + 4 nb ..
+// + 3]) and the epilogue fetches each value with an asm v_accvgpr_read: hipcc is given no accumulator variable.  With the
+// builtin its allocator moved accumulators between AGPRs and VGPRs inside the loop (44-296 v_accvgpr moves per group); as "+a"
+// asm operands the loop was clean, but a tile loop around it spilled and shuffled them.
+//
+// RUNON (plain inference launches, Cin >= 64): one workgroup per CU walks the linear tiles b, b + G, b + 2G, ... and its K loop
+// runs on into the next tile -- the staging slots that are idle in a tile's last groups fetch the next tile's first patch chunk
+// and filter image, so only the epilogue and the slot offsets of the tile after next stand between two tiles' MFMAs.
 #include "wino_common.h"
+
+#include <map>
+#include <mutex>
 
 namespace {
 
@@ -49,6 +58,10 @@ struct WinoArgs {
   // (a patch spans at most two images).  HS = 0: block rows per image, SB = N * TBY.
   int HS, SB;
   unsigned div_mul;    // ceil(2^32 / HS) (stacked) or ceil(2^32 / TBY) (0 for TBY = 1): row -> image by one s_mul_hi (the host checks the range)
+  // RUNON: linear tile L = (ct * nsp + sp) * ... -> ct = L / nsp, sp = rem / TBX, bx = rem % TBX, by multiply-high (ceil(2^32 / d), 0 for
+  // d = 1; the host checks the range); the grid is (workgroups, 1, 1)
+  int ntiles, nsp;
+  unsigned nsp_mul, tbx_mul;
   unsigned long long* stamps;   // DIAG instantiations only (bevf_debug_wino_stamps): kWinoStamps x s_memtime per workgroup
 };
 
@@ -62,8 +75,9 @@ constexpr int LDS_BYTES = (2 * PATCH_FLOATS + 2 * BG_FLOATS) * 4;
 
 // GEO = block geometry: 0 = 8x8 tiles (16x16 pixels; wave w: tile rows 2w, 2w+1), 1 = 16x4 tiles (32 rows x 8 columns; wave w:
 // tile rows 4w .. 4w+3) -- the host takes whichever covers the map with fewer blocks (57x100: 28 -> 26, 113x200: 104 -> 100).
-template <bool RES, bool RELU, bool STATS = false, int BNB = 0, int GEO = 0, bool DIAG = false>
+template <bool RES, bool RELU, bool STATS = false, int BNB = 0, int GEO = 0, bool DIAG = false, bool RUNON = false>
 __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
+  static_assert(!RUNON || (!STATS && BNB == 0 && !DIAG), "the run-on tile loop has no barrier after a tile: plain epilogues only");
   auto stamp_at = [&](int i, unsigned long long tm) {                // diagnostic launches only; the buffer is read by nothing else
     if constexpr (DIAG) {
       if (threadIdx.x == 0) p.stamps[(size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kWinoStamps + i] = tm;
@@ -72,7 +86,10 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   auto stamp = [&](int i) {
     if constexpr (DIAG) stamp_at(i, __builtin_amdgcn_s_memtime());
   };
-  stamp(0);
+  // (stamp 0 is taken here and stored with stamp 1: a store up here is a divergent branch that uses the workgroup ids, across which
+  //  hipcc carried them in VGPRs -- every filter DMA of the K loop, whose scalar offset comes from ct, then ran in a v_readfirstlane loop)
+  unsigned long long t_start = 0;
+  if constexpr (DIAG) t_start = __builtin_amdgcn_s_memtime();
   constexpr int BHP = GEO ? 32 : 16, BWP = GEO ? 8 : 16;          // block height / width in pixels
   constexpr int PWP = BWP + 2, PIXG = (BHP + 2) * PWP;            // patch width, patch pixels (324 or 340)
   constexpr int PSLOTSG = PIXG * 9;
@@ -85,7 +102,13 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   const int G = p.Cin >> 3;                                     // channel groups of 8
   const int NCH = p.Cin >> 5;                                   // patch chunks of 32 channels
   // grid = (TBX, SB, nct): dispatch order x, y, z = spatial blocks of one 64-channel slab first, so concurrent workgroups share one slab
-  // of transformed filters (L2-resident); no index arithmetic to decode a tile
+  // of transformed filters (L2-resident); no index arithmetic to decode a tile.  RUNON: the same order as a linear tile index
+  auto tile_of = [&](int lt, int& bx, int& sp, int& ct) {           // wave-uniform: scalar multiplies
+    ct = p.nsp_mul ? (int)__umulhi((unsigned)lt, p.nsp_mul) : lt;
+    const int rem = lt - ct * p.nsp;
+    sp = p.tbx_mul ? (int)__umulhi((unsigned)rem, p.tbx_mul) : rem;
+    bx = rem - sp * p.TBX;
+  };
   // ---- patch staging by LDS-DMA (buffer_load ... lds: an out-of-range lane writes zeros -- the pad ring, the pad slot of
   //      every pixel, the slots past the patch): instruction (4 j + wave), j < 12, fills 64 consecutive 16-byte slots;
   //      slot s = pixel s / 9, piece s % 9 (8 = pad) --------------------------------------------------------------------
@@ -138,11 +161,10 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   auto patch_dma = [&](unsigned voff, unsigned soff, int buf, int j) { patch_dma_from(rsx, voff, soff, buf, j); };
   // the twelve slot offsets of this block's patch; each slot's chunk-0 DMA is issued as soon as its offset exists, so that its latency
   // and its transfer into LDS (48 KB at 64 bytes per clock: ~770 cycles for the patch) run under the arithmetic of the slots behind it
-  auto make_pv = [&](unsigned (&pv)[PDMA], int& n, int& rb, int& hw, int& bx, int& ct) {
-    bx = blockIdx.x;
-    ct = blockIdx.z;
+  // (issuec false: the offsets only -- a later tile's, whose DMAs the K loop issues)
+  auto make_pv = [&](unsigned (&pv)[PDMA], auto issuec, int bx, int sp, int& n, int& rb, int& hw) {
     int n0, r0;
-    block_rows(blockIdx.y, n0, r0, n, rb, hw);
+    block_rows(sp, n0, r0, n, rb, hw);
     const int ix0 = BWP * bx - 1;
 #pragma unroll
     for (int j = 0; j < PDMA; ++j) {
@@ -152,15 +174,31 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
       const unsigned off = pixel_off(pix, n0, r0, hw, ix0, pok);
       const bool in_patch = (4 * j + 3) * 64 + 63 < PSLOTSG || sl < (unsigned)PSLOTSG;          // (wave < 4: only the last instruction's slots can lie past the patch)
       pv[j] = (in_patch && piece < 8u && pok) ? off + 16u * piece : kOob;
-      patch_dma(pv[j], 0, 0, j);
-      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (decltype(issuec)::value) {
+        patch_dma(pv[j], 0, 0, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
   };
   // RES: in a tile's LAST chunk the "next chunk" slots have nothing to fetch; two of them (group 0's first two) then touch one 16-byte
   // piece of every 128-byte line of this wave's residual pixels -- the data lands in the idle patch buffer and is never read, but the
   // lines are in L2 when the epilogue asks for them ~3 groups later (the epilogue waited 4.7k cycles for HBM here: tools/wino_stamps.py)
+  // RUNON: those slots fetch the next tile's patch; the lines are touched by two ordinary one-dword loads per lane (pfv: their offsets,
+  // kOob outside a tile's last chunk) into registers nobody reads
   const __amdgpu_buffer_rsrc_t rsr_pf = buf_rsrc(RES ? p.res : p.x);
   bool pf_res = false;                                              // group 0's part of the patch comes through rsr_pf
+  unsigned pfv[2] = {kOob, kOob};
+  unsigned junk[2] = {0u, 0u};
+  // byte offset in res of residual line s2 * 64 + lane of this wave (its 64 pixels x two 128-byte halves of their 64 channels), or kOob
+  auto res_line = [&](int s2, int n, int rb, int hw, int bx, int ct) {
+    const int line = s2 * 64 + lane, pw = line >> 1;
+    const int prow = GEO ? (pw >> 3) : (pw >> 4), pcol = GEO ? (pw & 7) : (pw & 15);
+    int ry = rb + (GEO ? 8 : 4) * wave + prow;
+    const bool wr = wrap_row(ry, hw);
+    const int rn = n + (wr ? 1 : 0), rx = BWP * bx + pcol;
+    const bool ok = rn < p.N && ry < p.H && rx < p.W && ct * 64 + (line & 1) * 32 < p.Cout;
+    return ok ? (unsigned)((((rn * p.H + ry) * p.W + rx) * p.res_cs + ct * 64 + (line & 1) * 32) * 4) : kOob;
+  };
 
   // ---- B staging by LDS-DMA: group image = 32 pieces of 1 KiB; wave w issues pieces 8w .. 8w+7 ----------------------
   // (buffer form: the per-lane part of the address is one constant VGPR, the image / piece offset a scalar -- the global
@@ -178,7 +216,6 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   const int a_lane = ((2 * ty) * PWP + 2 * tx) * PITCH + 2 * kq;    // floats: patch pixel (2ty, 2tx), channels 2kq..
   const int b_lane = kq * 64 + t * 4;                              // floats within a [4 kq][16 n][2 nb][2 cin] block: lane * 16 bytes, linear
 
-  f32x4 acc[16][4];
   // A fragments: two sets -- group g multiplies from set g & 1 while the WHOLE input transform of group g + 1 is written into the other
   // set in ONE MFMA gap: a lone VALU instruction between fp32 MFMAs costs ~15 cycles, the ones right behind it ~3 (probe),
   // so 32 packed adds cost ~120 cycles as one cluster and ~250 as the twelve they used to be
@@ -204,14 +241,36 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   };
 
   // ---- prologue: first tile's patch chunk 0, B group 0, A fragments of group 0 -----------------------------------------
-  unsigned pv[PDMA], pvl[PDMA];
-  int n, rb, hw, bx, ct;
-  {                                                                 // filter DMA first: it flies while the slot offsets are computed
-    const int ct0 = blockIdx.z;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dma_piece((unsigned)(ct0 * G) * (BG_FLOATS * 4), 0, i);
+  // pv: this tile's slot offsets; pvn (RUNON): the workgroup's next tile's (all kOob behind its last tile); pvl: what the staging slots
+  // of the current chunk fetch
+  unsigned pv[PDMA], pvn[PDMA], pvl[PDMA];
+  int n, rb, hw, bx, ct, sp;
+  int nn = 0, rbn = 0, hwn = 0, bxn = 0, ctn = 0;                   // RUNON: the next tile
+  int lt = blockIdx.x;                                              // RUNON: this tile's linear index
+  bool has_next = false;
+  if constexpr (RUNON) {
+    tile_of(lt, bx, sp, ct);
+  } else {
+    bx = blockIdx.x; sp = blockIdx.y; ct = blockIdx.z;
   }
-  make_pv(pv, n, rb, hw, bx, ct);
+  {                                                                 // filter DMA first: it flies while the slot offsets are computed
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dma_piece((unsigned)(ct * G) * (BG_FLOATS * 4), 0, i);
+  }
+  make_pv(pv, std::true_type{}, bx, sp, n, rb, hw);
+  // the offsets of the tile after this one: computed where nothing waits for them (the first tile's under its own first wait, later
+  // ones between two tiles: the one serial piece the run-on loop keeps)
+  auto make_next = [&]() {
+    has_next = lt + (int)gridDim.x < p.ntiles;
+    if (has_next) {
+      int spn;
+      tile_of(lt + (int)gridDim.x, bxn, spn, ctn);
+      make_pv(pvn, std::false_type{}, bxn, spn, nn, rbn, hwn);
+    } else {
+#pragma unroll
+      for (int j = 0; j < PDMA; ++j) pvn[j] = kOob;
+    }
+  };
   unsigned long long t_issued = 0;                                  // DIAG: everything the first wait depends on is in flight from here
   if constexpr (DIAG) t_issued = __builtin_amdgcn_s_memtime();
   // Staging schedule (filter image of group g+1 and a third of a later patch chunk per group, everything by LDS-DMA, no
@@ -222,6 +281,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   // adds vmcnt(0) before any ds_write that follows an LDS-DMA: in-kernel ablation put 13 % of the kernel on those waits.)
 #pragma unroll
   for (int j = 0; j < 4; ++j) patch_dma(NCH > 1 ? pv[j] : kOob, 128, 1, j);
+  if constexpr (RUNON) make_next();
   // (wait + barrier as ONE asm, as at a group's end: __syncthreads() waits vmcnt(0), i.e. also for the four chunk-1 loads just issued,
   //  which nothing reads before group 3; the first group's end, vmcnt(4) behind twelve younger loads, covers them)
   asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -232,6 +292,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
   }
   transform_into(vv[0]);
   int pbuf = 0;                                                     // patch buffer holding the current chunk
+  stamp_at(0, t_start);
   stamp_at(1, t_issued);
   stamp(2);
 
@@ -249,84 +310,112 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
     f32x4 b0[2], b1[2];
     b0[0] = *reinterpret_cast<const f32x4*>(pb);
     b0[1] = *reinterpret_cast<const f32x4*>(pb + 256);
-#pragma unroll
-    for (int f = 0; f < 16; ++f) {
+    static_for<16>([&](auto fc) {
+      constexpr int f = decltype(fc)::value;
       f32x4 (&bc)[2] = (f & 1) ? b1 : b0;
       f32x4 (&bn)[2] = (f & 1) ? b0 : b1;
       const f32x2 a = vv[gl & 1][f];
       // 8 MFMAs; after each one a small piece of the other work, pinned in place, so that every non-MFMA instruction
       // issues in the shadow of an executing MFMA (one wave per SIMD: nothing else would fill the gap)
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int j = k >> 2, nb = k & 3;
-        if (kFirst && j == 0) MFMA0(acc[f][nb], a[j], bc[nb >> 1][(nb & 1) * 2 + j]);
-        else MFMA(acc[f][nb], a[j], bc[nb >> 1][(nb & 1) * 2 + j]);
-        if (k == 0 && f < 15) bn[0] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2) * 256);
-        if (k == 1 && f < 15) bn[1] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2 + 1) * 256);
-        if (f < 4) {                                                // patch row f of the next group: 4 x b64 over two gaps
-          if (k == 2) load_patch(pa, f, 0);
-          if (k == 3) load_patch(pa, f, 2);
+      static_for<8>([&](auto kc) {
+        constexpr int k = decltype(kc)::value, j = k >> 2, nb = k & 3;
+        mfma_named<16 * f + 4 * nb, kFirst && j == 0>(a[j], bc[nb >> 1][(nb & 1) * 2 + j]);
+        if constexpr (k == 0 && f < 15) bn[0] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2) * 256);
+        if constexpr (k == 1 && f < 15) bn[1] = *reinterpret_cast<const f32x4*>(pb + ((f + 1) * 2 + 1) * 256);
+        if constexpr (f < 4) {                                      // patch row f of the next group: 4 x b64 over two gaps
+          if constexpr (k == 2) load_patch(pa, f, 0);
+          if constexpr (k == 3) load_patch(pa, f, 2);
         }
-        if (f == 5 && k == 2) transform_into(vv[(gl + 1) & 1]);       // patch rows landed (read at f < 4): B^T d B, all of it
+        if constexpr (f == 5 && k == 2) transform_into(vv[(gl + 1) & 1]);   // patch rows landed (read at f < 4): B^T d B, all of it
         // staging: the next group's filter image first, then this group's part of a later patch chunk (see above)
-        if (f == 0 && bnext) dma_piece(bimg, (gl + 1) & 1, k);
-        if (f == 1 && k >= 4 && gl != 2) {
+        if constexpr (f == 0) {
+          if (bnext) dma_piece(bimg, (gl + 1) & 1, k);
+        }
+        if constexpr (f == 1 && k >= 4 && gl != 2) {
           constexpr int part = gl == 3 ? 0 : gl + 1;
-          if (RES && gl == 0 && pf_res) patch_dma_from(rsr_pf, pvl[part * 4 + (k - 4)], psoff, pbuf ^ 1, part * 4 + (k - 4));
+          if (RES && !RUNON && gl == 0 && pf_res) patch_dma_from(rsr_pf, pvl[part * 4 + (k - 4)], psoff, pbuf ^ 1, part * 4 + (k - 4));
           else patch_dma(pvl[part * 4 + (k - 4)], psoff, gl == 3 ? pbuf : pbuf ^ 1, part * 4 + (k - 4));
         }
+        if constexpr (RES && RUNON && gl == 0 && f == 2 && k < 2)    // the residual lines, behind this group's patch part
+          junk[k] = __builtin_amdgcn_raw_buffer_load_b32(rsr_pf, pfv[k], 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+      });
+    });
     // group end: the filter image (and, after group 2, the whole next patch chunk) has landed; the patch part issued in
     // this group stays in flight.  Wait and barrier are ONE asm with a memory clobber (no LDS access moves across it):
     // through __syncthreads() or a workgroup fence hipcc waits vmcnt(0) here, the DMA being an LDS write to it.
-    // (a chunk's last group also lets its MFMAs land: they are inline asm, unseen by hipcc's hazard pass, and hipcc puts accumulator
-    //  copies / the epilogue's v_accvgpr_read right behind the loop)
+    // (a chunk's last group also lets its MFMAs land: nothing but these nops stands between a tile's last MFMA and the epilogue's first
+    //  v_accvgpr_read)
+    // (RUNON + RES: group 0's two residual-line loads are younger than its patch part -- six loads stay in flight; they have landed
+    //  by the end of group 1, and only behind group 2's vmcnt(0) are their registers let go)
     if constexpr (gl == 3) asm volatile("s_nop 15\n\ts_nop 15\n\ts_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(gl == 2 ? 0 : 4) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(gl == 2 ? 0 : (RES && RUNON && gl == 0) ? 6 : 4) : "memory");
+    if constexpr (RES && RUNON && gl == 2) asm volatile("" ::"v"(junk[0]), "v"(junk[1]));
   };
 
-  {                                                                 // one tile per workgroup
+  for (;;) {                                                        // the workgroup's tiles: one, or (RUNON) lt, lt + gridDim.x, ...
     using T = std::true_type;
     using F = std::false_type;
+    if constexpr (!RUNON) {
 #pragma unroll
-    for (int j = 0; j < PDMA; ++j) pvl[j] = pv[j];
+      for (int j = 0; j < PDMA; ++j) pvl[j] = pv[j];
+    }
     for (int chunk = 0; chunk < NCH; ++chunk) {                     // 32 channels
       const bool lastc = chunk + 1 == NCH;
       const unsigned ug = (unsigned)(ct * G + chunk * 4) * (BG_FLOATS * 4), gb = BG_FLOATS * 4;
-      const unsigned soff = (unsigned)((chunk + 1) * 128);
-      if (lastc) {                                                  // no next chunk: out-of-range VGPR offsets, the DMA writes zeros
-#pragma unroll                                                      // into the idle buffer (the SGPR offset is not range-checked)
-        for (int j = 4; j < PDMA; ++j) pvl[j] = kOob;
-        if constexpr (RES) {                                        // ... except the two residual-prefetch slots (see rsr_pf)
-          pf_res = true;
+      unsigned soff = (unsigned)((chunk + 1) * 128), soff3 = soff + 128;   // channel offsets of what groups 0, 1 / group 3 fetch
+      unsigned bimg3 = ug + 4 * gb;                                 // group 3: the next chunk's first filter image
+      bool bnext3 = !lastc;
+      if constexpr (RUNON) {
+        // the chunks of the workgroup's tiles are ONE stream (NCH >= 2): groups 0, 1 fetch parts 1, 2 of the stream's next chunk, group 3
+        // part 0 of the one after it and the next group's filter image -- in a tile's last two chunks these belong to the next tile
+        // (behind the last tile pvn is all kOob: the DMA writes zeros into the idle buffer, as in a one-tile launch)
+        const bool nextc = chunk + 2 >= NCH;
 #pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            const int line = s2 * 64 + lane, pw = line >> 1;        // this wave's 64 pixels x two 128-byte halves of their 64 channels
-            const int prow = GEO ? (pw >> 3) : (pw >> 4), pcol = GEO ? (pw & 7) : (pw & 15);
-            int ry = rb + (GEO ? 8 : 4) * wave + prow;
-            const bool wr = wrap_row(ry, hw);
-            const int rn = n + (wr ? 1 : 0), rx = BWP * bx + pcol;
-            const bool ok = rn < p.N && ry < p.H && rx < p.W && ct * 64 + (line & 1) * 32 < p.Cout;
-            // (the group adds soff to every address of this part: taken off here; an offset below soff wraps out of range and that
-            //  one line is simply not prefetched)
-            pvl[4 + s2] = ok ? (unsigned)((((rn * p.H + ry) * p.W + rx) * p.res_cs + ct * 64 + (line & 1) * 32) * 4) - soff : kOob;
+        for (int j = 0; j < 4; ++j) pvl[j] = nextc ? pvn[j] : pv[j];
+#pragma unroll
+        for (int j = 4; j < PDMA; ++j) pvl[j] = lastc ? pvn[j] : pv[j];
+        soff = lastc ? 0u : soff;
+        soff3 = nextc ? (unsigned)((chunk + 2 - NCH) * 128) : soff3;
+        bimg3 = lastc ? (unsigned)(ctn * G) * (BG_FLOATS * 4) : bimg3;
+        bnext3 = !lastc || has_next;
+        if constexpr (RES) {
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2) pfv[s2] = kOob;
+          if (lastc) {
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) pfv[s2] = res_line(s2, n, rb, hw, bx, ct);
           }
         }
-      }
-      if (chunk + 2 >= NCH) {                                       // no chunk after next: the same for the part group 3 fetches
+      } else {
+        if (lastc) {                                                // no next chunk: out-of-range VGPR offsets, the DMA writes zeros
+#pragma unroll                                                      // into the idle buffer (the SGPR offset is not range-checked)
+          for (int j = 4; j < PDMA; ++j) pvl[j] = kOob;
+          if constexpr (RES) {                                      // ... except the two residual-prefetch slots (see rsr_pf)
+            pf_res = true;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pvl[j] = kOob;
+            for (int s2 = 0; s2 < 2; ++s2) {
+              // (the group adds soff to every address of this part: taken off here; an offset below soff wraps out of range and that
+              //  one line is simply not prefetched)
+              const unsigned ro = res_line(s2, n, rb, hw, bx, ct);
+              pvl[4 + s2] = ro != kOob ? ro - soff : kOob;
+            }
+          }
+        }
+        if (chunk + 2 >= NCH) {                                     // no chunk after next: the same for the part group 3 fetches
+#pragma unroll
+          for (int j = 0; j < 4; ++j) pvl[j] = kOob;
+        }
       }
       if (chunk == 0) group(ic<0>{}, T{}, soff, ug + 1 * gb, true); else group(ic<0>{}, F{}, soff, ug + 1 * gb, true);
       group(ic<1>{}, F{}, soff, ug + 2 * gb, true);
       group(ic<2>{}, F{}, soff, ug + 3 * gb, true);
-      group(ic<3>{}, F{}, soff + 128, ug + 4 * gb, !lastc);
+      group(ic<3>{}, F{}, soff3, bimg3, bnext3);
       pbuf ^= 1;
     }
 
-    asm volatile("s_waitcnt vmcnt(0)");                             // (the last, all-out-of-range patch part: LDS is reused below)
+    // (the last, all-out-of-range patch part: LDS is reused below.  RUNON: what is in flight here is the next tile's, and stays so)
+    if (!RUNON || !has_next) asm volatile("s_waitcnt vmcnt(0)");
     stamp(3);
     if constexpr (STATS || BNB != 0) __syncthreads();              // ... by EVERY wave's zero-writing DMAs before any wave's partial sums land there
     // ---- epilogue: output transform per (tile, channel), scale/shift (+res) (+relu), store ----------------------------
@@ -397,8 +486,8 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
           res_fetch(0, 0);                                           // free up (L2 hits: the last chunk prefetched the lines); 32
           res_fetch(1, 1);                                           // registers instead of 64
         }
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
+        static_for<4>([&](auto nbc) {
+          constexpr int nb = decltype(nbc)::value;
           __builtin_amdgcn_sched_barrier(0);
           if constexpr (BNB != 0) {
             if (nb < 3) fetch(nb + 1, (nb + 1) & 1);
@@ -418,16 +507,16 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
           }
           // A^T M over the frequency rows, all four tiles r at once -- as two-float halves with the subtractions as explicit packed
           // instructions: left to hipcc every vector subtraction here became scalar v_sub_f32 (192 per epilogue beside fp32 MFMAs' shared pipe)
+          // (acc[f][nb][r] = accumulator register 16 f + 4 nb + r, read here)
           f32x2 sr[2][4][2];
-#pragma unroll
-          for (int nu = 0; nu < 4; ++nu)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-              const f32x2 m0 = {acc[0 + nu][nb][2 * hh], acc[0 + nu][nb][2 * hh + 1]}, m1 = {acc[4 + nu][nb][2 * hh], acc[4 + nu][nb][2 * hh + 1]};
-              const f32x2 m2 = {acc[8 + nu][nb][2 * hh], acc[8 + nu][nb][2 * hh + 1]}, m3 = {acc[12 + nu][nb][2 * hh], acc[12 + nu][nb][2 * hh + 1]};
-              sr[0][nu][hh] = m0 + m1 + m2;
-              sr[1][nu][hh] = pk_sub<false>(pk_sub<false>(m1, m2), m3);
-            }
+          static_for<8>([&](auto nhc) {
+            constexpr int nu = decltype(nhc)::value >> 1, hh = decltype(nhc)::value & 1;
+            constexpr int r0 = 16 * nu + 4 * nb + 2 * hh;
+            const f32x2 m0 = {acc_named<r0>(), acc_named<r0 + 1>()}, m1 = {acc_named<r0 + 64>(), acc_named<r0 + 65>()};
+            const f32x2 m2 = {acc_named<r0 + 128>(), acc_named<r0 + 129>()}, m3 = {acc_named<r0 + 192>(), acc_named<r0 + 193>()};
+            sr[0][nu][hh] = m0 + m1 + m2;
+            sr[1][nu][hh] = pk_sub<false>(pk_sub<false>(m1, m2), m3);
+          });
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
             f32x2 yh[2][2];                                          // [j][half]
@@ -451,7 +540,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
                 if constexpr (RES) o += rv[set][q];
                 if constexpr (RELU) o = fmaxf(o, 0.f);
                 if constexpr (BNB != 0) {                             // the consumer's ReLU mask, then its backward sums
-                  const float tv = BNB == 2 ? ly[set][q] : fmaf(lx[set][q], fa, fb);
+                  const float tv = BNB == 2 ? ly[BNB == 2 ? set : 0][q] : fmaf(lx[set][q], fa, fb);
                   o = tv > 0.f ? o : 0.f;
                   if (live(nb, q)) {
                     st1 += o;
@@ -477,7 +566,7 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
               lds[(wave * 64 + nb * 16 + t) * 2 + 1] = st2;
             }
           }
-        }
+        });
       };
       if (interior) emit(std::true_type{}); else emit(std::false_type{});
       if constexpr (DIAG) {
@@ -496,6 +585,17 @@ __global__ __launch_bounds__(256, 1) void wino_f32(const WinoArgs p) {
           dst[1] = a2;
         }
       }
+    }
+    if constexpr (!RUNON) {
+      break;
+    } else {
+      // on to the next tile: its chunk-0 patch, its first filter image and its group-0 A fragments (vv[0]) are in place or in flight
+      if (!has_next) break;
+      lt += (int)gridDim.x;
+      n = nn; rb = rbn; hw = hwn; bx = bxn; ct = ctn;
+#pragma unroll
+      for (int j = 0; j < PDMA; ++j) pv[j] = pvn[j];
+      make_next();
     }
   }
 }
@@ -531,6 +631,41 @@ __global__ __launch_bounds__(256) void wino_filter_transform(const float* __rest
 }
 
 }  // namespace
+
+// Diagnostic / tests: workgroups of the run-on launches (0 = one per compute unit); a count at or above a launch's tile count gives the
+// one-tile-per-workgroup launch
+static int g_wino_workgroups = 0;
+extern "C" int bevf_debug_wino_workgroups(int n) {
+  BEVF_REQUIRE(n >= 0, "bevf_debug_wino_workgroups: n=%d < 0", n);
+  g_wino_workgroups = n;
+  return BEVF_OK;
+}
+
+// Compute units of the current device, asked once per device
+static int wino_cu_count(int* out) {
+  static std::mutex mu;
+  static std::map<int, int> known;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = known.find(dev);
+    if (it != known.end()) {
+      *out = it->second;
+      return BEVF_OK;
+    }
+    int cus = 0;
+    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess && cus > 0) {
+      known[dev] = cus;
+      *out = cus;
+      return BEVF_OK;
+    }
+  }
+  (void)hipGetLastError();
+  bevf_set_error("conv_wino: cannot read the device's compute-unit count: %s", hipGetErrorString(e));
+  return BEVF_ERR_LAUNCH;
+}
 
 static unsigned long long* g_wino_stamps = nullptr;
 // Diagnostic (tools/wino_stamps.py): buf = device buffer of 6 x 8 bytes (kWinoStamps) per workgroup of the NEXT plain launches (relu, optional residual),
@@ -612,23 +747,51 @@ extern "C" int bevf_conv3x3_wino_f32(const bevf_conv_desc* d, void* stream) {
     a.div_mul = (unsigned)(((1ull << 32) + dv - 1) / dv);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)a.TBX, (unsigned)a.SB, (unsigned)a.nct), block(256);
+  dim3 grid((unsigned)a.TBX, (unsigned)a.SB, (unsigned)a.nct);
+  const dim3 block(256);
+  const bool diag = g_wino_stamps && d->relu;                      // diagnostic launch: same kernel, six time stamps per workgroup
+  // Run-on launch (plain epilogues, at least two patch chunks): one workgroup per compute unit, each walking tiles b, b + G, ... -- when
+  // that is fewer workgroups than tiles and the tile decode's multiply-high is exact ((n + d) * d < 2^32 for both divisors)
+  a.ntiles = (int)ntiles; a.nsp = a.SB * a.TBX; a.nsp_mul = a.tbx_mul = 0;
+  bool runon = false;
+  if (!d->stats && !d->bnb_x && !diag && d->Cin >= 64) {
+    int wgs = g_wino_workgroups;
+    bool pays = true;
+    if (wgs == 0) {
+      const int rc = wino_cu_count(&wgs);
+      if (rc != BEVF_OK) return rc;
+      // The fixed tile -> workgroup assignment gives up the dispatcher's balancing: with few, uneven rounds per compute unit the idle
+      // tail costs more than the run-on saves (measured: 2.8 rounds + 1.0 %, 4.8 rounds + 0.5 %; 8.7 rounds - 3 %, 4 whole rounds
+      // - 9 %; profiles/r10_wino_cells.txt).  A forced count is taken as given.
+      pays = ntiles % wgs == 0 || ntiles >= 8ll * wgs;
+    }
+    const unsigned long long nsp = (unsigned long long)a.nsp, tbx = (unsigned long long)a.TBX;
+    if (pays && wgs < ntiles && ((unsigned long long)ntiles + nsp) * nsp < (1ull << 32) && (nsp + tbx) * tbx < (1ull << 32)) {
+      runon = true;
+      if (nsp > 1) a.nsp_mul = (unsigned)(((1ull << 32) + nsp - 1) / nsp);
+      if (tbx > 1) a.tbx_mul = (unsigned)(((1ull << 32) + tbx - 1) / tbx);
+      grid = dim3((unsigned)wgs);
+    }
+  }
   auto go = [&](auto kern) { return bevf_launch("bevf_conv3x3_wino_f32", kern, grid, block, LDS_BYTES, st, a); };
-  // the launchable instantiations of wino_f32<RES, RELU, STATS, BNB, GEO, DIAG>: BNB 1 / 2 x RES, STATS, DIAG x RES x GEO, plain RES x RELU x GEO
+  // the launchable instantiations of wino_f32<RES, RELU, STATS, BNB, GEO, DIAG, RUNON>: BNB 1 / 2 x RES, STATS, DIAG x RES x GEO,
+  // plain RES x RELU x GEO x RUNON
   if (d->bnb_x)
     return bevf_dispatch_bool(d->res != nullptr, [&](auto R) {
       constexpr bool res = decltype(R)::value;
       return d->bnb_y ? go(&wino_f32<res, false, false, 2>) : go(&wino_f32<res, false, false, 1>);
     });
   if (d->stats) return go(&wino_f32<false, false, true>);
-  const bool diag = g_wino_stamps && d->relu;                      // diagnostic launch: same kernel, six time stamps per workgroup
   if (diag) a.stamps = g_wino_stamps;
   return bevf_dispatch_bool(d->res != nullptr, [&](auto R) {
     return bevf_dispatch_bool(geo1, [&](auto G) {
       constexpr bool res = decltype(R)::value;
       constexpr int geo = decltype(G)::value;
       if (diag) return go(&wino_f32<res, true, false, 0, geo, true>);
-      return d->relu ? go(&wino_f32<res, true, false, 0, geo>) : go(&wino_f32<res, false, false, 0, geo>);
+      return bevf_dispatch_bool(runon, [&](auto O) {
+        constexpr bool ro = decltype(O)::value;
+        return d->relu ? go(&wino_f32<res, true, false, 0, geo, false, ro>) : go(&wino_f32<res, false, false, 0, geo, false, ro>);
+      });
     });
   });
 }

@@ -556,6 +556,10 @@ int bevf_debug_conv3x3_stamps(void* buf);
 /* The same for bevf_conv3x3_wino_f32 (plain ReLU launches): start / first patch DMA issued / first operands transformed / K loop done /
  * epilogue issued / stores acknowledged, 6 x uint64 per workgroup. */
 int bevf_debug_wino_stamps(void* buf);
+/* Diagnostic / tests: the plain launches of bevf_conv3x3_wino_f32 with Cin >= 64 run `n` workgroups that each walk tiles b, b + n,
+ * b + 2n, ... (0 = automatic: one per compute unit); a count at or above a launch's tile count gives one tile per workgroup.  Results
+ * do not depend on it.  Never set by the product path. */
+int bevf_debug_wino_workgroups(int n);
 
 /* Opt-in "f32x3" convolution: same contract as bevf_conv2d_nhwc_f32 (fp32 activations in and out, no colmax), but
  * the products run on the bf16 MFMA over an exact three-way bf16 split of both operands (six partial products,

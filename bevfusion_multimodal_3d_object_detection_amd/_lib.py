@@ -568,7 +568,10 @@ def head_tail(hid, w, bias, outs: Sequence[torch.Tensor], B: int, P: int, hc: in
     d = HeadDesc()
     d.hid, d.w, d.bias, d.B, d.P, d.hc, d.n_sigmoid = _p(hid, hid.dtype), _pc(w), _pc(bias), B, P, hc, n_sigmoid
     for k in range(5):
-        if outs[k].numel() != B * cs[k] * P:
+        if cs[k] == 0:                                               # empty branch: no buffer, a null pointer
+            d.out[k], d.c[k] = None, 0
+            continue
+        if outs[k] is None or outs[k].numel() != B * cs[k] * P:
             raise BevfError("head_tail: output size wrong")
         d.out[k], d.c[k] = _pc(outs[k]), cs[k]
     fn = "bevf_head_tail_" + _sfx(hid)

@@ -1,6 +1,8 @@
 """bf16 storage / fp32 accumulate path (BASELINE configs 3 and 5).  Parity is against the fp32 CPU oracle run on
 the SAME bf16-rounded weights: what differs is only the bf16 rounding of every stored activation, so tolerances
-are bf16-sized (2^-9 per store) and stated per test.  Unpinned by the reference (it has no bf16 run)."""
+are bf16-sized (2^-9 per store) and stated per test.  Unpinned by the reference (it has no bf16 run).
+The bf16 glue kernels (camera mean, bilinear, broadcast, border-class expansion, head tail, max-pool, small-K pointwise and
+dense layers with a bf16 output) are pinned one by one, to half a bf16 ulp of a float64 reference, in tests/test_gpu_glue.py."""
 import pytest
 import torch
 import torch.nn.functional as F

@@ -63,7 +63,7 @@ def test_bf16_stem_pool_is_bit_identical_to_stem_then_maxpool(gpu, N, H, W):
     stem = torch.empty(N * H1 * W1 * 64, device=gpu, dtype=torch.bfloat16)
     L.stem_conv7x7_bf16mma(x, packed, scale, shift, stem, N, H, W)
     ref = torch.empty(N * Hp * Wp * 64, device=gpu, dtype=torch.bfloat16)
-    L.maxpool3x3s2(stem, ref, N, H1, W1, 64)
+    L.maxpool3x3s2(stem, ref, N, H1, W1, 64)                     # the bf16 max-pool itself is pinned to torch by tests/test_gpu_glue.py::test_maxpool
     got = torch.full((N * Hp * Wp * 64,), float("nan"), device=gpu, dtype=torch.bfloat16)
     L.stem_pool_bf16mma(x, packed, scale, shift, got, N, H, W)
     assert bool(torch.isfinite(got.float()).all())               # every pooled element was written

@@ -239,6 +239,11 @@ SIGNATURES = {
     "bevf_frustum_pool_bwd_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                             C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                             C.c_size_t] + [C.c_int] * 2 + [C.c_void_p]),
+    "bevf_depth_ce_work_doubles": (C.c_size_t, []),
+    "bevf_depth_targets_f64": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_int] * 5
+                               + [C.c_double] * 2 + [C.c_int] * 2 + [C.c_void_p] * 2),
+    "bevf_depth_ce_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bevf_depth_ce_bwd_f32": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_size_t, C.c_int, C.c_void_p]),
 }
 
 
@@ -1432,3 +1437,51 @@ def frustum_pool_bwd(cell_of, tables: int, npix: int, P: int, D: int, x, x_bs: i
             raise BevfError(f"frustum_pool_bwd: {name} and dx share storage")
     _call("bevf_frustum_pool_bwd_f32", _pc(cell_of, torch.int32), 0 if tables == 1 and B > 1 else npix * D, npix, D, _p(x), x_bs, x_cs,
           _p(pd), pd_bs, _p(dy), dy_bs, dy_cs, _p(dx), dx_bs, dx_cs, _p(dpd), dpd_bs, B, C)
+
+
+def depth_ce_work_doubles() -> int:
+    """fp64 elements of depth_ce's partials buffer."""
+    return int(lib().bevf_depth_ce_work_doubles())
+
+
+def depth_targets(points, N: int, counts, calib, shared: bool, B: int, ncam: int, Hc: int, Wc: int, D: int, depth_min: float,
+                  depth_max: float, image_size: Sequence[int], target) -> None:
+    """target [B][ncam][Hc][Wc] int32 = the nearest depth bin a LiDAR return puts on each feature pixel, -1 where there is none
+    (bevf_depth_targets_f64).  points [B][N][>= 3] fp32 with strides (rows may be wider than 3 and frames padded); counts [B] int32
+    valid rows per frame or None; calib fp64 [B][ncam][4][4], or [1][ncam][4][4] with shared = True (one calibration for every
+    frame); image_size = (H, W)."""
+    _depth_bins("depth_targets", D)
+    if N:
+        if points.dim() != 3 or points.shape[0] != B or points.shape[1] != N or points.shape[2] < 3 or points.stride(2) != 1:
+            raise BevfError(f"depth_targets: points must be (B, N, >= 3) with unit column stride, got {tuple(points.shape)} "
+                            f"strides {tuple(points.stride())} for B = {B}, N = {N}")
+        p_bs, p_rs = (points.stride(0) if B > 1 else (N - 1) * points.stride(1) + 3), points.stride(1)
+        if p_rs < 3 or p_bs < (N - 1) * p_rs + 3:
+            raise BevfError(f"depth_targets: overlapping point rows (strides {tuple(points.stride())})")
+    else:
+        p_bs = p_rs = 0
+    _need("depth_targets", counts=(counts, B), calib=(calib, (1 if shared else B) * ncam * 16), target=(target, B * ncam * Hc * Wc))
+    _call("bevf_depth_targets_f64", _p(points) if N else None, p_bs, p_rs, N, _pc(counts, torch.int32), _pc(calib, torch.float64),
+          0 if shared else ncam * 16, B, ncam, Hc, Wc, D, float(depth_min), float(depth_max), int(image_size[0]), int(image_size[1]),
+          _pc(target, torch.int32))
+
+
+def depth_ce(logits, l_rs: int, target, nrows: int, D: int, partials, out) -> None:
+    """out = (mean over the rows with target >= 0 of logsumexp(logits[r][0:D]) - logits[r][target[r]], their count) -- (0, 0) when
+    there is none (bevf_depth_ce_f32).  logits fp32 rows at stride l_rs, target [nrows] int32, partials fp64
+    [depth_ce_work_doubles()], out fp32 [2]."""
+    _depth_bins("depth_ce", D)
+    if nrows > 1 << 24:
+        raise BevfError(f"depth_ce: {nrows} rows, at most 2^24 (the count is returned as a float)")
+    _need("depth_ce", logits=(logits, _strided(nrows, D, l_rs)), target=(target, nrows), partials=(partials, depth_ce_work_doubles()),
+          out=(out, 2))
+    _call("bevf_depth_ce_f32", _p(logits), l_rs, _pc(target, torch.int32), nrows, D, _pc(partials, torch.float64), _pc(out))
+
+
+def depth_ce_bwd(pd, p_rs: int, target, g, out, dlogit, x_rs: int, nrows: int, D: int) -> None:
+    """dlogit[r][d] += g[0] / max(out[1], 1) * (pd[r][d] - [d == target[r]]) for d < D on the rows with target >= 0
+    (bevf_depth_ce_bwd_f32); g: one fp32 on the device, out: depth_ce's."""
+    _depth_bins("depth_ce_bwd", D)
+    _need("depth_ce_bwd", pd=(pd, _strided(nrows, D, p_rs)), target=(target, nrows), g=(g, 1), out=(out, 2),
+          dlogit=(dlogit, _strided(nrows, D, x_rs)))
+    _call("bevf_depth_ce_bwd_f32", _p(pd), p_rs, _pc(target, torch.int32), _pc(g), _pc(out), _p(dlogit), x_rs, nrows, D)

@@ -411,19 +411,56 @@ class FlexibleMultiModal3DDetector(nn.Module):
             return self.fusion.camera_calib_tensor(camera_calib, 0, 0)             # None ('mean' still raises)
         return self.fusion.camera_calib_tensor(camera_calib, camera_imgs.shape[0], camera_imgs.shape[1] if camera_imgs.dim() == 5 else 1)
 
+    def _depth_supervision(self, camera_imgs, depth_points, depth_point_counts):
+        """`depth_points=` / `depth_point_counts=` of forward -> (points, counts), or None without them.  Raises BevfError for every
+        combination the depth loss is not built for; the tensors themselves are checked by depth_supervision.check_points."""
+        if depth_points is None:
+            if depth_point_counts is not None:
+                raise E.L.BevfError("depth_point_counts without depth_points: the counts say how many rows of depth_points are valid")
+            return None
+        if not self.use_camera:
+            raise E.L.BevfError("depth_points with a detector that has no camera branch is not supported: there are no depth logits "
+                                "to supervise")
+        kind = getattr(self.fusion, "camera_view_transform", None)
+        if kind not in ("frustum", "lift"):
+            raise E.L.BevfError(f"depth_points with camera_view_transform={kind!r} is not supported: LiDAR depth supervision needs the "
+                                "learned depth distribution of camera_view_transform='frustum' or 'lift'")
+        if self.fusion.depth_net.weight.dtype != torch.float32:
+            raise E.L.BevfError(f"depth_points with {self.fusion.depth_net.weight.dtype} storage is not supported: the depth loss "
+                                "kernels are fp32 only")
+        if camera_imgs is None:
+            raise E.L.BevfError("depth_points without camera_imgs: there are no depth logits to supervise")
+        if not (self.training and (torch.is_grad_enabled() or _any_bn_training(self))):
+            raise E.L.BevfError("depth_points in eval mode is not supported: the depth loss is part of the training step (a validation "
+                                "depth loss: depth_supervision.depth_targets and depth_cross_entropy on depth_net's logits)")
+        return depth_points, depth_point_counts
+
     def forward(self, camera_imgs: Optional[torch.Tensor] = None, lidar_points: Optional[torch.Tensor] = None,
-                radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None) -> Dict[str, torch.Tensor]:
+                radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None, depth_points: Optional[torch.Tensor] = None,
+                depth_point_counts: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
-        fusion's rig for every frame."""
+        fusion's rig for every frame.
+        depth_points (train mode, camera_view_transform='frustum' or 'lift'): fp32 (B, N, >= 3) LiDAR points on the
+        device in the frame of point_cloud_range -- usually lidar_points itself, though a camera-only detector may be given them
+        too --, depth_point_counts (B,) their valid rows per frame (None: all; all-zero rows are padding either way).  The result
+        then also holds 'depth_loss', the mean cross entropy of depth_net's logits against the nearest LiDAR return's depth bin
+        under the step's calibration (differentiable, add w * depth_loss to the training loss), and 'depth_pixels', the number of
+        feature pixels that had a return."""
+        depth_sup = self._depth_supervision(camera_imgs, depth_points, depth_point_counts)
         camera_calib = self.camera_calib_tensor(camera_imgs, camera_calib)
         if hasattr(self.fusion, "check_lift_supported"):
             self.fusion.check_lift_supported()
             self.fusion.check_frustum_supported()
+        if depth_sup is not None:
+            from . import depth_supervision
+            depth_sup = depth_supervision.check_points(*depth_sup)
         if self.training and (torch.is_grad_enabled() or _any_bn_training(self)):
             # under no_grad a train-mode model still normalises with batch statistics and updates the running buffers, as torch does
             from . import training                      # train-mode BN + tape + hand-written backward (training.py)
             E.require_cuda(camera_imgs, lidar_points)
+            if depth_sup is not None:
+                return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib, depth_sup)
             return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib)
         with torch.no_grad():
             return self._forward_inference(camera_imgs, lidar_points, radar_points, camera_calib)

@@ -985,8 +985,23 @@ class _FusionBranchTape:
     """One input branch of FusionTape, owning its layer records: forward(x, B, concat, ccs, slot, cam_geom, camera_calib) fills the
     branch's bev_channels-wide slot of the concatenated NHWC map (row stride ccs), backward(dconcat, sink) returns the gradient of x."""
 
+    depth_sup = None      # (points, counts) of the step's depth supervision: FusionTape sets it on a learned-depth camera branch
+    depth = None          # the branch's DepthLossTape once its forward has run with depth_sup
+    depth_grad = None     # the gradient arriving at depth.out[0]: DetectorTape sets it before the backward
+
     def __init__(self, fus):
         self.fus, self.H, self.W, self.bc, self.pair = fus, fus.bev_h, fus.bev_w, fus.bev_channels, ConvPair()
+
+    def _depth_forward(self, logits, calib, B, ncam, Hc, Wc, rows) -> None:
+        """After softmax_rows: the LiDAR depth targets and the cross entropy of the padded logits (DepthLossTape)."""
+        if self.depth_sup is not None:
+            self.depth = DepthLossTape(self.fus, self.depth_sup, calib, B, ncam, Hc, Wc, logits.device)
+            self.depth.forward(logits, self.Dp, rows)
+
+    def _depth_backward(self, dlogit, rows) -> None:
+        """After softmax_rows_bwd, before depth_net's backward: the depth loss's share of dlogit."""
+        if self.depth is not None and self.depth_grad is not None:
+            self.depth.backward(self.pd, self.depth_grad, dlogit, self.Dp, rows)
 
     def _slot(self, buf):
         """This branch's [B*H*W][bev_channels] columns of a concatenated NHWC map."""
@@ -1079,6 +1094,38 @@ class _PaddedDepthNet:
         return _Sink()
 
 
+class DepthLossTape:
+    """LiDAR depth supervision of a learned-depth branch tape (depth_supervision.py): the targets of depth_sup =
+    (points (B, N, >= 3) fp32, counts (B,) int32 or None) under the step's calibration -- calib = (fp64 [B, ncam, 4, 4], image_size),
+    or the module rig's for every frame (stride 0) when None -- and the cross entropy of the tape's padded logits against them.
+    out = (mean loss, supervised pixels) stays on the device; the backward adds the loss's share to dlogit between the softmax
+    backward and depth_net's, scaled by the gradient that arrives at the detector's sixth output."""
+
+    def __init__(self, fus, depth_sup, calib, B, ncam, Hc, Wc, dev):
+        from . import depth_supervision as DS
+        points, counts = depth_sup
+        if points.shape[0] != B:
+            raise L.BevfError(f"depth_points holds {points.shape[0]} frames, the camera input {B}")
+        if calib is None:
+            rig, eng = fus.camera_rig, fus._eng()
+            key = ("depth_calib", rig.key(), str(dev))
+            ct = eng._camera_tables.get(key)
+            if ct is None:
+                ct = eng._camera_tables[key] = DS.calib_tensor(rig, dev)
+            image_size = rig.image_size
+        else:
+            ct, image_size = calib[0].to(dev).contiguous(), calib[1]
+        self.D = fus.cam_depth[0]
+        self.target = DS.build_targets(points, counts, ct, image_size, Hc, Wc, fus.cam_depth).view(-1)
+        self.out = _new(2, dev)
+
+    def forward(self, logits, width: int, rows: int) -> None:
+        L.depth_ce(logits, width, self.target, rows, self.D, _new(L.depth_ce_work_doubles(), logits.device, torch.float64), self.out)
+
+    def backward(self, pd, g, dlogit, width: int, rows: int) -> None:
+        L.depth_ce_bwd(pd, self.D, self.target, g.reshape(1).float().contiguous(), self.out, dlogit, width, rows, self.D)
+
+
 class CameraLiftBranchTape(_FusionBranchTape):
     """Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net -> softmax over the depth bins -> the lift gather through the module
     rig's lift table -> camera_proj on the grid, the slot copy.  Keeps x and Pd; the backward runs the transposed table (dx and dPd
@@ -1098,6 +1145,7 @@ class CameraLiftBranchTape(_FusionBranchTape):
         logits, _, _ = self.dn.forward(cam, B * ncam, Hc, Wc)
         self.x, self.pd = cam, _new(rows * tab.D, dev)
         L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
+        self._depth_forward(logits, None, B, ncam, Hc, Wc, rows)
         proj = _new(B * self.H * self.W * Cc, dev)
         tab.lift(cam, self.pd, proj, B, Cc)
         self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
@@ -1110,6 +1158,7 @@ class CameraLiftBranchTape(_FusionBranchTape):
         tab.lift_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # transposed table: every element written once
         dlogit = _new(rows * self.Dp, dev)
         L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
+        self._depth_backward(dlogit, rows)
         dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
         return dcam
 
@@ -1140,6 +1189,7 @@ class CameraFrustumBranchTape(_FusionBranchTape):
         logits, _, _ = self.dn.forward(cam, B * ncam, Hc, Wc)
         self.x, self.pd = cam, _new(rows * tab.D, dev)
         L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
+        self._depth_forward(logits, self.calib, B, ncam, Hc, Wc, rows)
         proj = _new(B * self.H * self.W * Cc, dev)
         tab.pool(cam, self.pd, proj, B, Cc)
         self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
@@ -1156,6 +1206,7 @@ class CameraFrustumBranchTape(_FusionBranchTape):
         tab.pool_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # every element of both written once
         dlogit = _new(rows * self.Dp, dev)
         L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
+        self._depth_backward(dlogit, rows)
         dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
         return dcam
 
@@ -1231,9 +1282,13 @@ class FusionTape:
         self.branches = [self.BRANCHES[fus.camera_view_transform](fus) if fus.use_camera else None,
                          self.BRANCHES[fus.lidar_kind](fus) if fus.use_lidar else None, RadarBranchTape(fus) if fus.use_radar else None]
 
-    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None):
-        """camera_calib ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape."""
+    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None, depth_sup=None):
+        """camera_calib ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape.
+        depth_sup ('frustum' / 'lift' branches): (points, counts) of the LiDAR depth supervision, see DepthLossTape; the camera
+        branch then keeps its loss in .depth."""
         fus = self.fus
+        if depth_sup is not None:
+            self.branches[0].depth_sup = depth_sup
         self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
         feats = (cam_feat, lid_feat, rad_feat)
         present, ccs, B = E.concat_slots(fus, self.branches, feats,
@@ -1318,9 +1373,10 @@ class DetectorTape:
     the order radar, camera, LiDAR (RELU_TRACE follows it), then fusion and head.  The backward walks them in reverse and marks
     where gradients become final for the data-parallel all-reduce (sink.ready())."""
 
-    def __init__(self, model, camera_calib=None):
+    def __init__(self, model, camera_calib=None, depth_sup=None):
         self.m = model
         self.camera_calib = camera_calib          # per-frame calibration of the 'project' camera branch (FusionTape.forward)
+        self.depth_sup = depth_sup                # (points, counts): LiDAR depth supervision of the 'frustum' / 'lift' branch, a sixth output
 
     def forward(self, imgs, pts, radars):
         m = self.m
@@ -1350,12 +1406,21 @@ class DetectorTape:
             lid_feat = self.lidar.forward(pts)
             B = self.lidar.B
         self.fusion = FusionTape(m.fusion)
-        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None)
+        if self.depth_sup is None:
+            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None)
+        else:
+            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None, self.depth_sup)
         self.head = HeadTape(m.det_head)
-        return self.head.forward(fused, B, self.fusion.H, self.fusion.W)
+        outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
+        if self.depth_sup is None:
+            return outs
+        self.depth_out = self.fusion.branches[0].depth.out
+        return outs + [self.depth_out[0]]
 
     def backward(self, douts: List[torch.Tensor], sink: GradSink) -> list:
-        dfused, pre_f2 = self.head.backward(douts, sink, fuse_next=self.fusion.f2)
+        if self.depth_sup is not None:
+            self.fusion.branches[0].depth_grad = douts[5]
+        dfused, pre_f2 = self.head.backward(douts[:5], sink, fuse_next=self.fusion.f2)
 
         def camera(dfeat):
             sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
@@ -1442,10 +1507,15 @@ def wants_train_path(module: nn.Module) -> bool:
     return any_bn_training(module) or torch.is_grad_enabled()
 
 
-def detector_train_forward(model, imgs, pts, radars, camera_calib=None) -> Dict[str, torch.Tensor]:
-    tape = DetectorTape(model, camera_calib)
+def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_sup=None) -> Dict[str, torch.Tensor]:
+    """depth_sup = (points, counts): the LiDAR depth supervision of the 'frustum' / 'lift' camera branch (DepthLossTape); the
+    result then carries 'depth_loss', a sixth output of the same autograd node, and 'depth_pixels', the supervised pixels."""
+    tape = DetectorTape(model, camera_calib, depth_sup)
     outs = _TapeFn.apply("detector", tape.forward, tape.backward, _GRAD_REDUCER, 3, imgs, pts, radars, *_trainable(model))
-    return dict(zip(E.HEAD_BRANCHES, outs))
+    res = dict(zip(E.HEAD_BRANCHES, outs))
+    if depth_sup is not None:
+        res["depth_loss"], res["depth_pixels"] = outs[5], tape.depth_out[1].clone()
+    return res
 
 
 # ---- stand-alone modules under train-mode BatchNorm (ref src/encoders.py:792-846 calls freshly built encoders, i.e. in train mode) ----

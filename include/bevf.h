@@ -531,6 +531,47 @@ int bevf_frustum_pool_bwd_f32(const int32_t* cell_of, size_t c_stride, int npix,
                               const float* pd, size_t pd_bs, const float* dy, size_t dy_bs, int dy_cs, float* dx,
                               size_t dx_bs, int dx_cs, float* dpd, size_t dpd_bs, int B, int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * LiDAR depth supervision of the 'frustum' and 'lift' camera branches (csrc/depth_sup.hip; BEVDepth, Li et al.
+ * 2022): opt-in through the detector's `depth_points=` argument and depth_supervision.py.  None of these has a counterpart in
+ * the reference.  fp64 geometry, fp32 logits, stream-ordered, capture-safe (nothing allocated, no host synchronisation), no
+ * floating-point atomics, two launches give the same bits.  D = depth bins, 1 <= D <= 64.
+ *
+ * bevf_depth_targets_f64.  points: B frames of N rows, frame b at points + b * p_bs, row p at + p * p_stride floats, columns
+ * 0-2 = (x, y, z) in the frame the calibration maps from; counts [B] = valid rows per frame or NULL (= N).  calib as
+ * bevf_frustum_table_build_f64 takes it, frame b at calib + b * calib_bs doubles; calib_bs == 0: one calibration for all frames
+ * (the static rig).  Rows 0-2 only are read; ROW 2 MUST EQUAL THE DEPTH ROW.  For frame b, camera c and point p = (x, y, z, 1):
+ *     q = calib[b][c][0:3] . p,   zc = q_2,   u = q_0 / zc,   v = q_1 / zc
+ *     X = floor((u + 1/2) Wc / img_w),   Y = floor((v + 1/2) Hc / img_h)      (the inverse of u = (x + 1/2) img_w / Wc - 1/2)
+ *     d = min(floor((zc - depth_min) D / (depth_max - depth_min)), D - 1)     (camera_rig.depth_bin_of)
+ * The point counts for camera c when depth_min <= zc < depth_max, 0 <= X < Wc and 0 <= Y < Hc.  A row whose x, y, z are all
+ * exactly 0 is padding, and so is a row at or past counts[b]: padding never counts.  target [B][ncam][Hc][Wc] int32 = the
+ * smallest d among the pixel's points (the nearest return), -1 for a pixel with none: filled with 0xFFFFFFFF in the stream,
+ * then one thread per (point, camera, frame) and an integer atomicMin on the unsigned bin, which no order can change.
+ * B <= 65535, ncam <= 65535.  No reference counterpart.
+ *
+ * bevf_depth_ce_f32.  logits: nrows rows of D floats at row stride l_rs (columns >= D are never read); target [nrows] as above
+ * (< 0: not supervised, else < D).  Row r with target t >= 0 contributes logsumexp(logits[r][0:D]) - logits[r][t], computed
+ * from the logits with the row maximum subtracted (one lane per bin, bevf_softmax_rows_f32's butterfly).  Workgroups write
+ * (sum, count) pairs in fp64 to partials (bevf_depth_ce_work_doubles() doubles, 8-byte aligned) in a fixed order and a second,
+ * single-wave launch adds them in fp64: out[0] = sum / max(count, 1), out[1] = count (exact as a float: nrows <= 2^24 is
+ * required).  With no supervised row out = (0, 0) exactly.  No reference counterpart.
+ *
+ * bevf_depth_ce_bwd_f32.  pd: the softmax of the logits, rows at stride p_rs; g: the gradient arriving at out[0], ONE FLOAT ON
+ * THE DEVICE; out: what bevf_depth_ce_f32 wrote.  For a row with a target
+ *     dlogit[r][d] += g[0] / max(out[1], 1) * (pd[r][d] - [d == target[r]])     for d < D     (rows at stride x_rs)
+ * Rows without a target and columns >= D are not touched; every touched element is read and written once.  No reference
+ * counterpart.
+ * ------------------------------------------------------------------------------------------ */
+size_t bevf_depth_ce_work_doubles(void);
+int bevf_depth_targets_f64(const float* points, size_t p_bs, int p_stride, int N, const int32_t* counts, const double* calib,
+                           size_t calib_bs, int B, int ncam, int Hc, int Wc, int D, double depth_min, double depth_max,
+                           int img_h, int img_w, int32_t* target, void* stream);
+int bevf_depth_ce_f32(const float* logits, int l_rs, const int32_t* target, size_t nrows, int D, double* partials, float* out,
+                      void* stream);
+int bevf_depth_ce_bwd_f32(const float* pd, int p_rs, const int32_t* target, const float* g, const float* out, float* dlogit,
+                          int x_rs, size_t nrows, int D, void* stream);
+
 /* ==========================================================================================
  * bf16 storage, fp32 accumulate (BASELINE configs 3 and 5).  Same layouts and geometry as the fp32 entry
  * points, element type bfloat16 wherever a pointer is typed void*: the convolution runs on

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import camera_rig as CR
 
 
 # ---- packing ---------------------------------------------------------------------------------------
@@ -532,6 +533,11 @@ class CameraTable:
     t_col: torch.Tensor
     t_w: torch.Tensor
 
+    @classmethod
+    def from_host(cls, t, dev) -> "CameraTable":
+        """camera_rig.ProjectionTable `t` copied to device `dev`."""
+        return cls(t.P, t.ncols, *(torch.from_numpy(getattr(t, n)).to(dev) for n in ("row_ptr", "col", "w", "t_row_ptr", "t_col", "t_w")))
+
     def project(self, x, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
         """y[b][cell][0:C] (row stride y_cs) = the lift of x = NHWC camera features [B][ncols][C]."""
         L.csr_gather(self.row_ptr, self.col, self.w, self.P, self.ncols, x, self.ncols * C, C, y, self.P * (y_cs or C),
@@ -542,24 +548,38 @@ class CameraTable:
         L.csr_gather(self.t_row_ptr, self.t_col, self.t_w, self.ncols, self.P, dy, self.P * C, C, dx, self.ncols * C, C, B, C)
 
 
+def _check_rig_cameras(fus: nn.Module, ncam: int) -> None:
+    rig = fus.camera_rig
+    if ncam != rig.num_cameras:
+        raise L.BevfError(f"BEV fusion (camera_view_transform='{fus.camera_view_transform}'): the camera rig has {rig.num_cameras} "
+                          f"cameras ({', '.join(rig.names)}) but the camera input has {ncam} (a 4-D input is one camera); pass "
+                          f"(B, {rig.num_cameras}, C, H, W) features or call set_camera_rig() with a matching rig")
+
+
+def _rig_cached(fus: nn.Module, kind: tuple, extra: tuple, what: str, dev, build):
+    """What the fusion's engine caches for the module rig under kind + (rig key,) + extra + (device,), until set_camera_rig: built
+    by build() on first use, which has to happen outside a graph capture (`what` names it in the refusal)."""
+    tables = fus._eng()._camera_tables
+    key = kind + (fus.camera_rig.key(),) + extra + (str(dev),)
+    if key not in tables:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.BevfError(f"BEV fusion: the camera {what} is built on first use, which cannot happen inside a graph "
+                              "capture -- run the forward once before capturing")
+        tables[key] = build()
+    return tables[key]
+
+
+def _grid_key(fus: nn.Module, Hc: int, Wc: int) -> tuple:
+    return Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range)
+
+
 def camera_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraTable:
     """The projection table of FlexibleBEVFusion `fus` ('project' branch) for ncam cameras of Hc x Wc features, built on the host in
     fp64 (camera_rig.build_projection_table) on first use and cached on the fusion's engine until set_camera_rig."""
     _check_rig_cameras(fus, ncam)
-    rig, eng = fus.camera_rig, fus._eng()
-    key = (rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_num_heights,
-           fus.cam_min_depth, str(dev))
-    tab = eng._camera_tables.get(key)
-    if tab is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise L.BevfError("BEV fusion: the camera projection table is built on first use, which cannot happen inside a graph "
-                              "capture -- run the forward once before capturing")
-        from . import camera_rig as CR
-        t = CR.build_projection_table(rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, fus.cam_num_heights, fus.cam_min_depth)
-        d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
-        tab = CameraTable(t.P, t.ncols, d(t.row_ptr), d(t.col), d(t.w), d(t.t_row_ptr), d(t.t_col), d(t.t_w))
-        eng._camera_tables[key] = tab
-    return tab
+    heights = (fus.cam_num_heights, fus.cam_min_depth)
+    return _rig_cached(fus, (), _grid_key(fus, Hc, Wc) + heights, "projection table", dev, lambda: CameraTable.from_host(
+        CR.build_projection_table(fus.camera_rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, *heights), dev))
 
 
 @dataclass
@@ -577,6 +597,12 @@ class CameraLiftTable:
     t_bin: torch.Tensor
     t_w: torch.Tensor
 
+    @classmethod
+    def from_host(cls, t, dev) -> "CameraLiftTable":
+        """camera_rig.LiftTable `t` copied to device `dev`."""
+        return cls(t.P, t.ncols, t.D, *(torch.from_numpy(getattr(t, n)).to(dev)
+                                        for n in ("row_ptr", "col2", "w", "t_row_ptr", "t_cell", "t_bin", "t_w")))
+
     def lift(self, x, pd, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
         """y[b][cell][0:C] (row stride y_cs) = sum_e w_e pd[b][pix_e][bin_e] x[b][pix_e][0:C]: x NHWC features [B][ncols][C], pd the
         depth distribution [B][ncols][D]."""
@@ -589,34 +615,15 @@ class CameraLiftTable:
                        self.ncols * self.D, dy, self.P * C, C, dx, self.ncols * C, C, dpd, self.ncols * self.D, B, C)
 
 
-def _check_rig_cameras(fus: nn.Module, ncam: int) -> None:
-    rig = fus.camera_rig
-    if ncam != rig.num_cameras:
-        raise L.BevfError(f"BEV fusion (camera_view_transform='{fus.camera_view_transform}'): the camera rig has {rig.num_cameras} "
-                          f"cameras ({', '.join(rig.names)}) but the camera input has {ncam} (a 4-D input is one camera); pass "
-                          f"(B, {rig.num_cameras}, C, H, W) features or call set_camera_rig() with a matching rig")
-
-
 def camera_lift_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> CameraLiftTable:
     """The lift table of FlexibleBEVFusion `fus` ('lift' branch) for ncam cameras of Hc x Wc features, built on the host in fp64
     (camera_rig.build_lift_table) on first use and cached on the fusion's engine, next to the projection tables, until
     set_camera_rig."""
     _check_rig_cameras(fus, ncam)
-    rig, eng = fus.camera_rig, fus._eng()
-    key = ("lift", rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_num_heights,
-           fus.cam_min_depth, fus.cam_depth, str(dev))
-    tab = eng._camera_tables.get(key)
-    if tab is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise L.BevfError("BEV fusion: the camera lift table is built on first use, which cannot happen inside a graph "
-                              "capture -- run the forward once before capturing")
-        from . import camera_rig as CR
-        t = CR.build_lift_table(rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, fus.cam_num_heights, fus.cam_min_depth,
-                                *fus.cam_depth)
-        d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
-        tab = CameraLiftTable(t.P, t.ncols, t.D, d(t.row_ptr), d(t.col2), d(t.w), d(t.t_row_ptr), d(t.t_cell), d(t.t_bin), d(t.t_w))
-        eng._camera_tables[key] = tab
-    return tab
+    heights = (fus.cam_num_heights, fus.cam_min_depth)
+    key = _grid_key(fus, Hc, Wc) + heights + (fus.cam_depth,)
+    return _rig_cached(fus, ("lift",), key, "lift table", dev, lambda: CameraLiftTable.from_host(
+        CR.build_lift_table(fus.camera_rig, Hc, Wc, fus.pc_range, fus.bev_h, fus.bev_w, *heights, *fus.cam_depth), dev))
 
 
 def depth_net_width(D: int) -> int:
@@ -634,22 +641,37 @@ def pad_depth_net(conv, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return w.contiguous(), b.contiguous()
 
 
-class FrameCameraTables:
+class _DeviceTables:
+    """What the tables built on the device from a calibration tensor share: the fusion engine they belong to, `version`, which
+    counts the builds -- eager ones in build(), the replay of a captured one through invalidate(), which GraphedDetector calls: a
+    tape that finds another version in its backward rebuilds from the calibration it kept -- and the grid the builds take."""
+
+    def __init__(self, eng: "_Engine"):
+        self.eng, self.version = eng, 0
+
+    def invalidate(self) -> None:
+        """The buffers are about to be rewritten by launches this object does not see (a graph replay of a captured build)."""
+        self.version += 1
+
+    def grid(self):
+        """-> ((x0, y0, vx, vy) of the module's pillar grid, its z range rounded to fp32), as the table builds take them."""
+        import numpy as np
+        from .encoders import pillar_grid
+        m = self.eng.module
+        return pillar_grid(m.pc_range, m.bev_h, m.bev_w)[:4], (float(np.float32(m.pc_range[2])), float(np.float32(m.pc_range[5])))
+
+
+class FrameCameraTables(_DeviceTables):
     """The per-frame sibling of CameraTable: one projection table per frame, built on the device from a [B][ncam][4][4] fp64
     calibration tensor (camera_rig.calib_matrices) into grow-only buffers of the fusion's engine, of the worst-case capacity
     P * num_heights * ncam * 4 entries per frame -- no host synchronisation and no allocation once the buffers exist, so build,
-    transposition and gather run inside a graph capture.  `version` counts the builds -- eager ones in build(), the replay of a
-    captured one through invalidate(), which GraphedDetector calls: a tape that finds another version in its backward rebuilds
-    from the calibration it kept."""
+    transposition and gather run inside a graph capture.  `version`: _DeviceTables."""
 
     def __init__(self, eng: "_Engine"):
-        self.eng = eng
-        self.version = 0
+        super().__init__(eng)
         self.t_version = -1
 
     def build(self, calib: torch.Tensor, image_size, B: int, ncam: int, Hc: int, Wc: int) -> None:
-        import numpy as np
-        from .encoders import pillar_grid
         m = self.eng.module
         self.B, self.P, self.ncols = B, m.bev_h * m.bev_w, ncam * Hc * Wc
         self.cap = cap = L.camera_table_capacity(self.P, m.cam_num_heights, ncam)
@@ -658,14 +680,9 @@ class FrameCameraTables:
         self.col = buf("ct_col", B * cap, torch.int32)
         self.w = buf("ct_w", B * cap, torch.float32)
         self.work = buf("ct_work", L.camera_table_work_elems(B, cap, max(self.P, self.ncols)), torch.int32)
-        x0, y0, vx, vy, _ = pillar_grid(m.pc_range, m.bev_h, m.bev_w)
-        z = (float(np.float32(m.pc_range[2])), float(np.float32(m.pc_range[5])))
-        L.camera_table_build(calib, B, ncam, (x0, y0, vx, vy), m.bev_h, m.bev_w, z, m.cam_num_heights, m.cam_min_depth, image_size,
+        grid, z = self.grid()
+        L.camera_table_build(calib, B, ncam, grid, m.bev_h, m.bev_w, z, m.cam_num_heights, m.cam_min_depth, image_size,
                              Hc, Wc, self.row_ptr, self.col, self.w, cap, self.work)
-        self.version += 1
-
-    def invalidate(self) -> None:
-        """The buffers are about to be rewritten by launches this object does not see (a graph replay of a captured build)."""
         self.version += 1
 
     def transpose(self) -> None:
@@ -692,37 +709,41 @@ class FrameCameraTables:
                             self.ncols * C, C, B, C)
 
 
-def frame_camera_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev) -> FrameCameraTables:
-    """The per-frame projection tables of FlexibleBEVFusion `fus` for camera_calib = (fp64 [B, ncam, 4, 4] tensor, image_size) as
-    FlexibleBEVFusion.camera_calib_tensor returns it, built now on the current stream."""
+def _frame_tables(cls, fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev):
+    """The fusion engine's one `cls` object (made on first use), built now on the current stream for camera_calib = (fp64
+    [B, ncam, 4, 4] tensor, image_size) as FlexibleBEVFusion.camera_calib_tensor returns it."""
     calib, image_size = camera_calib
     if tuple(calib.shape) != (B, ncam, 4, 4):
         raise L.BevfError(f"BEV fusion: camera_calib is {tuple(calib.shape)} but the camera features are {B} frames of {ncam} cameras")
     eng = fus._eng()
-    if eng._frame_tables is None:
-        eng._frame_tables = FrameCameraTables(eng)
-    eng._frame_tables.build(calib.to(dev).contiguous(), image_size, B, ncam, Hc, Wc)
-    return eng._frame_tables
+    if cls not in eng._frame_tables:
+        eng._frame_tables[cls] = cls(eng)
+    eng._frame_tables[cls].build(calib.to(dev).contiguous(), image_size, B, ncam, Hc, Wc)
+    return eng._frame_tables[cls]
 
 
-class FrustumTables:
+def frame_camera_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev) -> FrameCameraTables:
+    """The per-frame projection tables of FlexibleBEVFusion `fus` for camera_calib = (fp64 [B, ncam, 4, 4] tensor, image_size) as
+    FlexibleBEVFusion.camera_calib_tensor returns it, built now on the current stream."""
+    return _frame_tables(FrameCameraTables, fus, camera_calib, B, ncam, Hc, Wc, dev)
+
+
+class FrustumTables(_DeviceTables):
     """The lift-splat tables of the 'frustum' branch (camera_rig.FrustumTable) on the device, built there from a [B][ncam][4][4] fp64
     calibration tensor (bevf_frustum_table_build_f64): cell_of [B][ncols * D] for the backward, row_ptr [B][P + 1] / col2
     [B][ncols * D] for the forward -- the capacity is exact, there are no weights.  Per-frame tables (own = False) live in grow-only
     buffers of the fusion's engine: no host synchronisation and no allocation once they exist, so build and pool run inside a graph
-    capture; `version` counts the builds as FrameCameraTables does.  The module rig's table (own = True) is the same build with
+    capture; `version`: _DeviceTables.  The module rig's table (own = True) is the same build with
     B = 1 into tensors of its own, cached beside the other rig tables and applied to every frame with stride 0."""
 
     def __init__(self, eng: "_Engine", own: bool = False):
-        self.eng, self.own = eng, own
-        self.version = 0
+        super().__init__(eng)
+        self.own = own
 
     def _buf(self, name: str, numel: int, dev) -> torch.Tensor:
         return torch.empty(numel, dtype=torch.int32, device=dev) if self.own else self.eng.buf(name, numel, torch.int32)
 
     def build(self, calib: torch.Tensor, image_size, B: int, ncam: int, Hc: int, Wc: int) -> None:
-        import numpy as np
-        from .encoders import pillar_grid
         m = self.eng.module
         self.D, dmin, dmax = m.cam_depth
         self.tables, self.P, self.ncols = B, m.bev_h * m.bev_w, ncam * Hc * Wc
@@ -732,14 +753,9 @@ class FrustumTables:
         self.row_ptr = self._buf("ft_row_ptr", B * (self.P + 1), dev)
         self.col2 = self._buf("ft_col2", B * cap, dev)
         work = self._buf("ft_work", L.frustum_table_work_elems(B, ncam, m.bev_h, m.bev_w, self.D, Hc, Wc), dev)
-        x0, y0, vx, vy, _ = pillar_grid(m.pc_range, m.bev_h, m.bev_w)
-        z = (float(np.float32(m.pc_range[2])), float(np.float32(m.pc_range[5])))
-        L.frustum_table_build(calib, B, ncam, (x0, y0, vx, vy), m.bev_h, m.bev_w, z, self.D, dmin, dmax, image_size, Hc, Wc,
+        grid, z = self.grid()
+        L.frustum_table_build(calib, B, ncam, grid, m.bev_h, m.bev_w, z, self.D, dmin, dmax, image_size, Hc, Wc,
                               self.cell_of, self.row_ptr, self.col2, work)
-        self.version += 1
-
-    def invalidate(self) -> None:
-        """The buffers are about to be rewritten by launches this object does not see (a graph replay of a captured build)."""
         self.version += 1
 
     def pool(self, x, pd, y, B: int, C: int, y_cs: Optional[int] = None) -> None:
@@ -758,32 +774,19 @@ def camera_frustum_table(fus: nn.Module, ncam: int, Hc: int, Wc: int, dev) -> Fr
     """The frustum table of FlexibleBEVFusion `fus`'s own rig for ncam cameras of Hc x Wc features: built on the device with B = 1
     on first use (outside a graph capture) and cached on the fusion's engine, next to the other rig tables, until set_camera_rig."""
     _check_rig_cameras(fus, ncam)
-    rig, eng = fus.camera_rig, fus._eng()
-    key = ("frustum", rig.key(), Hc, Wc, fus.bev_h, fus.bev_w, tuple(float(v) for v in fus.pc_range), fus.cam_depth, str(dev))
-    tab = eng._camera_tables.get(key)
-    if tab is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise L.BevfError("BEV fusion: the camera frustum table is built on first use, which cannot happen inside a graph "
-                              "capture -- run the forward once before capturing")
-        from . import camera_rig as CR
-        tab = FrustumTables(eng, own=True)
+
+    def build():
+        rig, tab = fus.camera_rig, FrustumTables(fus._eng(), own=True)
         tab.build(torch.from_numpy(CR.calib_matrices([rig])).to(dev), rig.image_size, 1, ncam, Hc, Wc)
-        eng._camera_tables[key] = tab
-    return tab
+        return tab
+    return _rig_cached(fus, ("frustum",), _grid_key(fus, Hc, Wc) + (fus.cam_depth,), "frustum table", dev, build)
 
 
 def frame_frustum_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: int, Wc: int, dev) -> FrustumTables:
     """The per-frame frustum tables of FlexibleBEVFusion `fus` for camera_calib = (fp64 [B, ncam, 4, 4] tensor, image_size) as
     FlexibleBEVFusion.camera_calib_tensor returns it, built now on the current stream."""
-    calib, image_size = camera_calib
-    if tuple(calib.shape) != (B, ncam, 4, 4):
-        raise L.BevfError(f"BEV fusion: camera_calib is {tuple(calib.shape)} but the camera features are {B} frames of {ncam} cameras")
     _check_rig_cameras(fus, ncam)
-    eng = fus._eng()
-    if eng._frustum_tables is None:
-        eng._frustum_tables = FrustumTables(eng)
-    eng._frustum_tables.build(calib.to(dev).contiguous(), image_size, B, ncam, Hc, Wc)
-    return eng._frustum_tables
+    return _frame_tables(FrustumTables, fus, camera_calib, B, ncam, Hc, Wc, dev)
 
 
 def concat_slots(fus: nn.Module, branches, feats, text: str, B: Optional[int] = None):
@@ -811,9 +814,31 @@ class _FusionBranch:
 
 
 class _CameraBranch(_FusionBranch):
+    TABLES = None        # view-transform branches: (the rig-table getter, the per-frame getter, the span name of its build)
+
     def pack(self, m) -> None:
         self.c1 = pack_conv(m.camera_proj[0], m.camera_proj[1], True)
         self.c2 = pack_conv(m.camera_proj[3], m.camera_proj[4], True)
+
+    def table(self, cam, B, geom, camera_calib):
+        """camera_calib None: the module rig's cached table; else per-frame tables built here into the engine's buffers."""
+        _, ncam, Hc, Wc = geom
+        rig_table, frame_tables, span = self.TABLES
+        if camera_calib is None:
+            return rig_table(self.eng.module, ncam, Hc, Wc, cam.device)
+        with _span(span):
+            return frame_tables(self.eng.module, camera_calib, B, ncam, Hc, Wc, cam.device)
+
+    def on_grid(self, span, transform, B, out, ccs) -> None:
+        """The tail of a view-transform branch: transform(proj) fills the cam_proj buffer [B][S_h * S_w][C] under `span`, then
+        camera_proj on the BEV grid, its second conv into the concat slice."""
+        buf, (Sh, Sw, _) = self.eng.buf, self.grid
+        proj = buf("cam_proj", B * Sh * Sw * self.c1.cin)
+        with span:
+            transform(proj)
+        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
+        _run_conv(self.c1, proj, t1, B, Sh, Sw)
+        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
 
 
 class CameraMeanBranch(_CameraBranch):
@@ -839,25 +864,20 @@ class CameraProjectBranch(_CameraBranch):
     """The same camera_proj after camera rig -> BEV grid (one gather), its second conv into the concat slice.  camera_calib None:
     the module rig's cached table; else per-frame tables built here into the engine's buffers."""
 
+    TABLES = (camera_table, frame_camera_tables, "cam_table_build")
+
     def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
-        _, ncam, Hc, Wc = geom
-        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
-        if camera_calib is None:
-            tab = camera_table(m, ncam, Hc, Wc, cam.device)
-        else:
-            with _span("cam_table_build"):
-                tab = frame_camera_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
-        proj = buf("cam_proj", B * Sh * Sw * Cc)
-        with _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (ncam * Hc * Wc + Sh * Sw)):
-            tab.project(cam, proj, B, Cc)
-        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
-        _run_conv(self.c1, proj, t1, B, Sh, Sw)
-        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+        (Sh, Sw, _), Cc = self.grid, self.c1.cin
+        tab = self.table(cam, B, geom, camera_calib)
+        span = _span("cam_project", nbytes=float(cam.element_size()) * B * Cc * (tab.ncols + Sh * Sw))
+        self.on_grid(span, lambda proj: tab.project(cam, proj, B, Cc), B, out, ccs)
 
 
 class CameraLiftBranch(_CameraBranch):
     """Learned depth: depth_net (exact 1x1 conv + bias) -> softmax over the depth bins -> the lift gather through
     the module rig's cached lift table -> camera_proj on the BEV grid, its second conv into the concat slice.  fp32, static rig."""
+
+    TABLES, SPAN = (camera_lift_table, None, None), "cam_lift"         # (a calibration is refused: the rig's table only)
 
     def pack(self, m) -> None:
         super().pack(m)
@@ -878,19 +898,18 @@ class CameraLiftBranch(_CameraBranch):
             L.softmax_rows(logits, self.Dp, pd, self.D, rows, self.D)
         return pd
 
+    def spread(self, tab, cam, pd, proj, B, Cc) -> None:
+        tab.lift(cam, pd, proj, B, Cc)
+
     def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
         _, ncam, Hc, Wc = geom
-        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
-        m.check_lift_supported(camera_calib)
-        tab = camera_lift_table(m, ncam, Hc, Wc, cam.device)
-        rows = B * ncam * Hc * Wc
+        (Sh, Sw, _), Cc, m = self.grid, self.c1.cin, self.eng.module
+        m.check_lift_supported(camera_calib)                       # (each looks at its own kind only, as in FlexibleBEVFusion.forward)
+        m.check_frustum_supported()
+        tab = self.table(cam, B, geom, camera_calib)
         pd = self.depth_distribution(cam, B * ncam, Hc, Wc)
-        proj = buf("cam_proj", B * Sh * Sw * Cc)
-        with _span("cam_lift", nbytes=4.0 * B * (Cc * (ncam * Hc * Wc + Sh * Sw) + rows * self.D // B)):
-            tab.lift(cam, pd, proj, B, Cc)
-        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
-        _run_conv(self.c1, proj, t1, B, Sh, Sw)
-        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+        span = _span(self.SPAN, nbytes=4.0 * B * (Cc * (tab.ncols + Sh * Sw) + tab.ncols * self.D))
+        self.on_grid(span, lambda proj: self.spread(tab, cam, pd, proj, B, Cc), B, out, ccs)
 
 
 class CameraFrustumBranch(CameraLiftBranch):
@@ -898,22 +917,10 @@ class CameraFrustumBranch(CameraLiftBranch):
     built on the device once and shared by every frame, or per-frame tables built here from camera_calib into the engine's buffers
     -- and camera_proj on the BEV grid, its second conv into the concat slice.  fp32."""
 
-    def run(self, cam, B, out, ccs, geom, camera_calib) -> None:
-        _, ncam, Hc, Wc = geom
-        buf, (Sh, Sw, _), Cc, m = self.eng.buf, self.grid, self.c1.cin, self.eng.module
-        m.check_frustum_supported()
-        if camera_calib is None:
-            tab = camera_frustum_table(m, ncam, Hc, Wc, cam.device)
-        else:
-            with _span("cam_frustum_table"):
-                tab = frame_frustum_tables(m, camera_calib, B, ncam, Hc, Wc, cam.device)
-        pd = self.depth_distribution(cam, B * ncam, Hc, Wc)
-        proj = buf("cam_proj", B * Sh * Sw * Cc)
-        with _span("cam_frustum_pool", nbytes=4.0 * B * (Cc * (tab.ncols + Sh * Sw) + tab.ncols * self.D)):
-            tab.pool(cam, pd, proj, B, Cc)
-        t1 = buf("cam_t1", B * Sh * Sw * self.c1.cout)
-        _run_conv(self.c1, proj, t1, B, Sh, Sw)
-        _run_conv(self.c2, t1, out, B, Sh, Sw, y_cs=ccs)
+    TABLES, SPAN = (camera_frustum_table, frame_frustum_tables, "cam_frustum_table"), "cam_frustum_pool"
+
+    def spread(self, tab, cam, pd, proj, B, Cc) -> None:
+        tab.pool(cam, pd, proj, B, Cc)
 
 
 class LidarVectorBranch(_FusionBranch):
@@ -1005,8 +1012,7 @@ class FusionEngine(_Engine):
     def __init__(self, module: nn.Module):
         super().__init__(module)
         self._camera_tables: Dict[tuple, CameraTable] = {}
-        self._frame_tables: Optional[FrameCameraTables] = None
-        self._frustum_tables: Optional[FrustumTables] = None
+        self._frame_tables: Dict[type, _DeviceTables] = {}          # the per-frame tables, one object per class (_frame_tables)
         m = module
         self.branches = [self.BRANCHES[m.camera_view_transform](self) if m.use_camera else None,
                          self.BRANCHES[m.lidar_kind](self) if m.use_lidar else None, RadarBranch(self) if m.use_radar else None]
@@ -1016,9 +1022,8 @@ class FusionEngine(_Engine):
 
     def invalidate_frame_tables(self) -> None:
         """A graph replay is about to rebuild the per-frame tables (FrameCameraTables.invalidate, FrustumTables.invalidate)."""
-        for tables in (self._frame_tables, self._frustum_tables):
-            if tables is not None:
-                tables.invalidate()
+        for tables in self._frame_tables.values():
+            tables.invalidate()
 
     def pack(self) -> None:
         m = self.module

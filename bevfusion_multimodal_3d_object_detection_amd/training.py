@@ -988,9 +988,31 @@ class _FusionBranchTape:
     depth_sup = None      # (points, counts) of the step's depth supervision: FusionTape sets it on a learned-depth camera branch
     depth = None          # the branch's DepthLossTape once its forward has run with depth_sup
     depth_grad = None     # the gradient arriving at depth.out[0]: DetectorTape sets it before the backward
+    TABLES = None         # a view-transform camera branch: engine's (rig-table getter, per-frame getter or None)
+    calib = None          # the per-frame calibration of the step (a clone), None with the module rig's table
 
     def __init__(self, fus):
         self.fus, self.H, self.W, self.bc, self.pair = fus, fus.bev_h, fus.bev_w, fus.bev_channels, ConvPair()
+
+    def _table_forward(self, calib, B, ncam, Hc, Wc, dev):
+        """The branch's table for this step: the module rig's cached one, or per-frame tables built now from calib = (fp64
+        [B, ncam, 4, 4], image_size).  Those live in the fusion engine's buffers, where the next forward replaces them: the tape
+        keeps a clone of the calibration and the build's version for _current_table()."""
+        rig_table, frame_tables = self.TABLES
+        if calib is None:
+            self.table = rig_table(self.fus, ncam, Hc, Wc, dev)
+        else:
+            self.shape = (B, ncam, Hc, Wc, dev)
+            self.table = frame_tables(self.fus, calib, *self.shape)
+            self.calib, self.version = (calib[0].to(dev).clone(), calib[1]), self.table.version
+        return self.table
+
+    def _current_table(self):
+        """The forward's table in the backward, rebuilt from the kept calibration if another forward has replaced it since."""
+        if self.calib is not None and self.table.version != self.version:
+            self.table = self.TABLES[1](self.fus, self.calib, *self.shape)
+            self.version = self.table.version
+        return self.table
 
     def _depth_forward(self, logits, calib, B, ncam, Hc, Wc, rows) -> None:
         """After softmax_rows: the LiDAR depth targets and the cross entropy of the padded logits (DepthLossTape)."""
@@ -1044,31 +1066,25 @@ class CameraMeanBranchTape(_FusionBranchTape):
 class CameraProjectBranchTape(_FusionBranchTape):
     """Input NHWC features, geom = (B, ncam, Hc, Wc): the projection table onto the grid (the module rig's, or per-frame tables built
     here from calib = (fp64 [B, ncam, 4, 4], image_size)), camera_proj there, the slot copy; the transposed table in the backward.  The
-    per-frame tables live in the fusion engine's buffers: the tape keeps the calibration and the build's version, and its backward
-    rebuilds them if another forward has replaced them since."""
+    per-frame tables: _FusionBranchTape._table_forward / _current_table."""
+
+    TABLES = (E.camera_table, E.frame_camera_tables)
 
     def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
         _, ncam, Hc, Wc = geom
         fus, dev = self.fus, cam.device
         Cc = fus.camera_proj[0].weight.shape[1]
-        self.geom, self.calib = (ncam, Hc, Wc, Cc), None
-        if calib is None:
-            self.table = E.camera_table(fus, ncam, Hc, Wc, dev)
-        else:
-            self.table = E.frame_camera_tables(fus, calib, B, ncam, Hc, Wc, dev)
-            self.calib, self.version = (calib[0].to(dev).clone(), calib[1]), self.table.version
+        self.geom = (ncam, Hc, Wc, Cc)
+        tab = self._table_forward(calib, B, ncam, Hc, Wc, dev)
         proj = _new(B * self.H * self.W * Cc, dev)
-        self.table.project(cam, proj, B, Cc)
+        tab.project(cam, proj, B, Cc)
         self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
 
     def backward(self, dconcat, sink):
         dproj = self._pair_from_slot(dconcat, sink)
         B, (ncam, Hc, Wc, Cc) = self.B, self.geom
         dcam = _new(B * ncam * Hc * Wc * Cc, dconcat.device)
-        if self.calib is not None and self.table.version != self.version:
-            self.table = E.frame_camera_tables(self.fus, self.calib, B, ncam, Hc, Wc, dconcat.device)
-            self.version = self.table.version
-        self.table.project_backward(dproj, dcam, B, Cc)                     # transposed table: every element written once
+        self._current_table().project_backward(dproj, dcam, B, Cc)          # transposed table: every element written once
         return dcam
 
 
@@ -1107,11 +1123,8 @@ class DepthLossTape:
         if points.shape[0] != B:
             raise L.BevfError(f"depth_points holds {points.shape[0]} frames, the camera input {B}")
         if calib is None:
-            rig, eng = fus.camera_rig, fus._eng()
-            key = ("depth_calib", rig.key(), str(dev))
-            ct = eng._camera_tables.get(key)
-            if ct is None:
-                ct = eng._camera_tables[key] = DS.calib_tensor(rig, dev)
+            rig = fus.camera_rig
+            ct = E._rig_cached(fus, ("depth_calib",), (), "depth calibration", dev, lambda: DS.calib_tensor(rig, dev))
             image_size = rig.image_size
         else:
             ct, image_size = calib[0].to(dev).contiguous(), calib[1]
@@ -1126,63 +1139,22 @@ class DepthLossTape:
         L.depth_ce_bwd(pd, self.D, self.target, g.reshape(1).float().contiguous(), self.out, dlogit, width, rows, self.D)
 
 
-class CameraLiftBranchTape(_FusionBranchTape):
-    """Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net -> softmax over the depth bins -> the lift gather through the module
-    rig's lift table -> camera_proj on the grid, the slot copy.  Keeps x and Pd; the backward runs the transposed table (dx and dPd
-    in one pass), the softmax backward and depth_net's gradients, whose data gradient takes dx as its residual input: dcam =
-    dx_lift + dx_depthnet without another pass over the feature map."""
+class _LearnedDepthBranchTape(_FusionBranchTape):
+    """The learned-depth camera branches ('lift', 'frustum').  Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net (padded,
+    _PaddedDepthNet) -> softmax over the depth bins -> the depth loss if the step has depth_sup -> the subclass's spread of x * Pd
+    over its table onto the grid -> camera_proj there, the slot copy.  Keeps x and Pd; the backward runs the spread's backward (dx
+    and dPd in one pass), the softmax backward, the depth loss's share and depth_net's gradients, whose data gradient takes dx as
+    its residual input: dcam = dx_spread + dx_depthnet without another pass over the feature map.  A subclass names its TABLES and
+    supplies _spread and _spread_backward."""
 
     def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
         _, ncam, Hc, Wc = geom
         fus, dev = self.fus, cam.device
-        fus.check_lift_supported(calib)
-        Cc = fus.camera_proj[0].weight.shape[1]
-        self.table = tab = E.camera_lift_table(fus, ncam, Hc, Wc, dev)
-        self.geom, self.Dp = (ncam, Hc, Wc, Cc), E.depth_net_width(tab.D)
-        rows = B * tab.ncols
-        self.padded = _PaddedDepthNet(fus.depth_net, self.Dp)
-        self.dn = ConvBNLayer(self.padded, None, relu=False)
-        logits, _, _ = self.dn.forward(cam, B * ncam, Hc, Wc)
-        self.x, self.pd = cam, _new(rows * tab.D, dev)
-        L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
-        self._depth_forward(logits, None, B, ncam, Hc, Wc, rows)
-        proj = _new(B * self.H * self.W * Cc, dev)
-        tab.lift(cam, self.pd, proj, B, Cc)
-        self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
-
-    def backward(self, dconcat, sink):
-        dproj = self._pair_from_slot(dconcat, sink)
-        B, (ncam, Hc, Wc, Cc), tab, dev = self.B, self.geom, self.table, dconcat.device
-        rows = B * tab.ncols
-        dx, dpd = _new(rows * Cc, dev), _new(rows * tab.D, dev)
-        tab.lift_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # transposed table: every element written once
-        dlogit = _new(rows * self.Dp, dev)
-        L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
-        self._depth_backward(dlogit, rows)
-        dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
-        return dcam
-
-
-class CameraFrustumBranchTape(_FusionBranchTape):
-    """Input NHWC features, geom = (B, ncam, Hc, Wc): depth_net -> softmax over the depth bins -> the lift-splat pool over the
-    frustum table (the module rig's, or per-frame tables built here from calib = (fp64 [B, ncam, 4, 4], image_size)) -> camera_proj
-    on the grid, the slot copy.  Keeps x and Pd; the backward is the dense pool backward (dx and dPd in one pass over cell_of), the
-    softmax backward and depth_net's gradients, whose data gradient takes dx as its residual input.  Per-frame tables live in the
-    fusion engine's buffers: the tape keeps the calibration and the build's version and rebuilds them in its backward if another
-    forward has replaced them since (CameraProjectBranchTape)."""
-
-    def forward(self, cam, B, concat, ccs, slot, geom, calib) -> None:
-        _, ncam, Hc, Wc = geom
-        fus, dev = self.fus, cam.device
+        fus.check_lift_supported(calib)                              # (each looks at its own kind only, as in FlexibleBEVFusion.forward)
         fus.check_frustum_supported()
         Cc = fus.camera_proj[0].weight.shape[1]
-        self.geom, self.calib = (ncam, Hc, Wc, Cc), None
-        if calib is None:
-            self.table = tab = E.camera_frustum_table(fus, ncam, Hc, Wc, dev)
-        else:
-            self.table = tab = E.frame_frustum_tables(fus, calib, B, ncam, Hc, Wc, dev)
-            self.calib, self.version = (calib[0].to(dev).clone(), calib[1]), tab.version
-        self.Dp = E.depth_net_width(tab.D)
+        tab = self._table_forward(calib, B, ncam, Hc, Wc, dev)
+        self.geom, self.Dp = (ncam, Hc, Wc, Cc), E.depth_net_width(tab.D)
         rows = B * tab.ncols
         self.padded = _PaddedDepthNet(fus.depth_net, self.Dp)
         self.dn = ConvBNLayer(self.padded, None, relu=False)
@@ -1191,24 +1163,46 @@ class CameraFrustumBranchTape(_FusionBranchTape):
         L.softmax_rows(logits, self.Dp, self.pd, tab.D, rows, tab.D)
         self._depth_forward(logits, self.calib, B, ncam, Hc, Wc, rows)
         proj = _new(B * self.H * self.W * Cc, dev)
-        tab.pool(cam, self.pd, proj, B, Cc)
+        self._spread(tab, cam, self.pd, proj, B, Cc)
         self._pair_to_slot(fus.camera_proj, proj, B, concat, ccs, slot)
 
     def backward(self, dconcat, sink):
         dproj = self._pair_from_slot(dconcat, sink)
-        B, (ncam, Hc, Wc, Cc), dev = self.B, self.geom, dconcat.device
-        if self.calib is not None and self.table.version != self.version:
-            self.table = E.frame_frustum_tables(self.fus, self.calib, B, ncam, Hc, Wc, dev)
-            self.version = self.table.version
-        tab = self.table
+        B, Cc, tab, dev = self.B, self.geom[3], self._current_table(), dconcat.device
         rows = B * tab.ncols
         dx, dpd = _new(rows * Cc, dev), _new(rows * tab.D, dev)
-        tab.pool_backward(self.x, self.pd, dproj, dx, dpd, B, Cc)           # every element of both written once
+        self._spread_backward(tab, self.x, self.pd, dproj, dx, dpd, B, Cc)  # every element of both written once
         dlogit = _new(rows * self.Dp, dev)
         L.softmax_rows_bwd(self.pd, dpd, tab.D, dlogit, self.Dp, self.Dp, rows, tab.D)
         self._depth_backward(dlogit, rows)
         dcam, _ = self.dn.backward(dlogit, self.padded.sink(sink), add=dx)  # dW, db; dx rides the data gradient's residual input
         return dcam
+
+
+class CameraLiftBranchTape(_LearnedDepthBranchTape):
+    """The lift gather through the module rig's lift table (a calibration is refused, so the depth loss takes the rig's too); the
+    transposed table in the backward."""
+
+    TABLES = (E.camera_lift_table, None)
+
+    def _spread(self, tab, x, pd, proj, B, Cc) -> None:
+        tab.lift(x, pd, proj, B, Cc)
+
+    def _spread_backward(self, tab, x, pd, dproj, dx, dpd, B, Cc) -> None:
+        tab.lift_backward(x, pd, dproj, dx, dpd, B, Cc)
+
+
+class CameraFrustumBranchTape(_LearnedDepthBranchTape):
+    """The lift-splat pool over the frustum table (the module rig's, or per-frame tables built here from calib = (fp64
+    [B, ncam, 4, 4], image_size): _FusionBranchTape._table_forward / _current_table); the dense pool backward over cell_of."""
+
+    TABLES = (E.camera_frustum_table, E.frame_frustum_tables)
+
+    def _spread(self, tab, x, pd, proj, B, Cc) -> None:
+        tab.pool(x, pd, proj, B, Cc)
+
+    def _spread_backward(self, tab, x, pd, dproj, dx, dpd, B, Cc) -> None:
+        tab.pool_backward(x, pd, dproj, dx, dpd, B, Cc)
 
 
 class LidarVectorBranchTape(_FusionBranchTape):
@@ -1406,10 +1400,7 @@ class DetectorTape:
             lid_feat = self.lidar.forward(pts)
             B = self.lidar.B
         self.fusion = FusionTape(m.fusion)
-        if self.depth_sup is None:
-            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None)
-        else:
-            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None, self.depth_sup)
+        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None, self.depth_sup)
         self.head = HeadTape(m.det_head)
         outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
         if self.depth_sup is None:

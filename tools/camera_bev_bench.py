@@ -57,8 +57,7 @@ def gather(rounds, dev):
     B, ncam, Hc, Wc, C, S = 8, 6, 57, 100, 512, 128
     t0 = time.perf_counter()
     t = CR.build_projection_table(CR.default_rig(), Hc, Wc, RANGE, S, S)
-    d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
-    tab = engine.CameraTable(t.P, t.ncols, d(t.row_ptr), d(t.col), d(t.w), d(t.t_row_ptr), d(t.t_col), d(t.t_w))
+    tab = engine.CameraTable.from_host(t, dev)
     base = dict(batch=B, cams=ncam, feat=f"{Hc}x{Wc}x{C}", bev=S, nnz=t.nnz, table_build_s=round(time.perf_counter() - t0, 3))
     for dt in (torch.float32, torch.bfloat16):
         x = torch.randn(B * t.ncols * C, device=dev).to(dt)
@@ -128,8 +127,7 @@ def per_frame(rounds, dev):
     out.append(dict(base, stage="device table build, 8 frames", us=round(ub, 1)))
     out.append(dict(base, stage="device table build + transposition, 8 frames", us=round(ubt, 1), transposition_us=round(ubt - ub, 1)))
     t = CR.build_projection_table(CR.default_rig(), Hc, Wc, RANGE, S, S)
-    d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
-    static = engine.CameraTable(t.P, t.ncols, d(t.row_ptr), d(t.col), d(t.w), d(t.t_row_ptr), d(t.t_col), d(t.t_w))
+    static = engine.CameraTable.from_host(t, dev)
     for dt in (torch.float32, torch.bfloat16):
         x = torch.randn(B * t.ncols * C, device=dev).to(dt)
         y = torch.empty(B * t.P * C, device=dev, dtype=dt)
@@ -184,13 +182,11 @@ def lift(rounds, dev):
     out = []
     B, ncam, Hc, Wc, C, S, D = 8, 6, 57, 100, 512, 128, CR.DEFAULT_DEPTH_BINS
     rig = CR.default_rig()
-    d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
     p = CR.build_projection_table(rig, Hc, Wc, RANGE, S, S)
     t0 = time.perf_counter()
     t = CR.build_lift_table(rig, Hc, Wc, RANGE, S, S)
     build_s = round(time.perf_counter() - t0, 3)
-    proj = engine.CameraTable(p.P, p.ncols, d(p.row_ptr), d(p.col), d(p.w), d(p.t_row_ptr), d(p.t_col), d(p.t_w))
-    tab = engine.CameraLiftTable(t.P, t.ncols, t.D, d(t.row_ptr), d(t.col2), d(t.w), d(t.t_row_ptr), d(t.t_cell), d(t.t_bin), d(t.t_w))
+    proj, tab = engine.CameraTable.from_host(p, dev), engine.CameraLiftTable.from_host(t, dev)
     base = dict(batch=B, cams=ncam, feat=f"{Hc}x{Wc}x{C}", bev=S, depth_bins=D, nnz_lift=t.nnz, nnz_project=p.nnz,
                 entry_ratio=round(t.nnz / p.nnz, 4), lift_table_build_s=build_s)
     rows = B * t.ncols
@@ -275,11 +271,9 @@ def frustum(rounds, dev):
     out = []
     B, ncam, Hc, Wc, C, S, D = 8, 6, 57, 100, 512, 128, CR.DEFAULT_DEPTH_BINS
     rig = CR.default_rig()
-    d = lambda a: torch.from_numpy(a).to(dev)                   # noqa: E731
     p = CR.build_projection_table(rig, Hc, Wc, RANGE, S, S)
     t = CR.build_lift_table(rig, Hc, Wc, RANGE, S, S)
-    proj = engine.CameraTable(p.P, p.ncols, d(p.row_ptr), d(p.col), d(p.w), d(p.t_row_ptr), d(p.t_col), d(p.t_w))
-    lift_tab = engine.CameraLiftTable(t.P, t.ncols, t.D, d(t.row_ptr), d(t.col2), d(t.w), d(t.t_row_ptr), d(t.t_cell), d(t.t_bin), d(t.t_w))
+    proj, lift_tab = engine.CameraTable.from_host(p, dev), engine.CameraLiftTable.from_host(t, dev)
     fus = fusion.FlexibleBEVFusion(use_camera=True, use_lidar=False, use_radar=False, bev_h=S, bev_w=S, pc_range=list(RANGE),
                                    camera_view_transform="frustum").to(dev)
     calib = (torch.from_numpy(CR.calib_matrices(jittered_rigs(B))).to(dev), (900, 1600))

@@ -148,6 +148,11 @@ SIGNATURES = {
     "bevf_points_affine_filter_pad_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.POINTER(C.c_float), C.c_void_p]),
     "bevf_points_affine_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_int] * 5 + [C.c_void_p]),
     "bevf_boxes_affine_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
+    # ---- points in boxes, GT-paste ----
+    "bevf_points_in_boxes_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    "bevf_paste_accept_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 6 + [C.c_void_p]),
+    "bevf_paste_points_work_ints": (C.c_size_t, [C.c_int] * 2),
+    "bevf_paste_points_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 7 + [C.c_void_p]),
     # ---- bf16 storage path ----
     "bevf_split_weights_f32x3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bevf_conv2d_nhwc_f32x3": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
@@ -1243,6 +1248,63 @@ def boxes_affine(boxes, labels, velocities, mat, scale, B: int, M: int, ncol: in
     _need("boxes_affine", boxes=(boxes, B * M * ncol), labels=(labels, B * M), velocities=(velocities, B * M * 2), mat=(mat, B * 12),
           scale=(scale, B))
     _call("bevf_boxes_affine_f32", _pc(boxes), _pc(labels, torch.int64), _pc(velocities), _pc(mat), _pc(scale), B, M, ncol)
+
+
+# ---- points in boxes, GT-paste (csrc/gt_paste.hip) ----------------------------------------------------------------
+
+def _ncol(what: str, ncol: int) -> None:
+    if ncol not in (7, 9):
+        raise BevfError(f"{what}: boxes have 7 or 9 columns, got {ncol}")
+
+
+def points_in_boxes(points, n_in, boxes, box_mask, idx, B: int, N: int, Cc: int, M: int, ncol: int) -> None:
+    """idx [B][N] int32 = the lowest box of boxes [B][M][ncol] that contains point i of points [B][N][C], or -1; n_in [B] int32 valid
+    rows (or None), box_mask [B][M] int32 (or None): rows < 0 are ignored (bevf_points_in_boxes_f32)."""
+    _ncol("points_in_boxes", ncol)
+    _need("points_in_boxes", points=(points, B * N * Cc), n_in=(n_in, B), boxes=(boxes, B * M * ncol), box_mask=(box_mask, B * M),
+          idx=(idx, B * N))
+    i32 = torch.int32
+    _call("bevf_points_in_boxes_f32", _pc(points), _pc(n_in, i32), _pc(boxes), _pc(box_mask, i32), _pc(idx, i32), B, N, Cc, M, ncol)
+
+
+def paste_accept(gt_boxes, gt_labels, gt_velocities, bank_boxes, bank_labels, obj_ptr, cand, accepted, prefix, out_boxes, out_labels,
+                 out_velocities, B: int, M: int, ncol: int, K: int, bank_ncol: int, Kc: int) -> None:
+    """The greedy accept step and the new GT rows (bevf_paste_accept_f32): cand / accepted [B][Kc] int32, prefix [B][Kc + 1] int32,
+    out_* with M + Kc rows per frame; labels int64."""
+    _ncol("paste_accept", ncol)
+    _ncol("paste_accept", bank_ncol)
+    if not 0 < Kc <= 64 or K <= 0:
+        raise BevfError(f"paste_accept: needs 0 < Kc <= 64 candidates per frame and a bank that holds objects, got Kc = {Kc}, K = {K}")
+    if (gt_velocities is None) != (out_velocities is None):
+        raise BevfError("paste_accept: velocities go in and come out together")
+    R = M + Kc
+    _need("paste_accept", gt_boxes=(gt_boxes, B * M * ncol), gt_labels=(gt_labels, B * M), gt_velocities=(gt_velocities, B * M * 2),
+          bank_boxes=(bank_boxes, K * bank_ncol), bank_labels=(bank_labels, K), obj_ptr=(obj_ptr, K + 1), cand=(cand, B * Kc),
+          accepted=(accepted, B * Kc), prefix=(prefix, B * (Kc + 1)), out_boxes=(out_boxes, B * R * ncol), out_labels=(out_labels, B * R),
+          out_velocities=(out_velocities, B * R * 2))
+    i32, i64 = torch.int32, torch.int64
+    _call("bevf_paste_accept_f32", _pc(gt_boxes), _pc(gt_labels, i64), _pc(gt_velocities), _pc(bank_boxes), _pc(bank_labels, i64),
+          _pc(obj_ptr, i32), _pc(cand, i32), _pc(accepted, i32), _pc(prefix, i32), _pc(out_boxes), _pc(out_labels, i64),
+          _pc(out_velocities), B, M, ncol, K, bank_ncol, Kc)
+
+
+def paste_points_work_ints(B: int, N: int) -> int:
+    return int(lib().bevf_paste_points_work_ints(B, N))
+
+
+def paste_points(points, n_in, bank_points, obj_ptr, bank_boxes, cand, accepted, prefix, out, count, work, B: int, N: int, Cc: int,
+                 K: int, bank_ncol: int, Kc: int, capacity: int) -> None:
+    """The remove and append steps (bevf_paste_points_f32): out [B][capacity][C], count [B] int32; bank_points [P][C] with P =
+    the bank's point total (the caller holds obj_ptr[K] <= P)."""
+    _ncol("paste_points", bank_ncol)
+    if not 0 < Kc <= 64 or K <= 0 or capacity <= 0:
+        raise BevfError(f"paste_points: needs 0 < Kc <= 64, K > 0 and capacity > 0, got Kc = {Kc}, K = {K}, capacity = {capacity}")
+    _need("paste_points", points=(points, B * N * Cc), n_in=(n_in, B), bank_points=(bank_points, Cc), obj_ptr=(obj_ptr, K + 1),
+          bank_boxes=(bank_boxes, K * bank_ncol), cand=(cand, B * Kc), accepted=(accepted, B * Kc), prefix=(prefix, B * (Kc + 1)),
+          out=(out, B * capacity * Cc), count=(count, B), work=(work, paste_points_work_ints(B, N)))
+    i32 = torch.int32
+    _call("bevf_paste_points_f32", _pc(points), _pc(n_in, i32), _pc(bank_points), _pc(obj_ptr, i32), _pc(bank_boxes), _pc(cand, i32),
+          _pc(accepted, i32), _pc(prefix, i32), _pc(out), _pc(count, i32), _pc(work, i32), B, N, Cc, K, bank_ncol, Kc, capacity)
 
 
 def csr_gather(row_ptr, col, w, nrows: int, ncols: int, x, x_bs: int, x_cs: int, y, y_bs: int, y_cs: int, B: int, C: int) -> None:

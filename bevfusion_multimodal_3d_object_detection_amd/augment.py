@@ -17,7 +17,8 @@ This module reads that section and applies the BEVFusion-style pair -- one world
   image is bit-equal to `preprocess.preprocess_camera_images`.
 
 Random numbers are drawn on the host from a `numpy.random.Generator` (a few dozen scalars per step); the radar noise is `torch.randn`
-on the device.  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' and 'frustum' camera branches.  No
+on the device.  `augment_batch(..., paste=, bank=)` runs the GT-paste of `gt_paste.py` in front of the world
+transform.  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' and 'frustum' camera branches.  No
 CPU fallback.
 """
 from __future__ import annotations
@@ -459,14 +460,30 @@ def augment_batch(frames_u8: Optional[torch.Tensor], lidar: Optional[torch.Tenso
                   gt_velocities: Optional[torch.Tensor], params: AugmentParams, settings: AugmentSettings, base_calib=None,
                   max_points: int = 35000, pc_range: Sequence[float] = PC_RANGE, lidar_vel_ch: Optional[Sequence[int]] = None,
                   radar_vel_ch: Optional[Sequence[int]] = None, generator: Optional[torch.Generator] = None,
-                  image_size: Optional[Tuple[int, int]] = None) -> Dict:
+                  image_size: Optional[Tuple[int, int]] = None, *, paste=None, bank=None) -> Dict:
     """One augmented training batch, everything on the device:
 
     frames_u8 (B, ncam, Hs, Ws, 3) uint8; lidar (B, N, C) fp32 with lidar_counts (B,) valid points per frame (None = N); radar: a
     sequence of (B, P, C) fp32 tensors (transformed in place on copies); gt_boxes (B, M, 7|9), gt_labels (B, M) with -1 padding,
     gt_velocities (B, M, 2) or None.  Any input may be None.  Returns camera_imgs (B, ncam, 3, Ho, Wo), lidar_points (B, max_points,
     C), lidar_count, radar_points, gt_boxes, gt_labels, gt_velocities, camera_calib (None without base_calib): the inputs of
-    `model(...)` and `prepare_centernet_targets`."""
+    `model(...)` and `prepare_centernet_targets`.
+
+    paste= (a `gt_paste.PasteParams` with at least one candidate per frame) and bank= (a `gt_paste.ObjectBank`), given together, run
+    the GT-paste of `gt_paste.paste` first, before the world transform (ObjectSample, then GlobalRotScaleTrans): lidar, gt_boxes and
+    gt_labels are then required, the paste's outputs take their place (Kc more GT rows per frame), and the result gains
+    paste_accepted int32 (B, Kc).  With a camera branch the pasted objects are NOT drawn into the images, as in BEVFusion's own
+    recipe.  Without the two arguments the function takes exactly the path it takes without them."""
+    accepted = None
+    if (paste is None) != (bank is None):
+        raise L.BevfError("augment_batch: paste= and bank= go together")
+    if paste is not None and paste.Kc > 0:
+        if lidar is None or gt_boxes is None or gt_labels is None:
+            raise L.BevfError("augment_batch: paste= needs lidar, gt_boxes and gt_labels")
+        from . import gt_paste
+        pasted = gt_paste.paste(lidar, lidar_counts, gt_boxes, gt_labels, gt_velocities, bank, paste)
+        lidar, lidar_counts = pasted["lidar_points"], pasted["lidar_count"]
+        gt_boxes, gt_labels, gt_velocities, accepted = pasted["gt_boxes"], pasted["gt_labels"], pasted["gt_velocities"], pasted["accepted"]
     out: Dict = dict(camera_imgs=None, lidar_points=None, lidar_count=None, radar_points=None, gt_boxes=None, gt_labels=gt_labels,
                      gt_velocities=None, camera_calib=None)
     if frames_u8 is not None:
@@ -483,4 +500,6 @@ def augment_batch(frames_u8: Optional[torch.Tensor], lidar: Optional[torch.Tenso
         out["gt_boxes"], out["gt_velocities"] = transform_boxes(gt_boxes, gt_labels, gt_velocities, params, params.scale)
     if base_calib is not None:
         out["camera_calib"] = augmented_calib(base_calib, params, image_size)
+    if accepted is not None:
+        out["paste_accepted"] = accepted
     return out

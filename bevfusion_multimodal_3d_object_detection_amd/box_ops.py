@@ -5,6 +5,8 @@ with extent l along the heading (cos yaw, sin yaw) and w across it; its z-extent
 
 * `boxes_iou_bev(a, b)` / `boxes_iou3d(a, b)` -- pairwise IoU, (N,7) x (M,7) -> (N,M), or batched (B,N,7) x (B,M,7) -> (B,N,M)
   with optional per-frame counts (entries past a count are 0).
+* `points_in_boxes(points, boxes, point_counts, box_mask)` -- per point the lowest index of a box that contains it, or -1
+  (csrc/gt_paste.hip; the crop of `gt_paste.ObjectBank.from_frames`).
 * `nms_rotated(boxes, scores, iou_thresh, ...)` / `nms_circle(boxes, scores, radius, ...)` -- greedy NMS of one frame, kept
   indices in descending score order (ties: the lower index first).
 * `decode_settings(config, section)` -- the reference YAML's `<section>.post_processing` keys as keyword arguments of
@@ -65,6 +67,38 @@ def boxes_iou_bev(a: torch.Tensor, b: torch.Tensor, count_a=None, count_b=None) 
 def boxes_iou3d(a: torch.Tensor, b: torch.Tensor, count_a=None, count_b=None) -> torch.Tensor:
     """3-D IoU: BEV intersection area times the z-overlap / (vol_a + vol_b - intersection volume); h <= 0 gives 0 as well."""
     return _iou(a, b, "3d", count_a, count_b)
+
+
+def points_in_boxes(points: torch.Tensor, boxes: torch.Tensor, point_counts=None, box_mask=None) -> torch.Tensor:
+    """points (B,N,C>=3) fp32, boxes (B,M,7|9) fp32 -> int32 (B,N): the lowest index j of a box of the same frame that contains the
+    point, or -1 for none (csrc/gt_paste.hip).  Rows at or past `point_counts[b]` give -1.  `box_mask` (B,M): integer labels (rows < 0
+    are ignored) or bool (false rows are ignored).  With d = p - centre rotated by -yaw into (lx, ly), a point is inside iff
+    |lx| <= l/2, |ly| <= w/2, |dz| <= h/2 and w, l, h > 0; a NaN anywhere gives not inside.  Unbatched (N,C) / (M,7|9) inputs give
+    (N,)."""
+    E.require_cuda(points, boxes, box_mask)
+    if points.dim() != boxes.dim() or points.dim() not in (2, 3) or points.shape[-1] < 3 or boxes.shape[-1] not in (7, 9):
+        raise ValueError(f"points must be (N,C>=3) and boxes (M,7|9), or (B,N,C) and (B,M,7|9); got {tuple(points.shape)} and "
+                         f"{tuple(boxes.shape)}")
+    if points.dtype != torch.float32 or boxes.dtype != torch.float32:
+        raise ValueError(f"points and boxes must be fp32, got {points.dtype} and {boxes.dtype}")
+    single = points.dim() == 2
+    if single:
+        points, boxes = points[None], boxes[None]
+        box_mask = None if box_mask is None else box_mask[None]
+        point_counts = None if point_counts is None else torch.as_tensor(point_counts).reshape(1)
+    if points.shape[0] != boxes.shape[0]:
+        raise ValueError(f"batch sizes differ: {points.shape[0]} and {boxes.shape[0]}")
+    B, N, Cc = points.shape
+    M, ncol = boxes.shape[1], boxes.shape[2]
+    mask = None
+    if box_mask is not None:
+        if tuple(box_mask.shape) != (B, M) or box_mask.dtype.is_floating_point:
+            raise ValueError(f"box_mask must be (B,M) = {(B, M)} integer labels or bool, got {tuple(box_mask.shape)} {box_mask.dtype}")
+        mask = (box_mask.to(torch.int32) - 1 if box_mask.dtype == torch.bool else box_mask.clamp(min=-1).to(torch.int32)).contiguous()
+    out = torch.full((B, N), -1, dtype=torch.int32, device=points.device)
+    if B > 0 and N > 0 and M > 0:
+        L.points_in_boxes(points.contiguous(), _counts(point_counts, B, points.device), boxes.contiguous(), mask, out, B, N, Cc, M, ncol)
+    return out[0] if single else out
 
 
 def _nms(boxes: torch.Tensor, scores: torch.Tensor, mode: str, thresh: float, labels, pre_max, post_max) -> torch.Tensor:

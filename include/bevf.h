@@ -835,6 +835,42 @@ int bevf_points_affine_f32(float* points, const float* mat12, const float* noise
 int bevf_boxes_affine_f32(float* boxes, const int64_t* labels, float* velocities, const float* mat12, const float* scale, int B,
                           int M, int ncol, void* stream);
 
+/* ==========================================================================================
+ * Points in boxes and GT-paste (object-sample) augmentation (csrc/gt_paste.hip).
+ * Boxes are [x, y, z, w, l, h, yaw(, vx, vy)]: l along the heading (cos yaw, sin yaw), w across it, z-extent [z - h/2, z + h/2].
+ * ========================================================================================== */
+
+/* idx [B][N] = the lowest j such that box j of frame b contains point i, or -1.  points [B][N][C] (C >= 3; n_in [B] valid rows each,
+ * NULL = N; rows at or past n_in give -1), boxes [B][M][ncol] (ncol 7 or 9), box_mask [B][M] or NULL: rows < 0 are ignored.
+ * Inside iff, with d = p - centre, lx = fmaf(dy, sin, dx * cos), ly = fmaf(dy, cos, -(dx * sin)) (sincosf of yaw):
+ * |lx| <= l/2, |ly| <= w/2, |dz| <= h/2 and w, l, h > 0; a NaN anywhere gives not inside.  Any M: the boxes pass through LDS in
+ * chunks of 64.                                                                                                                  */
+int bevf_points_in_boxes_f32(const float* points, const int32_t* n_in, const float* boxes, const int32_t* box_mask, int32_t* idx,
+                             int B, int N, int C, int M, int ncol, void* stream);
+/* The accept step of the paste, one workgroup per frame.  cand [B][Kc] (Kc <= 64) indexes the bank (bank_boxes [K][bank_ncol],
+ * bank_labels [K], obj_ptr [K + 1] = the objects' point ranges); an entry < 0 or >= K is no candidate.  Candidates are taken in order
+ * k = 0 .. Kc - 1; candidate k is accepted iff it is one, its BEV rectangle collides with no GT row of label >= 0 (gt_boxes
+ * [B][M][ncol], gt_labels [B][M]) and with no ACCEPTED candidate k' < k (a rejected candidate blocks nothing).  Collision = the
+ * separating-axis test on the four edge directions, touching counts, z ignored; a rectangle with w <= 0, l <= 0 or a NaN / infinity
+ * among (x, y, w, l, yaw) collides with nothing.  Writes accepted [B][Kc] (0 / 1), prefix [B][Kc + 1] = the exclusive prefix of the
+ * accepted objects' point counts with their total last, and the new GT rows: out_boxes [B][M + Kc][ncol], out_labels [B][M + Kc],
+ * out_velocities [B][M + Kc][2] (NULL together with gt_velocities): rows < M are copies, row M + k is candidate k's box (columns 7-8
+ * zeros when the bank has none), label and velocity (the bank's columns 7-8, else zeros) if accepted, else label -1 and zeros.      */
+int bevf_paste_accept_f32(const float* gt_boxes, const int64_t* gt_labels, const float* gt_velocities, const float* bank_boxes,
+                          const int64_t* bank_labels, const int32_t* obj_ptr, const int32_t* cand, int32_t* accepted, int32_t* prefix,
+                          float* out_boxes, int64_t* out_labels, float* out_velocities, int B, int M, int ncol, int K, int bank_ncol,
+                          int Kc, void* stream);
+/* The remove and append steps.  Points of points [B][N][C] (n_in as above) inside the 3-D extent of an accepted candidate's box (the
+ * test of bevf_points_in_boxes_f32) are dropped, the survivors keep their order and their bits; behind them come the accepted objects'
+ * points in candidate order and bank order (bank_points [P][C]: xyz relative to the box centre, xyz = relative + centre with one fp32
+ * addition per coordinate, other channels copied); then zeros.  out [B][capacity][C] = the first `capacity` rows of that stream,
+ * count [B] = min(survivors + appended, capacity).  accepted / prefix: from bevf_paste_accept_f32.  work:
+ * bevf_paste_points_work_ints(B, N) int32.  No float atomics; every element of out and count is written.                         */
+size_t bevf_paste_points_work_ints(int B, int N);
+int bevf_paste_points_f32(const float* points, const int32_t* n_in, const float* bank_points, const int32_t* obj_ptr,
+                          const float* bank_boxes, const int32_t* cand, const int32_t* accepted, const int32_t* prefix, float* out,
+                          int32_t* count, int32_t* work, int B, int N, int C, int K, int bank_ncol, int Kc, int capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

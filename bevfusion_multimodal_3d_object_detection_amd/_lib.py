@@ -135,6 +135,22 @@ SIGNATURES = {
     "bevf_pillar_moments_f32": (C.c_int, [C.POINTER(PillarGeom)] + [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_float] +
                                 [C.c_void_p] * 10),
     "bevf_pillar_pfn_backward_f32": (C.c_int, [C.POINTER(PillarGeom)] + [C.c_void_p] * 10 + [C.c_int] * 2 + [C.c_void_p] * 6),
+    # ---- sparse-voxel LiDAR encoder ----
+    "bevf_sparse_fill_index": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 3),
+    "bevf_sparse_down_work_bytes": (C.c_size_t, [C.c_int] * 4),
+    "bevf_sparse_down": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 5),
+    "bevf_sparse_table": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 10 + [C.c_void_p] * 2),
+    "bevf_sparse_vfe_mean_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "bevf_sparse_conv_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "bevf_sparse_conv_row_tile": (C.c_int, []),
+    "bevf_sparse_wgrad_work_floats": (C.c_size_t, [C.c_int] * 2),
+    "bevf_sparse_conv_wgrad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 3),
+    "bevf_sparse_canvas_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "bevf_sparse_canvas_bwd_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 2),
+    "bevf_sparse_bn_work_bytes": (C.c_size_t, [C.c_int]),
+    "bevf_sparse_bn_stats_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p] * 8),
+    "bevf_sparse_bn_apply_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p] * 6),
+    "bevf_sparse_bn_backward_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
     # ---- input pipeline ----
     "bevf_resize_normalize_u8": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2 +
                                  [C.c_int] + [C.POINTER(C.c_float)] * 2 + [C.c_void_p]),
@@ -862,6 +878,112 @@ def pillar_backward(g: PillarGeom, dcanvas, argmax, w, bias, scale, shift, mean,
     _call("bevf_pillar_pfn_backward_f32", C.byref(g), _pc(dcanvas), _pc(argmax, torch.uint8), _pc(w), _pc(bias), _pc(scale),
           _pc(shift), _pc(mean), _pc(invstd), _pc(gamma), _pc(moments, torch.float64), Cout,
           int(frozen), _p(dw), _p(db), _p(dgamma), _p(dbeta), _p(work, torch.uint8))
+
+
+# ---- sparse-voxel LiDAR encoder (csrc/sparse_index.hip, sparse_conv.hip, sparse_rows.hip) ---------------------------------
+# A level is `cap` row slots per frame, active while slot < count[b]; count stays on the device.
+
+I32 = torch.int32
+
+
+def _sp_need(what: str, **bufs) -> None:
+    for name, (t, n) in bufs.items():
+        if t is not None and t.numel() < n:
+            raise BevfError(f"{what}: {name} holds {t.numel()} elements, needs {n}")
+
+
+def sparse_fill_index(coords, count, B: int, cap: int, D: int, H: int, W: int, index, cell) -> None:
+    if B * D * H * W >= 1 << 31:
+        raise BevfError(f"sparse encoder: B * cells = {B * D * H * W} does not fit int32 (an index volume per level; no hash table)")
+    _sp_need("sparse_fill_index", coords=(coords, B * cap * 3), count=(count, B), index=(index, B * D * H * W), cell=(cell, B * cap))
+    _call("bevf_sparse_fill_index", _pc(coords, torch.int64), _pc(count, I32), B, cap, D, H, W, _pc(index, I32), _pc(cell, I32))
+
+
+def sparse_down_work_bytes(B: int, D: int, H: int, W: int) -> int:
+    return int(lib().bevf_sparse_down_work_bytes(B, D, H, W))
+
+
+def sparse_down(index_in, B: int, D: int, H: int, W: int, cap_out: int, index_out, cell_out, count_out, work) -> None:
+    co = (D // 2) * (H // 2) * (W // 2)
+    _sp_need("sparse_down", index_in=(index_in, B * D * H * W), index_out=(index_out, B * co), cell_out=(cell_out, B * cap_out),
+             count_out=(count_out, B), work=(work, sparse_down_work_bytes(B, D, H, W)))
+    _call("bevf_sparse_down", _pc(index_in, I32), B, D, H, W, cap_out, _pc(index_out, I32), _pc(cell_out, I32), _pc(count_out, I32),
+          _pc(work, torch.uint8))
+
+
+def sparse_table(index, cell, count, B: int, cap: int, in_dims, row_dims, stride: int, transposed: bool, table) -> None:
+    (Di, Hi, Wi), (Dr, Hr, Wr) = in_dims, row_dims
+    _sp_need("sparse_table", index=(index, B * Di * Hi * Wi), cell=(cell, B * cap), count=(count, B), table=(table, B * cap * 27))
+    _call("bevf_sparse_table", _pc(index, I32), _pc(cell, I32), _pc(count, I32), B, cap, Di, Hi, Wi, Dr, Hr, Wr, stride, int(transposed),
+          _pc(table, I32))
+
+
+def sparse_vfe_mean(feats, npts, nvox, B: int, Nv: int, P: int, Cc: int, Cpad: int, rows) -> None:
+    _sp_need("sparse_vfe_mean", feats=(feats, B * Nv * P * Cc), npts=(npts, B * Nv), nvox=(nvox, B), rows=(rows, B * Nv * Cpad))
+    _call("bevf_sparse_vfe_mean_f32", _pc(feats), _pc(npts, I32), _pc(nvox, I32), B, Nv, P, Cc, Cpad, _pc(rows))
+
+
+def sparse_conv_row_tile() -> int:
+    return int(lib().bevf_sparse_conv_row_tile())
+
+
+def sparse_conv(x, table, count, w, scale, shift, B: int, cap: int, rows_in: int, Cin: int, Cout: int, relu: bool, y) -> None:
+    """y [B * cap][Cout] = gather-GEMM of x [rows_in][Cin] through table [B * cap][27] with w [27][Cin][Cout] (+ scale / shift / ReLU)."""
+    _sp_need("sparse_conv", x=(x, rows_in * Cin), table=(table, B * cap * 27), count=(count, B), w=(w, 27 * Cin * Cout),
+             scale=(scale, Cout), shift=(shift, Cout), y=(y, B * cap * Cout))
+    _call("bevf_sparse_conv_f32", _pc(x), _pc(table, I32), _pc(count, I32), _pc(w), _pc(scale), _pc(shift), B, cap, rows_in, Cin, Cout,
+          int(relu), _pc(y))
+
+
+def sparse_wgrad_work_floats(Cin: int, Cout: int) -> int:
+    return int(lib().bevf_sparse_wgrad_work_floats(Cin, Cout))
+
+
+def sparse_conv_wgrad(x, dy, table, count, B: int, cap: int, rows_in: int, Cin: int, Cout: int, cin_real: int, dw, work) -> None:
+    _sp_need("sparse_conv_wgrad", x=(x, rows_in * Cin), dy=(dy, B * cap * Cout), table=(table, B * cap * 27), count=(count, B),
+             dw=(dw, Cout * cin_real * 27), work=(work, sparse_wgrad_work_floats(Cin, Cout)))
+    _call("bevf_sparse_conv_wgrad_f32", _pc(x), _pc(dy), _pc(table, I32), _pc(count, I32), B, cap, rows_in, Cin, Cout, cin_real, _pc(dw),
+          _pc(work))
+
+
+def sparse_canvas(rows, cell, count, B: int, cap: int, D: int, H: int, W: int, Cc: int, canvas) -> None:
+    """canvas [B][H][W][D * C] (fp32 or bf16) from the level's rows; inactive cells exactly 0."""
+    _sp_need("sparse_canvas", rows=(rows, B * cap * Cc), cell=(cell, B * cap), count=(count, B), canvas=(canvas, B * D * H * W * Cc))
+    bf = canvas.dtype == BF16
+    _call("bevf_sparse_canvas_f32", _pc(rows), _pc(cell, I32), _pc(count, I32), B, cap, D, H, W, Cc,
+          _pc(canvas, canvas.dtype if bf else torch.float32), int(bf))
+
+
+def sparse_canvas_bwd(dcanvas, cell, count, B: int, cap: int, D: int, H: int, W: int, Cc: int, drows) -> None:
+    _sp_need("sparse_canvas_bwd", dcanvas=(dcanvas, B * D * H * W * Cc), cell=(cell, B * cap), count=(count, B), drows=(drows, B * cap * Cc))
+    _call("bevf_sparse_canvas_bwd_f32", _pc(dcanvas), _pc(cell, I32), _pc(count, I32), B, cap, D, H, W, Cc, _pc(drows))
+
+
+def sparse_bn_work_bytes(Cc: int) -> int:
+    return int(lib().bevf_sparse_bn_work_bytes(Cc))
+
+
+def sparse_bn_stats(y, count, B: int, cap: int, Cc: int, eps: float, momentum: float, running_mean, running_var, nbt, mean, invstd,
+                    nrows, work) -> None:
+    _sp_need("sparse_bn_stats", y=(y, B * cap * Cc), count=(count, B), running_mean=(running_mean, Cc), running_var=(running_var, Cc),
+             nbt=(nbt, 1), mean=(mean, Cc), invstd=(invstd, Cc), nrows=(nrows, 1), work=(work, sparse_bn_work_bytes(Cc)))
+    _call("bevf_sparse_bn_stats_f32", _pc(y), _pc(count, I32), B, cap, Cc, float(eps), float(momentum), _pc(running_mean),
+          _pc(running_var), _pc(nbt, torch.int64), _pc(mean), _pc(invstd), _pc(nrows, I32), _pc(work, torch.uint8))
+
+
+def sparse_bn_apply(y, count, B: int, cap: int, Cc: int, mean, invstd, gamma, beta, a) -> None:
+    _sp_need("sparse_bn_apply", y=(y, B * cap * Cc), count=(count, B), mean=(mean, Cc), invstd=(invstd, Cc), gamma=(gamma, Cc),
+             beta=(beta, Cc), a=(a, B * cap * Cc))
+    _call("bevf_sparse_bn_apply_f32", _pc(y), _pc(count, I32), B, cap, Cc, _pc(mean), _pc(invstd), _pc(gamma), _pc(beta), _pc(a))
+
+
+def sparse_bn_backward(y, da, count, B: int, cap: int, Cc: int, mean, invstd, gamma, beta, frozen: bool, dy, dgamma, dbeta, sums,
+                       work) -> None:
+    _sp_need("sparse_bn_backward", y=(y, B * cap * Cc), da=(da, B * cap * Cc), count=(count, B), mean=(mean, Cc), invstd=(invstd, Cc),
+             gamma=(gamma, Cc), beta=(beta, Cc), dy=(dy, B * cap * Cc), dgamma=(dgamma, Cc), dbeta=(dbeta, Cc), sums=(sums, 2 * Cc),
+             work=(work, sparse_bn_work_bytes(Cc)))
+    _call("bevf_sparse_bn_backward_f32", _pc(y), _pc(da), _pc(count, I32), B, cap, Cc, _pc(mean), _pc(invstd), _pc(gamma), _pc(beta),
+          int(frozen), _pc(dy), _pc(dgamma), _pc(dbeta), _pc(sums), _pc(work, torch.uint8))
 
 
 # ---- training step --------------------------------------------------------------------------------------------------------

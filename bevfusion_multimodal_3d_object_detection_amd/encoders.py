@@ -351,17 +351,20 @@ class VFELayer(nn.Module):
 
 
 PILLAR_TYPES = ("pointpillars", "pillars")
+SPARSE_TYPES = ("sparsevoxel", "sparse", "second")
 DEFAULT_PC_RANGE = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0)
 
 
 def lidar_encoder_kind(lidar_encoder_type: Optional[str] = None, config: Optional[Dict] = None) -> str:
     """'pillars' when the keyword -- or, when it is None, `model.lidar_encoder.type` of the config -- names PointPillars
-    (case-insensitive, 'PointPillars' or 'pillars'); 'pointnet' for anything else or nothing (incl. 'PointNet' / 'VoxelNet',
-    the values configs/base.yaml documents but the reference never reads)."""
+    (case-insensitive, 'PointPillars' or 'pillars'); 'sparse' when it names the sparse-voxel encoder ('SparseVoxel', 'sparse' or
+    'SECOND'); 'pointnet' for anything else or nothing (incl. 'PointNet' / 'VoxelNet', the values configs/base.yaml documents but
+    the reference never reads)."""
     t = lidar_encoder_type
     if t is None and config is not None:
         t = (config.get("model", {}).get("lidar_encoder", {}) or {}).get("type")
-    return "pillars" if isinstance(t, str) and t.strip().lower() in PILLAR_TYPES else "pointnet"
+    t = t.strip().lower() if isinstance(t, str) else None
+    return "pillars" if t in PILLAR_TYPES else ("sparse" if t in SPARSE_TYPES else "pointnet")
 
 
 def pillar_grid(point_cloud_range, bev_h: int, bev_w: int) -> Tuple[float, float, float, float, Tuple[float, float, float]]:
@@ -439,6 +442,121 @@ class PillarLiDAREncoder(nn.Module):
         return E.to_nchw(c, c.shape[0], self.pfn_channels, self.bev_h, self.bev_w)
 
 
+def sparse_grid(point_cloud_range, bev_h: int, bev_w: int, z_voxels: int):
+    """Level-0 grid of the sparse-voxel encoder: ((Dz, 4 bev_h, 4 bev_w), voxel_size) -- the xy voxel is pillar_grid's fp32 cell
+    divided by 4 (exact), the z voxel the fp32 z range divided by Dz."""
+    _, _, vx, vy, _ = pillar_grid(point_cloud_range, bev_h, bev_w)
+    r = np.asarray(point_cloud_range, dtype=np.float32)
+    vz = np.float32(r[5] - r[2]) / np.float32(z_voxels)
+    return (int(z_voxels), 4 * int(bev_h), 4 * int(bev_w)), (float(np.float32(vx) / np.float32(4)), float(np.float32(vy) / np.float32(4)), float(vz))
+
+
+class SparseConvBlock(nn.Module):
+    """Parameters of one sparse layer: Conv3d(cin, cout, 3, bias=False) + BatchNorm1d(cout) (+ ReLU) as plain torch modules, so the
+    state dict is torch-native and a dense restatement loads the same one.  stride 1 = submanifold, stride 2 = strided (pad 1)."""
+
+    def __init__(self, cin: int, cout: int, stride: int):
+        super().__init__()
+        self.conv = nn.Conv3d(cin, cout, 3, stride=stride, padding=1, bias=False)
+        self.bn = nn.BatchNorm1d(cout)
+        self.stride = stride
+
+
+SPARSE_LAYERS = ("conv_in", "down1", "subm1", "down2", "subm2")
+
+
+class SparseLiDAREncoder(nn.Module):
+    """Sparse-voxel (VoxelNet / SECOND style) LiDAR encoder on the BEV grid (opt-in: `model.lidar_encoder.type: 'SparseVoxel'`).
+    Not in the reference, whose voxel path never runs; spconv's semantics (include/bevf.h, sparse-voxel encoder):
+    points (B,N,C) -> voxelize on the (z_voxels, 4 bev_h, 4 bev_w) grid -> mean of each voxel's kept points -> conv_in (submanifold
+    3x3x3, C -> c0) -> down1 (stride 2, c0 -> c1) -> subm1 -> down2 (stride 2, c1 -> c2) -> subm2, each + BatchNorm over the active
+    voxels + ReLU, computed over the occupied voxels only -> z folded into channels -> canvas (B, c2 z_voxels / 4, bev_h, bev_w),
+    channel z * c2 + c, exactly 0 at inactive cells.  Consumed by the fusion's lidar_bev exactly like the pillar canvas."""
+
+    is_sparse = True
+
+    def __init__(self, input_channels: Optional[int] = None, channels=None, z_voxels: Optional[int] = None,
+                 bev_h: Optional[int] = None, bev_w: Optional[int] = None, point_cloud_range=None,
+                 max_points_per_voxel: Optional[int] = None, max_voxels: Optional[int] = None, config: Optional[Dict] = None,
+                 config_path: Optional[str] = None):
+        super().__init__()
+        config = _cfg(config, config_path)
+        if config is not None:
+            c, d = config.get("model", {}).get("lidar_encoder", {}) or {}, config.get("dataset", {})
+            input_channels = c.get("input_channels", 5) if input_channels is None else input_channels
+            channels = c.get("channels", (32, 64, 128)) if channels is None else channels
+            z_voxels = c.get("z_voxels", 8) if z_voxels is None else z_voxels
+            max_points_per_voxel = c.get("max_points_per_voxel", 8) if max_points_per_voxel is None else max_points_per_voxel
+            max_voxels = c.get("max_voxels", 40000) if max_voxels is None else max_voxels
+            point_cloud_range = d.get("point_cloud_range", DEFAULT_PC_RANGE) if point_cloud_range is None else point_cloud_range
+            bev_h = d.get("bev_h", 50) if bev_h is None else bev_h
+            bev_w = d.get("bev_w", 50) if bev_w is None else bev_w
+        self.input_channels = 4 if input_channels is None else int(input_channels)
+        self.channels = tuple(int(v) for v in ((32, 64, 128) if channels is None else channels))
+        self.z_voxels = 8 if z_voxels is None else int(z_voxels)
+        self.max_points = 8 if max_points_per_voxel is None else int(max_points_per_voxel)
+        self.max_voxels = 40000 if max_voxels is None else int(max_voxels)
+        self.pc_range = tuple(float(v) for v in (DEFAULT_PC_RANGE if point_cloud_range is None else point_cloud_range))
+        self.bev_h = 50 if bev_h is None else int(bev_h)
+        self.bev_w = 50 if bev_w is None else int(bev_w)
+        if not 3 <= self.input_channels <= 8:
+            raise L.BevfError(f"SparseLiDAREncoder: input_channels={self.input_channels}: a point carries x, y, z and at most 8 "
+                              "channels (zero-padded to the 32-channel K granule of the first layer), so 3 <= C <= 8")
+        if len(self.channels) != 3 or any(v % 32 or not 0 < v <= 128 for v in self.channels):
+            raise L.BevfError(f"SparseLiDAREncoder: channels={self.channels} must be three multiples of 32 up to 128")
+        if self.z_voxels <= 0 or self.z_voxels % 4:
+            raise L.BevfError(f"SparseLiDAREncoder: z_voxels={self.z_voxels} must be a positive multiple of 4 (two stride-2 layers)")
+        if self.max_points <= 0 or self.max_voxels <= 0 or self.bev_h <= 0 or self.bev_w <= 0:
+            raise L.BevfError("SparseLiDAREncoder: need max_points_per_voxel > 0, max_voxels > 0 and a BEV grid")
+        c0, c1, c2 = self.channels
+        self.conv_in = SparseConvBlock(self.input_channels, c0, 1)
+        self.down1 = SparseConvBlock(c0, c1, 2)
+        self.subm1 = SparseConvBlock(c1, c1, 1)
+        self.down2 = SparseConvBlock(c1, c2, 2)
+        self.subm2 = SparseConvBlock(c2, c2, 1)
+        self.out_channels = c2 * self.z_voxels // 4
+        self._engine = None
+
+    def layers(self):
+        return [getattr(self, n) for n in SPARSE_LAYERS]
+
+    def grid(self):
+        """((Dz, 4 bev_h, 4 bev_w), voxel_size) of level 0."""
+        return sparse_grid(self.pc_range, self.bev_h, self.bev_w, self.z_voxels)
+
+    def level_dims(self):
+        """Grid (D, H, W) and per-frame row capacity of levels 0, 1, 2: capacity(0) = max_voxels, then the worst case
+        min(8 capacity(l - 1), cells(l)) -- nothing is ever truncated past voxelize's own cap."""
+        (D, H, W), _ = self.grid()
+        dims, caps = [(D, H, W)], [self.max_voxels]
+        for _ in range(2):
+            D, H, W = D // 2, H // 2, W // 2
+            dims.append((D, H, W))
+            caps.append(min(8 * caps[-1], D * H * W))
+        return dims, caps
+
+    def _eng(self) -> "E.SparseLiDAREngine":
+        if self._engine is None:
+            object.__setattr__(self, "_engine", E.SparseLiDAREngine(self))
+        return self._engine
+
+    def forward_nhwc(self, points: torch.Tensor) -> torch.Tensor:
+        """Internal fast path: the canvas as an NHWC view (B, bev_h, bev_w, out_channels) in the storage dtype."""
+        E.require_cuda(points)
+        return self._eng().run(points)
+
+    def forward(self, points: torch.Tensor) -> torch.Tensor:
+        if self.training and _training().wants_train_path(self):
+            E.require_cuda(points)
+            return _training().sparse_train_forward(self, points)
+        with torch.no_grad():
+            return self._forward_eval(points)
+
+    def _forward_eval(self, points: torch.Tensor) -> torch.Tensor:
+        c = self.forward_nhwc(points)
+        return E.to_nchw(c, c.shape[0], self.out_channels, self.bev_h, self.bev_w)
+
+
 class VoxelNetLiDAREncoder(nn.Module):
     """ref src/encoders.py:308-417.  Dead code in the reference (never imported by fusion.py) and its
     forward raises: vfe2 receives vfe1's 3-D output and cannot unpack 4 dims (ref :395-396 vs :438).
@@ -481,4 +599,5 @@ def print_encoder_specs():
     print("camera : ResNet-18 conv1..layer3 + 1x1 proj, (B,6,3,H,W) -> (B,6,512,H/16,W/16)")
     print("lidar  : PointNet shared MLP 64-128-256-512-1024 + max, (B,N,C) -> (B,1024)")
     print("         or (model.lidar_encoder.type: PointPillars) pillars on the BEV grid, decorated points -> PFN -> canvas")
+    print("         or (model.lidar_encoder.type: SparseVoxel) sparse 3x3x3 convolutions over the occupied voxels -> canvas")
     print("radar  : 5 x shared MLP 32-64-128-256 + max, concat -> Linear(1280,256), -> (B,256)")

@@ -114,7 +114,7 @@ def _check_eval(module: nn.Module) -> None:
                 f"{type(module).__name__} has a BatchNorm in train mode but was asked for the eval-mode kernels (BatchNorm "
                 "folded from running statistics) -- call .eval() first.  Train-mode BatchNorm, backward and optimiser run "
                 "through the training tapes (training.DetectorTape and its per-module tapes): the detector, ResNetCameraEncoder, "
-                "PointNetLiDAREncoder, PillarLiDAREncoder, RadarEncoder / MultiRadarEncoder, VFELayer, FlexibleBEVFusion and "
+                "PointNetLiDAREncoder, PillarLiDAREncoder, SparseLiDAREncoder, RadarEncoder / MultiRadarEncoder, VFELayer, FlexibleBEVFusion and "
                 "CenterNetHead reach them from forward() in train mode.")
 
 
@@ -461,6 +461,111 @@ class PillarEngine(_Engine):
         with _span("pillar_pfn", flops=0.0, nbytes=float(canvas.element_size()) * n):
             L.pillar_pfn(g, self.w, self.scale, self.shift, self.cout, canvas)
         return canvas[:n].view(B, m.bev_h, m.bev_w, self.cout)
+
+
+# ---- sparse-voxel LiDAR encoder ------------------------------------------------------------------------
+
+# layer -> (level of its rows, level its taps look into, stride)
+SPARSE_SPEC = dict(conv_in=(0, 0, 1), down1=(1, 0, 2), subm1=(1, 1, 1), down2=(2, 1, 2), subm2=(2, 2, 1))
+SPARSE_KPAD = 32             # the first layer's point channels are zero-padded to the gather-GEMM's K granule
+
+
+def sparse_pack_weight(conv: nn.Conv3d, transposed: bool = False) -> torch.Tensor:
+    """Conv3d weight [Cout][Cin][3][3][3] -> [27][Cin padded to 32][Cout] fp32, tap k = (kz * 3 + ky) * 3 + kx.  transposed: the
+    data gradient's [27][Cout][Cin]; a submanifold layer reuses its forward table there, so its taps are mirrored (k -> 26 - k)."""
+    w = conv.weight.detach().float()
+    cout, cin = w.shape[:2]
+    wp = w.permute(2, 3, 4, 1, 0).reshape(27, cin, cout)
+    if transposed:
+        wp = wp.transpose(1, 2)
+        if conv.stride[0] == 1:
+            wp = wp.flip(0)
+        return wp.contiguous().view(-1)
+    if cin % SPARSE_KPAD:
+        wp = torch.cat([wp, wp.new_zeros(27, SPARSE_KPAD - cin % SPARSE_KPAD, cout)], 1)
+    return wp.contiguous().view(-1)
+
+
+class SparseStructure:
+    """What one batch's geometry gives the sparse layers: per level l the grid dims[l], the per-frame row capacity caps[l], the
+    index volume, the rows' cells and the per-frame counts (device int32); per layer its neighbour table; x0, the mean-VFE rows
+    of level 0 [B * caps[0]][32].  grad=True adds the input-side tables of the two strided layers (their data gradient)."""
+
+    def __init__(self, enc: nn.Module, pts: torch.Tensor, alloc, grad: bool = False):
+        if pts.dim() != 3 or pts.shape[2] != enc.input_channels:
+            raise L.BevfError(f"SparseLiDAREncoder: points must be (B, N, {enc.input_channels}), got {tuple(pts.shape)}")
+        pts = pts.float().contiguous()
+        B, N, Cc = pts.shape
+        P = enc.max_points
+        self.B, self.P, self.C = B, P, Cc
+        self.dims, self.caps = enc.level_dims()
+        dims, caps = self.dims, self.caps
+        _, vsize = enc.grid()
+        I32 = torch.int32
+        feats = alloc("vox_feats", B * caps[0] * P * Cc, torch.float32)
+        coords = alloc("vox_coords", B * caps[0] * 3, torch.int64)
+        npts = alloc("vox_npts", B * caps[0], I32)
+        nvox = alloc("vox_nvox", B, I32)
+        work = alloc("vox_work", L.voxelize_work_bytes(B, N), torch.uint8)
+        with _span("voxelize"):
+            L.voxelize(pts, enc.pc_range, vsize, P, caps[0], out=(feats, coords, npts, nvox, work))
+        self.index = [alloc(f"sp_index{l}", B * d[0] * d[1] * d[2], I32) for l, d in enumerate(dims)]
+        self.cell = [alloc(f"sp_cell{l}", B * caps[l], I32) for l in range(3)]
+        self.count = [nvox, alloc("sp_count1", B, I32), alloc("sp_count2", B, I32)]
+        with _span("sparse_structure"):
+            L.sparse_fill_index(coords, nvox, B, caps[0], *dims[0], self.index[0], self.cell[0])
+            for l in (1, 2):
+                dwork = alloc("sp_down_work", L.sparse_down_work_bytes(B, *dims[l - 1]), torch.uint8)
+                L.sparse_down(self.index[l - 1], B, *dims[l - 1], caps[l], self.index[l], self.cell[l], self.count[l], dwork)
+            self.table = {}
+            for name, (lr, li, stride) in SPARSE_SPEC.items():
+                t = alloc(f"sp_tab_{name}", B * caps[lr] * 27, I32)
+                L.sparse_table(self.index[li], self.cell[lr], self.count[lr], B, caps[lr], dims[li], dims[lr], stride, False, t)
+                self.table[name] = t
+            self.grad_table = {}
+            if grad:
+                for name in ("down1", "down2"):
+                    lr, li, stride = SPARSE_SPEC[name]                 # rows = the layer's inputs (level li), taps look into level lr
+                    t = alloc(f"sp_gtab_{name}", B * caps[li] * 27, I32)
+                    L.sparse_table(self.index[lr], self.cell[li], self.count[li], B, caps[li], dims[lr], dims[li], stride, True, t)
+                    self.grad_table[name] = t
+        self.x0 = alloc("sp_x0", B * caps[0] * SPARSE_KPAD, torch.float32)
+        with _span("sparse_vfe_mean"):
+            L.sparse_vfe_mean(feats, npts, nvox, B, caps[0], P, Cc, SPARSE_KPAD, self.x0)
+        self.keep = (feats, coords, npts)
+
+
+class SparseLiDAREngine(_Engine):
+    """SparseLiDAREncoder, eval mode: voxelize -> structure (index volumes, active sets, neighbour tables) -> mean VFE -> five
+    bevf_sparse_conv_f32 launches with BatchNorm folded into scale / shift (+ ReLU) -> NHWC canvas [B][bev_h][bev_w][c2 * Dz / 4]
+    in the storage dtype (the convolutions compute in fp32).  Row counts stay on the device: nothing here waits for the GPU."""
+
+    def pack(self) -> None:
+        self.layers = []
+        for name, blk in zip(SPARSE_SPEC, self.module.layers()):
+            cout = blk.conv.weight.shape[0]
+            scale, shift = _bn_fold(None, blk.bn, cout, blk.conv.weight.device)
+            self.layers.append((name, sparse_pack_weight(blk.conv), scale, shift, cout))
+
+    def run(self, pts: torch.Tensor) -> torch.Tensor:
+        self.ensure_packed()
+        m = self.module
+        s = SparseStructure(m, pts, lambda name, n, dt: self.buf(name, n, dt))
+        B, caps = s.B, s.caps
+        x, cin, rows_in = s.x0, SPARSE_KPAD, B * caps[0]
+        for name, w, scale, shift, cout in self.layers:
+            lr = SPARSE_SPEC[name][0]
+            y = self.buf(f"sp_y_{name}", B * caps[lr] * cout, torch.float32)
+            with _span(f"sparse_conv_f32:{name}"):
+                L.sparse_conv(x, s.table[name], s.count[lr], w, scale, shift, B, caps[lr], rows_in, cin, cout, True, y)
+            x, cin, rows_in = y, cout, B * caps[lr]
+        D2, H2, W2 = s.dims[2]
+        n = B * H2 * W2 * D2 * cin
+        canvas = self.buf("canvas", n)
+        with _span("sparse_canvas", nbytes=float(canvas.element_size()) * n):
+            L.sparse_canvas(x, s.cell[2], s.count[2], B, caps[2], D2, H2, W2, cin, canvas)
+        self.last = s                                                  # (tests read the structure of the last batch)
+        return canvas[:n].view(B, H2, W2, D2 * cin)
 
 
 class RadarEngine(_Engine):
@@ -1007,7 +1112,7 @@ class RadarBranch(_FusionBranch):
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
     BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, lift=CameraLiftBranch, frustum=CameraFrustumBranch,
-                    pointnet=LidarVectorBranch, pillars=LidarPillarsBranch)
+                    pointnet=LidarVectorBranch, pillars=LidarPillarsBranch, sparse=LidarPillarsBranch)
 
     def __init__(self, module: nn.Module):
         super().__init__(module)

@@ -17,8 +17,10 @@ import torch.nn as nn
 
 from . import engine as E
 from . import camera_rig as CR
-from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, _cfg,  # noqa: F401
-                       lidar_encoder_kind, load_config)
+from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, SparseLiDAREncoder,  # noqa: F401
+                       _cfg, lidar_encoder_kind, load_config)
+
+CANVAS_KINDS = ("pillars", "sparse")          # LiDAR encoders that hand the fusion an NHWC canvas on the BEV grid (lidar_bev)
 
 
 def _cbr(cin: int, cout: int, k: int) -> List[nn.Module]:
@@ -74,7 +76,7 @@ class FlexibleBEVFusion(nn.Module):
             self.cam_num_heights, self.cam_min_depth, self._camera_rig = CR.camera_bev_settings(config)
         if self.camera_view_transform in ("lift", "frustum"):   # (depth bins D, depth_min, depth_max) of the learned depth distribution
             self.cam_depth = CR.camera_lift_settings(config, self.cam_min_depth)
-        pillars = self.lidar_kind == "pillars"
+        pillars = self.lidar_kind in CANVAS_KINDS              # the LiDAR input is a canvas on the BEV grid: lidar_bev, no lidar_init
         if config is not None:
             mc = config.get("model", {})
             bc, dc = mc.get("bev_fusion", {}), config.get("dataset", {})
@@ -85,7 +87,10 @@ class FlexibleBEVFusion(nn.Module):
                 camera_channels = mc.get("camera_encoder", {}).get("output_channels", 512)
             if lidar_channels is None:
                 le = mc.get("lidar_encoder", {}) or {}
-                lidar_channels = le.get("pfn_channels", 64) if pillars else le.get("feature_dim", 1024)
+                if self.lidar_kind == "sparse":
+                    lidar_channels = int(tuple(le.get("channels", (32, 64, 128)))[-1]) * int(le.get("z_voxels", 8)) // 4
+                else:
+                    lidar_channels = le.get("pfn_channels", 64) if pillars else le.get("feature_dim", 1024)
             if radar_channels is None:
                 radar_channels = mc.get("radar_encoder", {}).get("feature_dim", 256)
             self.bev_h = bc.get("bev_h", dc.get("bev_h", 200)) if bev_h is None else bev_h
@@ -97,7 +102,7 @@ class FlexibleBEVFusion(nn.Module):
             self.use_lidar = True if use_lidar is None else use_lidar
             self.use_radar = True if use_radar is None else use_radar
             camera_channels = 512 if camera_channels is None else camera_channels
-            lidar_channels = (64 if pillars else 1024) if lidar_channels is None else lidar_channels
+            lidar_channels = {"pillars": 64, "sparse": 256}.get(self.lidar_kind, 1024) if lidar_channels is None else lidar_channels
             radar_channels = 256 if radar_channels is None else radar_channels
             self.bev_h = 200 if bev_h is None else bev_h
             self.bev_w = 200 if bev_w is None else bev_w
@@ -221,7 +226,7 @@ class FlexibleBEVFusion(nn.Module):
                 B, Cc, H, W = x.shape
                 cam_nhwc, cam_geom = E.to_nhwc(x).to(self._eng().dtype), (B, 1, H, W)
         lid = lidar_features.float() if lidar_features is not None else None
-        if lid is not None and self.lidar_kind == "pillars" and self.use_lidar:
+        if lid is not None and self.lidar_kind in CANVAS_KINDS and self.use_lidar:
             B, Cc, H, W = lid.shape                                       # NCHW canvas -> the engine's NHWC storage
             lid = E.to_nhwc(lid).to(self._eng().dtype).view(B, H, W, Cc)
         out, B = self.forward_nhwc(cam_nhwc, cam_geom, lid,
@@ -237,7 +242,7 @@ class FlexibleBEVFusion(nn.Module):
         out = {}
         if self.use_camera:
             out["camera_proj"] = cnt(self.camera_proj)
-        if self.use_lidar and self.lidar_kind == "pillars":
+        if self.use_lidar and self.lidar_kind in CANVAS_KINDS:
             out["lidar_bev"] = cnt(self.lidar_bev)
             out["lidar_total"] = out["lidar_bev"]
         elif self.use_lidar:
@@ -349,7 +354,9 @@ class FlexibleMultiModal3DDetector(nn.Module):
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
         # encoder + lidar_bev; anything else -> the reference's PointNet + lidar_init / lidar_upsample
-        self.lidar_encoder_type = "PointPillars" if lidar_encoder_kind(lidar_encoder_type, config) == "pillars" else "PointNet"
+        # 'SparseVoxel' / 'sparse' / 'SECOND' -> the sparse-voxel encoder + lidar_bev
+        self.lidar_encoder_type = dict(pillars="PointPillars", sparse="SparseVoxel", pointnet="PointNet")[
+            lidar_encoder_kind(lidar_encoder_type, config)]
         if config is not None:
             mc, dc = config.get("model", {}), config.get("dataset", {})
             self.use_camera = mc.get("use_camera", True) if use_camera is None else use_camera
@@ -377,6 +384,9 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if self.use_lidar and pillars:
             self.lidar_encoder = (PillarLiDAREncoder(bev_h=bev_h, bev_w=bev_w, config=config) if config is not None
                                   else PillarLiDAREncoder(input_channels=4, bev_h=bev_h, bev_w=bev_w))
+        elif self.use_lidar and self.lidar_encoder_type == "SparseVoxel":
+            self.lidar_encoder = (SparseLiDAREncoder(bev_h=bev_h, bev_w=bev_w, config=config) if config is not None
+                                  else SparseLiDAREncoder(input_channels=4, bev_h=bev_h, bev_w=bev_w))
         elif self.use_lidar:
             self.lidar_encoder = (PointNetLiDAREncoder(config=config) if config is not None
                                   else PointNetLiDAREncoder(input_channels=4, feat_dim=1024))
@@ -387,6 +397,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
             extra = dict(lidar_encoder_type=self.lidar_encoder_type, camera_view_transform=camera_view_transform)
             if self.use_lidar and pillars:
                 extra["lidar_channels"] = self.lidar_encoder.pfn_channels
+            elif self.use_lidar and self.lidar_encoder_type == "SparseVoxel":
+                extra["lidar_channels"] = self.lidar_encoder.out_channels
             self.fusion = FlexibleBEVFusion(use_camera=self.use_camera, use_lidar=self.use_lidar,
                                             use_radar=self.use_radar, bev_h=bev_h, bev_w=bev_w, config=config, **extra)
         elif self.fusion_type == "attention":
@@ -470,7 +482,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if self.use_camera and camera_imgs is not None:
             cam, geom = self.camera_encoder.forward_nhwc(camera_imgs)       # stays NHWC: no layout change
         if self.use_lidar and lidar_points is not None:
-            if getattr(self.lidar_encoder, "is_pillars", False):
+            if getattr(self.lidar_encoder, "is_pillars", False) or getattr(self.lidar_encoder, "is_sparse", False):
                 lid = self.lidar_encoder.forward_nhwc(lidar_points)            # NHWC canvas on the fusion grid
             else:
                 lid = self.lidar_encoder._forward_eval(lidar_points)

@@ -816,6 +816,119 @@ class PillarPFNLayer:
         sink.add(bn.bias, dbeta[:Cout])
 
 
+class SparseConvLayer:
+    """One sparse layer (encoders.SparseConvBlock) under train-mode BatchNorm: the gather-GEMM's raw sums over the active rows ->
+    L.sparse_bn_stats (fp64 fixed-order partials over the active rows of the whole batch, running buffers moved there; frozen
+    BatchNorm: the buffers are the statistics) -> relu(batchnorm).  Backward: L.sparse_bn_backward (bn_rows.h's mask and dx), the
+    weight gradient through the forward table, and -- unless the layer is the first -- the data gradient: the same gather-GEMM on
+    dy through the input-side table (a submanifold layer: its forward table with mirrored taps)."""
+
+    def __init__(self, name: str, blk, st: "E.SparseStructure", first: bool):
+        self.name, self.blk, self.st, self.first = name, blk, st, first
+        self.lr, self.li, self.stride = E.SPARSE_SPEC[name]
+
+    def forward(self, x, cin: int, nrows_slot):
+        st, conv, bn = self.st, self.blk.conv, self.blk.bn
+        B, cap, dev = st.B, st.caps[self.lr], x.device
+        self.x, self.cin, self.cin_real = x, cin, conv.weight.shape[1]
+        self.cout = cout = conv.weight.shape[0]
+        self.rows_in = B * st.caps[self.li]
+        self.y = _new(B * cap * cout, dev)
+        with E._span(f"sparse_conv_f32:{self.name}"):
+            L.sparse_conv(x, st.table[self.name], st.count[self.lr], E.sparse_pack_weight(conv), None, None, B, cap, self.rows_in, cin,
+                          cout, False, self.y)
+        self.gamma = bn.weight.detach().float().contiguous() if bn.weight is not None else None
+        self.beta = bn.bias.detach().float().contiguous() if bn.bias is not None else None
+        self.frozen = bn_is_frozen(bn)
+        if self.frozen:
+            self.mean = bn.running_mean.detach().float().contiguous()
+            self.invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps).contiguous()
+        else:
+            self.mean, self.invstd = _new(cout, dev), _new(cout, dev)
+            work = torch.empty(L.sparse_bn_work_bytes(cout), dtype=torch.uint8, device=dev)
+            track = bn.track_running_stats and bn.running_mean is not None
+            with E._span("sparse_bn_stats"):
+                L.sparse_bn_stats(self.y, st.count[self.lr], B, cap, cout, bn.eps, -1.0 if bn.momentum is None else bn.momentum,
+                                  bn.running_mean if track else None, bn.running_var if track else None,
+                                  bn.num_batches_tracked if track else None, self.mean, self.invstd, nrows_slot, work)
+            if track:
+                for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):   # written through raw pointers
+                    if t is not None:
+                        torch.autograd.graph.increment_version(t)
+        a = _new(B * cap * cout, dev)
+        with E._span("sparse_bn_apply"):
+            L.sparse_bn_apply(self.y, st.count[self.lr], B, cap, cout, self.mean, self.invstd, self.gamma, self.beta, a)
+        return a
+
+    def backward(self, da, sink: GradSink):
+        st, conv, bn = self.st, self.blk.conv, self.blk.bn
+        B, cap, cout, dev = st.B, st.caps[self.lr], self.cout, da.device
+        dy, dgamma, dbeta, sums = _new(B * cap * cout, dev), _new(cout, dev), _new(cout, dev), _new(2 * cout, dev)
+        work = torch.empty(L.sparse_bn_work_bytes(cout), dtype=torch.uint8, device=dev)
+        with E._span("sparse_bn_backward"):
+            L.sparse_bn_backward(self.y, da, st.count[self.lr], B, cap, cout, self.mean, self.invstd, self.gamma, self.beta, self.frozen,
+                                 dy, dgamma, dbeta, sums, work)
+        sink.add(bn.weight, dgamma[:cout])
+        sink.add(bn.bias, dbeta[:cout])
+        dw = _new(cout * self.cin_real * 27, dev)
+        wwork = _new(L.sparse_wgrad_work_floats(self.cin, cout), dev)
+        with E._span(f"sparse_conv_wgrad_f32:{self.name}"):
+            L.sparse_conv_wgrad(self.x, dy, st.table[self.name], st.count[self.lr], B, cap, self.rows_in, self.cin, cout, self.cin_real, dw,
+                                wwork)
+        sink.add(conv.weight, dw[:cout * self.cin_real * 27])
+        if self.first:
+            return None
+        cap_in = st.caps[self.li]
+        dx = _new(B * cap_in * self.cin, dev)
+        table = st.table[self.name] if self.stride == 1 else st.grad_table[self.name]
+        with E._span(f"sparse_conv_f32:{self.name}:dgrad"):
+            L.sparse_conv(dy, table, st.count[self.li], E.sparse_pack_weight(conv, transposed=True), None, None, B, cap_in, B * cap, cout,
+                          self.cin, False, dx)
+        return dx
+
+
+class SparseEncoderTape:
+    """SparseLiDAREncoder under train-mode BatchNorm: structure (with the strided layers' input-side tables) -> mean VFE -> five
+    SparseConvLayer -> fp32 NHWC canvas.  Backward: the canvas gradient gathered into the level-2 rows, then the layers in reverse.
+    The one host read of a step is here: the five layers' active row counts, after the forward has been queued, because a
+    train-mode BatchNorm over fewer than two rows is refused (as torch refuses it)."""
+
+    def __init__(self, enc):
+        self.enc = enc
+
+    def forward(self, pts):
+        enc, dev = self.enc, pts.device
+        if next(enc.parameters()).dtype != torch.float32:
+            raise L.BevfError("training: SparseLiDAREncoder trains in fp32 storage only")
+        st = self.st = E.SparseStructure(enc, pts, lambda name, n, dt: _new(n, dev, dt), grad=True)
+        self.B = st.B
+        nrows = torch.full((8,), 2, dtype=torch.int32, device=dev)
+        self.layers = []
+        x, cin = st.x0, E.SPARSE_KPAD
+        for i, (name, blk) in enumerate(zip(E.SPARSE_SPEC, enc.layers())):
+            layer = SparseConvLayer(name, blk, st, first=i == 0)
+            x = layer.forward(x, cin, nrows[i:i + 1])
+            cin = layer.cout
+            self.layers.append(layer)
+        D2, H2, W2 = st.dims[2]
+        self.c2 = cin
+        self.canvas = _new(st.B * H2 * W2 * D2 * cin, dev)
+        L.sparse_canvas(x, st.cell[2], st.count[2], st.B, st.caps[2], D2, H2, W2, cin, self.canvas)
+        few = [n for n, v in zip(E.SPARSE_SPEC, nrows[:5].tolist()) if v < 2]
+        if few:
+            raise L.BevfError(f"training: SparseLiDAREncoder: BatchNorm of {few} saw fewer than two active voxels in the whole batch "
+                              "(train-mode statistics need more than one row, as torch's BatchNorm1d); put the layer in eval mode")
+        return self.canvas
+
+    def backward(self, dcanvas, sink: GradSink) -> None:
+        st = self.st
+        D2, H2, W2 = st.dims[2]
+        d = _new(st.B * st.caps[2] * self.c2, dcanvas.device)
+        L.sparse_canvas_bwd(dcanvas.contiguous(), st.cell[2], st.count[2], st.B, st.caps[2], D2, H2, W2, self.c2, d)
+        for layer in reversed(self.layers):
+            d = layer.backward(d, sink)
+
+
 # ---- module tapes ---------------------------------------------------------------------------------------------------------------
 # One tape per module kind, built from the real nn.Module.  forward() runs the module under train-mode BatchNorm, keeps what the
 # backward needs and exposes the geometry its callers need (B: batch size, cout: output channels, H / W: spatial size);
@@ -1269,7 +1382,8 @@ class FusionTape:
     callback, after radar and LiDAR have contributed theirs."""
 
     BRANCHES = dict(mean=CameraMeanBranchTape, project=CameraProjectBranchTape, lift=CameraLiftBranchTape,
-                    frustum=CameraFrustumBranchTape, pointnet=LidarVectorBranchTape, pillars=LidarPillarsBranchTape)
+                    frustum=CameraFrustumBranchTape, pointnet=LidarVectorBranchTape, pillars=LidarPillarsBranchTape,
+                    sparse=LidarPillarsBranchTape)
 
     def __init__(self, fus):
         self.fus = fus
@@ -1395,6 +1509,9 @@ class DetectorTape:
             if getattr(m.lidar_encoder, "is_pillars", False):              # PointPillars: NHWC fp32 canvas on the BEV grid
                 _no_input_grad(pts, "the LiDAR points")
                 self.lidar = PillarPFNLayer(m.lidar_encoder)
+            elif getattr(m.lidar_encoder, "is_sparse", False):             # sparse voxels: the same kind of canvas, the same route
+                _no_input_grad(pts, "the LiDAR points")
+                self.lidar = SparseEncoderTape(m.lidar_encoder)
             else:
                 self.lidar = PointMLPTape(m.lidar_encoder, 5, fuse_max=True)
             lid_feat = self.lidar.forward(pts)
@@ -1580,6 +1697,23 @@ def pillar_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sparse_train_forward(enc, x: torch.Tensor) -> torch.Tensor:
+    """SparseLiDAREncoder.forward under train-mode BatchNorm -> canvas (B, out_channels, bev_h, bev_w), gradients for the five
+    conv / BatchNorm pairs."""
+    _no_input_grad(x, "the LiDAR points")
+    tape = SparseEncoderTape(enc)
+
+    def fwd(x):
+        return (E.to_nchw(tape.forward(x), tape.B, enc.out_channels, enc.bev_h, enc.bev_w),)
+
+    def bwd(douts, sink):
+        tape.backward(_nhwc(douts[0]), sink)
+        return [None]
+
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(enc))
+    return out
+
+
 def vfe_train_forward(layer, x: torch.Tensor) -> torch.Tensor:
     """VFELayer.forward under train-mode BatchNorm (ref src/encoders.py:431-455): Linear -> BatchNorm1d over all B*Nv*P rows (padding
     rows included, as the reference) -> ReLU -> max over the P points of a voxel -> (B, Nv, out_channels)."""
@@ -1636,7 +1770,7 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
     if first is None:
         raise ValueError("No modality features provided")
     B = first.shape[0]
-    pillars = fus.lidar_kind == "pillars"
+    pillars = fus.lidar_kind in ("pillars", "sparse")                  # the LiDAR input is an NCHW canvas
     geom = None
     if cam is not None:
         geom = (B, cam.shape[1], cam.shape[3], cam.shape[4]) if cam.dim() == 5 else (B, 1, cam.shape[2], cam.shape[3])

@@ -383,6 +383,66 @@ int bevf_pillar_pfn_backward_f32(const bevf_pillar_geom* g, const float* dcanvas
                                  const float* invstd, const float* gamma, const double* moments, int Cout, int frozen,
                                  float* dw, float* db, float* dgamma, float* dbeta, void* work, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sparse-voxel LiDAR encoder (csrc/sparse_index.hip, sparse_conv.hip, sparse_rows.hip): the opt-in LiDAR branch
+ * `model.lidar_encoder.type: SparseVoxel`.  The reference has no line for it: spconv's semantics, held
+ * against the fp64 restatement of tests/sparse_ref.py.  A level is `cap` row slots per frame: row r = b * cap + v is active
+ * iff v < count[b].  The counts stay on the device: grids are sized by capacity, threads past the count return, inactive
+ * slots are neither read nor written.  No atomics anywhere: every entry point is bit-reproducible.
+ * ------------------------------------------------------------------------------------------ */
+/* Level 0 from bevf_voxelize_f32's voxel_coords [B][cap][3] (z, y, x) / num_voxels: index [B][D][H][W] = the row of each cell
+ * or -1 (memset inside), cell [B][cap] = (z * H + y) * W + x of each active row.  B * D * H * W must fit int32.          */
+int bevf_sparse_fill_index(const int64_t* coords, const int32_t* count, int B, int cap, int D, int H, int W, int32_t* index,
+                           int32_t* cell, void* stream);
+/* The active set of a 3x3x3 / stride 2 / pad 1 layer: output cell o of (D/2, H/2, W/2) is active iff some active input i has
+ * 2o-1 <= i <= 2o+1 on every axis.  Rows in raster (z, y, x) order within a frame (mark, fixed-order scan, emit); writes
+ * index_out [B][D/2][H/2][W/2], cell_out [B][cap_out], count_out [B] (clamped to cap_out; cap_out >= min(8 cap_in, cells)
+ * never truncates).  work: bevf_sparse_down_work_bytes(B, D, H, W) bytes.                                               */
+size_t bevf_sparse_down_work_bytes(int B, int D, int H, int W);
+int bevf_sparse_down(const int32_t* index_in, int B, int D, int H, int W, int cap_out, int32_t* index_out, int32_t* cell_out,
+                     int32_t* count_out, void* work, void* stream);
+/* Neighbour table [B * cap][27] (tap k = (kz * 3 + ky) * 3 + kx; -1 = absent) of the rows whose cells (in the grid Dr, Hr, Wr)
+ * are `cell`, looking into `index` [B][Di][Hi][Wi]: forward, in = out * stride - 1 + k; transposed (the data gradient of a
+ * strided layer: the rows are the layer's inputs, index its output volume), out = (in + 1 - k) / stride when that divides. */
+int bevf_sparse_table(const int32_t* index, const int32_t* cell, const int32_t* count, int B, int cap, int Di, int Hi, int Wi,
+                      int Dr, int Hr, int Wr, int stride, int transposed, int32_t* table, void* stream);
+/* Mean VFE: rows[b * Nv + v][c] = mean over the voxel's kept points (fp32 sum in point order, one division) for c < C, 0 for
+ * C <= c < Cpad (the conv kernel's 32-channel K granule).  Inputs are bevf_voxelize_f32's outputs.                       */
+int bevf_sparse_vfe_mean_f32(const float* feats, const int32_t* num_points, const int32_t* num_voxels, int B, int Nv, int P,
+                             int C, int Cpad, float* rows, void* stream);
+/* y[r] = sum over taps k of x[table[r][k]] . w[k] on v_mfma_f32_32x32x2_f32 (exact fp32), then y * scale + shift (either may
+ * be NULL = 1 / 0) and ReLU when relu.  x [rows_in][Cin], w [27][Cin][Cout], y [B * cap][Cout]; Cin, Cout multiples of 32
+ * up to 128.  The data gradient is this entry point on dy, the input-side table and weights packed [27][Cout][Cin].
+ * bevf_sparse_conv_row_tile(): output rows per workgroup.                                                               */
+int bevf_sparse_conv_f32(const float* x, const int32_t* table, const int32_t* count, const float* w, const float* scale,
+                         const float* shift, int B, int cap, int rows_in, int Cin, int Cout, int relu, float* y, void* stream);
+int bevf_sparse_conv_row_tile(void);
+/* dw [Cout][cin_real][3][3][3] (torch's Conv3d layout; channels >= cin_real of x are padding) = sum over the active rows of
+ * x[table[r][k]]^T dy[r]: per-chunk fp32 partials, one fixed-order sum.  work: bevf_sparse_wgrad_work_floats(Cin, Cout).  */
+size_t bevf_sparse_wgrad_work_floats(int Cin, int Cout);
+int bevf_sparse_conv_wgrad_f32(const float* x, const float* dy, const int32_t* table, const int32_t* count, int B, int cap,
+                               int rows_in, int Cin, int Cout, int cin_real, float* dw, float* work, void* stream);
+/* canvas[b][y][x][z * C + c] = rows[r][c] at the row's cell (z, y, x) of (D, H, W), exactly 0 elsewhere (memset inside);
+ * fp32, or bf16 when canvas_bf16.  The backward gathers dcanvas (fp32) into drows.                                      */
+int bevf_sparse_canvas_f32(const float* rows, const int32_t* cell, const int32_t* count, int B, int cap, int D, int H, int W,
+                           int C, void* canvas, int canvas_bf16, void* stream);
+int bevf_sparse_canvas_bwd_f32(const float* dcanvas, const int32_t* cell, const int32_t* count, int B, int cap, int D, int H,
+                               int W, int C, float* drows, void* stream);
+/* BatchNorm over the active rows of y [B * cap][C].  stats: fp64 fixed-order partials -> mean, invstd (biased variance +
+ * eps), the running buffers as nn.BatchNorm1d moves them (momentum < 0 = cumulative average; untouched below two rows),
+ * nrows[0] = the active rows (optional).  apply: a = relu(batchnorm(y)).  backward: g = da through the recomputed ReLU mask,
+ * dgamma = sum g x_hat, dbeta = sum g, dy = gamma invstd (g - mean(g) - x_hat mean(g x_hat)), or gamma invstd g when frozen
+ * (mean / invstd then are the running statistics).  sums: 2 C floats of scratch.  work: bevf_sparse_bn_work_bytes(C).     */
+size_t bevf_sparse_bn_work_bytes(int C);
+int bevf_sparse_bn_stats_f32(const float* y, const int32_t* count, int B, int cap, int C, float eps, float momentum,
+                             float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean,
+                             float* invstd, int32_t* nrows, void* work, void* stream);
+int bevf_sparse_bn_apply_f32(const float* y, const int32_t* count, int B, int cap, int C, const float* mean, const float* invstd,
+                             const float* gamma, const float* beta, float* a, void* stream);
+int bevf_sparse_bn_backward_f32(const float* y, const float* da, const int32_t* count, int B, int cap, int C, const float* mean,
+                                const float* invstd, const float* gamma, const float* beta, int frozen, float* dy,
+                                float* dgamma, float* dbeta, float* sums, void* work, void* stream);
+
 /* Dense scatter of per-voxel features [B][Nv][C] into out [B][C][D][H][W] at voxel_coords (z,y,x) -- the pillar -> BEV
  * canvas step, ref src/encoders.py:399-410 (`feature_grid[b, :, c0, c1, c2] = features.T`, rows in order: when several
  * rows name one cell the LAST one wins; cells no row names are zero).  num_voxels [B] or NULL: with it only rows

@@ -265,6 +265,10 @@ SIGNATURES = {
                                + [C.c_double] * 2 + [C.c_int] * 2 + [C.c_void_p] * 2),
     "bevf_depth_ce_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bevf_depth_ce_bwd_f32": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_size_t, C.c_int, C.c_void_p]),
+    # ---- temporal fusion: ego-motion BEV warp ----
+    "bevf_bev_warp_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_void_p]),
+    "bevf_bev_warp_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_void_p]),
+    "bevf_bev_warp_bwd_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] * 4 + [C.c_void_p]),
 }
 
 
@@ -1669,3 +1673,50 @@ def depth_ce_bwd(pd, p_rs: int, target, g, out, dlogit, x_rs: int, nrows: int, D
     _need("depth_ce_bwd", pd=(pd, _strided(nrows, D, p_rs)), target=(target, nrows), g=(g, 1), out=(out, 2),
           dlogit=(dlogit, _strided(nrows, D, x_rs)))
     _call("bevf_depth_ce_bwd_f32", _p(pd), p_rs, _pc(target, torch.int32), _pc(g), _pc(out), _p(dlogit), x_rs, nrows, D)
+
+
+# ---- temporal fusion: ego-motion BEV warp (csrc/bev_warp.hip) ----
+
+def _warp_args(what: str, ego, B: int, C: int, *strides: int) -> None:
+    if C % 4 or any(cs % 4 or cs < C for cs in strides):
+        raise BevfError(f"{what}: C = {C} and the channel strides {strides} must be multiples of 4, strides >= C")
+    _need(what, ego=(ego, B * 16))
+
+
+def bev_warp(x, y, ego, B: int, H: int, W: int, Cc: int, x_cs: int, y_cs: int, grid) -> None:
+    """y [B][H][W] rows of Cc channels at stride y_cs = x (stride x_cs), the previous frame's map, sampled bilinearly where each
+    current cell was in the previous frame (bevf_bev_warp): ego fp64 [B][4][4] on the device maps current -> previous in metres,
+    grid = (x0, y0, vx, vy) of encoders.pillar_grid.  Zeros outside the map; every row of y is written.  fp32 or bf16 storage."""
+    _warp_args("bev_warp", ego, B, Cc, x_cs, y_cs)
+    if x.dtype != y.dtype:
+        raise BevfError(f"bev_warp: x is {x.dtype}, y is {y.dtype}")
+    _need("bev_warp", x=(x, _strided(B * H * W, Cc, x_cs)), y=(y, _strided(B * H * W, Cc, y_cs)))
+    if x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("bev_warp: x and y share storage")
+    _call("bevf_bev_warp_" + _sfx(x), _p(x, x.dtype), _p(y, x.dtype), _pc(ego, torch.float64), B, H, W, Cc, x_cs, y_cs,
+          *(float(v) for v in grid))
+
+
+def warp_singular_values(ego_host, grid):
+    """The singular values [B][2] of the index-space 2 x 2 part of each current -> previous map (numpy fp64 on the host)."""
+    import numpy as np
+    M = np.asarray(ego_host, dtype=np.float64).reshape(-1, 4, 4)
+    _, _, vx, vy = (float(v) for v in grid)
+    A = M[:, :2, :2] * np.array([[1.0, vy / vx], [vx / vy, 1.0]])
+    if not np.isfinite(M[:, :2, [0, 1, 3]]).all():
+        return np.full((M.shape[0], 2), np.nan)
+    return np.linalg.svd(A, compute_uv=False)
+
+
+def bev_warp_bwd(dy, dx, ego, B: int, H: int, W: int, Cc: int, dy_cs: int, grid, ego_host=None) -> None:
+    """dx [B][H][W][Cc] = the transpose of bev_warp applied to dy (stride dy_cs): a deterministic pull, every element written
+    (bevf_bev_warp_bwd_f32, fp32).  ego_host: the same matrices on the host (read back from `ego` when None, which waits for the
+    device); a map whose index-space singular values leave [1/4, 4], or with a non-finite entry, is refused -- the kernel's
+    candidate box would be unbounded."""
+    _warp_args("bev_warp_bwd", ego, B, Cc, dy_cs)
+    _need("bev_warp_bwd", dy=(dy, _strided(B * H * W, Cc, dy_cs)), dx=(dx, B * H * W * Cc))
+    sv = warp_singular_values(ego.detach().cpu().numpy() if ego_host is None else ego_host, grid)
+    if not (sv >= 0.25).all() or not (sv <= 4.0).all():
+        raise BevfError(f"bev_warp_bwd: the ego-motion map must be finite with index-space singular values within [1/4, 4], got "
+                        f"{sv.tolist()}")
+    _call("bevf_bev_warp_bwd_f32", _p(dy), _p(dx), _pc(ego, torch.float64), B, H, W, Cc, dy_cs, *(float(v) for v in grid))

@@ -895,11 +895,13 @@ def frame_frustum_tables(fus: nn.Module, camera_calib, B: int, ncam: int, Hc: in
 
 
 def concat_slots(fus: nn.Module, branches, feats, text: str, B: Optional[int] = None):
-    """-> ((branch, input) of every modality that has both, in slot order [camera, LiDAR, radar]; channels of the concatenated map,
-    checked against bev_fusion's first conv; frames B, the first input's leading dimension unless given).  text: the mismatch
-    message (FusionEngine's is torch's own, training.FusionTape has another)."""
+    """-> ((branch, input) of every modality that has both, in slot order [camera, LiDAR, radar, history]; channels of the concatenated
+    map, checked against bev_fusion's first conv; frames B, the first input's leading dimension unless given).  text: the mismatch
+    message (FusionEngine's is torch's own, training.FusionTape has another).  The history input of a module with temporal fusion
+    is the (prev_bev, ego, host ego) triple of temporal.check_history -- never None, so its slot is always present; prev_bev None
+    inside it is a first frame."""
     present = [(b, x) for b, x in zip(branches, feats) if b is not None and x is not None]
-    if not present:
+    if all(getattr(b, "is_history", False) for b, _ in present):          # (none at all, or the history alone)
         raise ValueError("No modality features provided")
     B = B or present[0][1].shape[0]
     ccs = fus.bev_channels * len(present)
@@ -1109,6 +1111,33 @@ class RadarBranch(_FusionBranch):
             _run_conv(self.c2, r1, out, B, Sh, Sw, y_cs=ccs)
 
 
+def history_slot(out: torch.Tensor, B: int, P: int, bc: int, ccs: int) -> torch.Tensor:
+    """The [B * P][bc] window (row stride ccs) that starts at out[0]."""
+    return torch.as_strided(out, (B * P, bc), (ccs, 1))
+
+
+class HistoryBranch(_FusionBranch):
+    """Temporal fusion.  Input: (prev_bev (B, bev_channels, S_h, S_w) in the storage dtype or None, ego fp64
+    [B][4][4] on the device, its host copy or None).  The previous map warped by ego-motion straight into the concat slice; a first
+    frame (prev_bev None) zero-fills it.  No weights."""
+
+    is_history = True
+
+    def pack(self, m) -> None:
+        pass
+
+    def run(self, x, B, out, ccs, *_) -> None:
+        from .encoders import pillar_grid
+        prev, ego, _host = x
+        (Sh, Sw, bc), m = self.grid, self.eng.module
+        if prev is None:
+            history_slot(out, B, Sh * Sw, bc, ccs).zero_()
+            return
+        rows = prev.permute(0, 2, 3, 1).contiguous()               # (a view of channels-last memory)
+        with _span("bev_warp", nbytes=2.0 * rows.element_size() * B * Sh * Sw * bc):
+            L.bev_warp(rows, out, ego, B, Sh, Sw, bc, bc, ccs, pillar_grid(m.pc_range, Sh, Sw)[:4])
+
+
 class FusionEngine(_Engine):
     collapse_radar = True        # set False to run radar_refine on the full map (tests compare both, bit for bit)
     BRANCHES = dict(mean=CameraMeanBranch, project=CameraProjectBranch, lift=CameraLiftBranch, frustum=CameraFrustumBranch,
@@ -1120,7 +1149,8 @@ class FusionEngine(_Engine):
         self._frame_tables: Dict[type, _DeviceTables] = {}          # the per-frame tables, one object per class (_frame_tables)
         m = module
         self.branches = [self.BRANCHES[m.camera_view_transform](self) if m.use_camera else None,
-                         self.BRANCHES[m.lidar_kind](self) if m.use_lidar else None, RadarBranch(self) if m.use_radar else None]
+                         self.BRANCHES[m.lidar_kind](self) if m.use_lidar else None, RadarBranch(self) if m.use_radar else None,
+                         HistoryBranch(self) if getattr(m, "temporal", False) else None]
 
     def drop_camera_tables(self) -> None:
         self._camera_tables.clear()
@@ -1138,10 +1168,11 @@ class FusionEngine(_Engine):
         self.f2 = pack_conv(m.bev_fusion[3], m.bev_fusion[4], True)
 
     def run(self, cam: Optional[torch.Tensor], cam_geom: Optional[Tuple[int, int, int, int]],
-            lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor], camera_calib=None) -> Tuple[torch.Tensor, int]:
+            lidar: Optional[torch.Tensor], radar: Optional[torch.Tensor], camera_calib=None, history=None) -> Tuple[torch.Tensor, int]:
         """cam: NHWC encoder features [B*ncam][Hc][Wc][C] with cam_geom = (B, ncam, Hc, Wc); lidar (B,1024), or with a
         PointPillars branch the NHWC canvas (B, S_h, S_w, pfn_channels) in the storage dtype; radar (B,256).  camera_calib
         ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size) for per-frame tables built here, None = the module rig's table.
+        history (a module with temporal fusion): the triple of temporal.check_history; None = a first frame.
         Returns the fused NHWC map [B][S_h*S_w][bev_channels] and B."""
         self.ensure_packed()
         m = self.module
@@ -1149,7 +1180,9 @@ class FusionEngine(_Engine):
         P = Sh * Sw
         text = ("Given groups=1, weight of size [{cout}, {cin}, 3, 3], expected input[{B}, {ccs}, {h}, {w}] to have {cin} channels, "
                 "but got {ccs} channels instead")
-        present, ccs, B = concat_slots(m, self.branches, (cam, lidar, radar), text, cam_geom and cam_geom[0])
+        if self.branches[3] is not None and history is None:
+            history = (None, None, None)
+        present, ccs, B = concat_slots(m, self.branches, (cam, lidar, radar, history), text, cam_geom and cam_geom[0])
         concat = self.buf("concat", B * P * ccs)
         for slot, (branch, x) in enumerate(present):
             branch.run(x, B, concat[slot * bc:], ccs, cam_geom, camera_calib)

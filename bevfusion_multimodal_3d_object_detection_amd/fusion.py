@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import engine as E
 from . import camera_rig as CR
+from . import temporal as T
 from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, SparseLiDAREncoder,  # noqa: F401
                        _cfg, lidar_encoder_kind, load_config)
 
@@ -55,6 +56,10 @@ class FlexibleBEVFusion(nn.Module):
     on the BEV grid.  The frustum is a function of the calibration, so `camera_calib=` works as in 'project' (and takes what
     augment.augment_batch returns); the module's rig serves every frame otherwise.  The calibration's third row must be its depth
     row, as camera_rig.calib_matrices and augment.augmented_calib make it.  camera_bev.num_heights is unused.  fp32 storage only.
+    Extension (opt-in, temporal=True / model.bev_fusion.temporal.enable): a fourth concat slot after radar holds the
+    previous frame's fused map `prev_bev`, resampled onto the current grid through `ego_motion` (temporal.py, csrc/bev_warp.hip);
+    bev_fusion's first conv then has bev_channels more input channels, and there are no other new parameters.  prev_bev=None is the
+    first frame of a sequence: the slot is zeros.
     """
 
     def __init__(self, use_camera: Optional[bool] = None, use_lidar: Optional[bool] = None,
@@ -63,10 +68,11 @@ class FlexibleBEVFusion(nn.Module):
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, bev_channels: Optional[int] = None,
                  pc_range: Optional[List[float]] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
-                 camera_view_transform: Optional[str] = None):
+                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None):
         super().__init__()
         config = _cfg(config, config_path)
         default_range = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+        self.temporal = T.temporal_enabled(temporal, config)    # a fourth concat slot: the previous fused map, warped by ego-motion
         self.lidar_kind = lidar_encoder_kind(lidar_encoder_type, config)
         # camera branch: 'mean' (the reference's camera average + resize), 'project' (camera rig -> BEV grid), 'lift' (+ learned depth)
         # or 'frustum' (lift-splat: learned depth, push to the cell of the frustum point)
@@ -128,7 +134,7 @@ class FlexibleBEVFusion(nn.Module):
         if self.use_radar:
             self.radar_proj = nn.Sequential(nn.Linear(radar_channels, bevc), nn.ReLU(inplace=True))
             self.radar_refine = nn.Sequential(*_cbr(bevc, bevc, 3), *_cbr(bevc, bevc, 3))
-        self.bev_fusion = nn.Sequential(*_cbr(bevc * self.num_modalities, bevc * 2, 3), *_cbr(bevc * 2, bevc, 3))
+        self.bev_fusion = nn.Sequential(*_cbr(bevc * (self.num_modalities + int(self.temporal)), bevc * 2, 3), *_cbr(bevc * 2, bevc, 3))
         self._engine = None
 
     def _eng(self) -> E.FusionEngine:
@@ -193,16 +199,32 @@ class FlexibleBEVFusion(nn.Module):
             raise E.L.BevfError(f"{self.depth_net.weight.dtype} storage with camera_view_transform='frustum' is not supported: the "
                                 "lift-splat kernels are fp32 only (bf16 models: camera_view_transform='project' or 'mean')")
 
-    def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib=None):
-        """Internal fast path on NHWC camera features (no layout change); camera_calib as camera_calib_tensor returns it."""
-        return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib)
+    def forward_nhwc(self, cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib=None, history=None):
+        """Internal fast path on NHWC camera features (no layout change); camera_calib as camera_calib_tensor returns it, history as
+        temporal.check_history returns it."""
+        if history is None:                                              # (the call every model without temporal fusion makes)
+            return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib)
+        return self._eng().run(cam_nhwc, cam_geom, lidar_features, radar_features, camera_calib, history)
+
+    def history(self, prev_bev, ego_motion, *inputs):
+        """`prev_bev=` / `ego_motion=` checked against the first input that is there (temporal.check_history)."""
+        first = next((t[0] if isinstance(t, (list, tuple)) else t for t in inputs if t is not None), None)
+        if first is None or not (self.temporal or prev_bev is not None or ego_motion is not None):
+            return None                                                  # (no input: the forward raises "No modality features provided")
+        return T.check_history(self, prev_bev, ego_motion, first.shape[0], first.device, self._eng().dtype)
 
     def forward(self, camera_features: Optional[torch.Tensor] = None, lidar_features: Optional[torch.Tensor] = None,
-                radar_features: Optional[torch.Tensor] = None, camera_calib=None) -> torch.Tensor:
+                radar_features: Optional[torch.Tensor] = None, camera_calib=None, prev_bev: Optional[torch.Tensor] = None,
+                ego_motion=None) -> torch.Tensor:
         """camera_calib ('project' and 'frustum' branches): per-frame calibration -- a sequence of B camera_rig.CameraRig or the
-        float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame."""
+        float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices; None = the module's rig for every frame.
+        prev_bev / ego_motion (temporal=True): the previous frame's fused map (B, bev_channels, bev_h, bev_w) in the storage dtype
+        and the float64 (B, 4, 4) current -> previous frame map of temporal.ego_motion (host or device); prev_bev None = the first
+        frame of a sequence (a zero history slot; a mixed batch passes zeros for the frames that start one)."""
         self.check_lift_supported(camera_calib)
         self.check_frustum_supported()
+        history = self.history(prev_bev, ego_motion, camera_features if self.use_camera else None,
+                               lidar_features if self.use_lidar else None, radar_features if self.use_radar else None)
         if camera_calib is not None:
             cf = camera_features if self.use_camera else None
             camera_calib = self.camera_calib_tensor(camera_calib, 0 if cf is None else cf.shape[0],
@@ -211,11 +233,16 @@ class FlexibleBEVFusion(nn.Module):
         if self.training:
             from . import training
             if training.wants_train_path(self):         # used outside the detector in train mode: batch statistics + gradients
+                if history is not None:
+                    return training.fusion_train_forward(self, camera_features, lidar_features, radar_features, camera_calib, history)
                 return training.fusion_train_forward(self, camera_features, lidar_features, radar_features, camera_calib)
         with torch.no_grad():
+            if history is not None:
+                E.require_cuda(history[0])
+                return self._forward_eval(camera_features, lidar_features, radar_features, camera_calib, history)
             return self._forward_eval(camera_features, lidar_features, radar_features, camera_calib)
 
-    def _forward_eval(self, camera_features, lidar_features, radar_features, camera_calib=None) -> torch.Tensor:
+    def _forward_eval(self, camera_features, lidar_features, radar_features, camera_calib=None, history=None) -> torch.Tensor:
         cam_nhwc = cam_geom = None
         if self.use_camera and camera_features is not None:
             x = camera_features.float()
@@ -230,7 +257,7 @@ class FlexibleBEVFusion(nn.Module):
             B, Cc, H, W = lid.shape                                       # NCHW canvas -> the engine's NHWC storage
             lid = E.to_nhwc(lid).to(self._eng().dtype).view(B, H, W, Cc)
         out, B = self.forward_nhwc(cam_nhwc, cam_geom, lid,
-                                   radar_features.float() if radar_features is not None else None, camera_calib)
+                                   radar_features.float() if radar_features is not None else None, camera_calib, history)
         return E.to_nchw(out, B, self.bev_channels, self.bev_h, self.bev_w)
 
     def get_config_str(self) -> str:
@@ -349,7 +376,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  fusion_type: Optional[str] = None, detection_head: Optional[str] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
-                 camera_view_transform: Optional[str] = None):
+                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -395,6 +422,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
                                   else MultiRadarEncoder(input_channels=7, feat_dim=256, num_radars=5))
         if self.fusion_type == "bev":
             extra = dict(lidar_encoder_type=self.lidar_encoder_type, camera_view_transform=camera_view_transform)
+            if temporal is not None:                      # (None: the fusion reads model.bev_fusion.temporal.enable itself)
+                extra["temporal"] = temporal
             if self.use_lidar and pillars:
                 extra["lidar_channels"] = self.lidar_encoder.pfn_channels
             elif self.use_lidar and self.lidar_encoder_type == "SparseVoxel":
@@ -448,9 +477,14 @@ class FlexibleMultiModal3DDetector(nn.Module):
         return depth_points, depth_point_counts
 
     def forward(self, camera_imgs: Optional[torch.Tensor] = None, lidar_points: Optional[torch.Tensor] = None,
-                radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None, depth_points: Optional[torch.Tensor] = None,
+                radar_points: Optional[List[torch.Tensor]] = None, camera_calib=None, prev_bev: Optional[torch.Tensor] = None,
+                ego_motion=None, depth_points: Optional[torch.Tensor] = None,
                 depth_point_counts: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
+        """prev_bev / ego_motion (temporal=True): the 'bev' output of the previous frame and the float64 (B, 4, 4)
+        current -> previous frame map of temporal.ego_motion (host or device); prev_bev None = the first frame of a sequence.  A model
+        with temporal fusion returns 'bev' as well: an owned (B, bev_channels, H, W) channels-last copy of the fused map (detached in
+        train mode, where the history is a constant), to hand back as prev_bev for the next frame.
+        camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame.
         depth_points (train mode, camera_view_transform='frustum' or 'lift'): fp32 (B, N, >= 3) LiDAR points on the
@@ -467,17 +501,38 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if depth_sup is not None:
             from . import depth_supervision
             depth_sup = depth_supervision.check_points(*depth_sup)
+        history = self._history(camera_imgs, lidar_points, radar_points, prev_bev, ego_motion)
         if self.training and (torch.is_grad_enabled() or _any_bn_training(self)):
             # under no_grad a train-mode model still normalises with batch statistics and updates the running buffers, as torch does
             from . import training                      # train-mode BN + tape + hand-written backward (training.py)
             E.require_cuda(camera_imgs, lidar_points)
+            if history is not None:
+                return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib, depth_sup, history)
             if depth_sup is not None:
                 return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib, depth_sup)
             return training.detector_train_forward(self, camera_imgs, lidar_points, radar_points, camera_calib)
         with torch.no_grad():
+            if history is not None:
+                return self._forward_inference(camera_imgs, lidar_points, radar_points, camera_calib, history)
             return self._forward_inference(camera_imgs, lidar_points, radar_points, camera_calib)
 
-    def _forward_inference(self, camera_imgs, lidar_points, radar_points, camera_calib=None) -> Dict[str, torch.Tensor]:
+    def _history(self, camera_imgs, lidar_points, radar_points, prev_bev, ego_motion):
+        """`prev_bev=` / `ego_motion=` of forward -> what FlexibleBEVFusion.history makes of them: None for a model without temporal
+        fusion (either argument then raises), else the (prev_bev, ego, host ego) triple."""
+        if not hasattr(self.fusion, "history"):
+            if prev_bev is not None or ego_motion is not None:
+                raise E.L.BevfError("prev_bev / ego_motion need the 'bev' fusion built with temporal=True")
+            return None
+        history = self.fusion.history(prev_bev, ego_motion, camera_imgs if self.use_camera else None,
+                                      lidar_points if self.use_lidar else None, radar_points if self.use_radar else None)
+        if history is not None and history[0] is not None:
+            if self.training:                           # inside the detector the history is a constant of the step
+                from .training import _no_input_grad
+                _no_input_grad(history[0], "the history BEV map (prev_bev)")
+            E.require_cuda(history[0])
+        return history
+
+    def _forward_inference(self, camera_imgs, lidar_points, radar_points, camera_calib=None, history=None) -> Dict[str, torch.Tensor]:
         cam = geom = lid = rad = None
         if self.use_camera and camera_imgs is not None:
             cam, geom = self.camera_encoder.forward_nhwc(camera_imgs)       # stays NHWC: no layout change
@@ -488,15 +543,24 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
-        return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
+        if history is None:
+            fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
+            return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
+        fus = self.fusion
+        fused, B = fus.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None, history)
+        out = self.det_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
+        out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
+        return out
 
     def get_config_str(self) -> str:
         return f"{self.fusion.get_config_str()}_{self.fusion_type}_{self.detection_head_type}"
 
-    def make_graphed(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None) -> "GraphedDetector":
+    def make_graphed(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None, prev_bev=None,
+                     ego_motion=None) -> "GraphedDetector":
         """Capture the inference forward for these input shapes into one hipGraph (launch-bound small batches)."""
-        return GraphedDetector(self, camera_imgs, lidar_points, radar_points, camera_calib)
+        if prev_bev is None and ego_motion is None:
+            return GraphedDetector(self, camera_imgs, lidar_points, radar_points, camera_calib)
+        return GraphedDetector(self, camera_imgs, lidar_points, radar_points, camera_calib, prev_bev, ego_motion)
 
 
 class GraphedDetector:
@@ -506,9 +570,12 @@ class GraphedDetector:
     copied into static buffers, outputs are static tensors that the next replay overwrites (clone to keep).
     Weights are baked in as of capture time: re-capture after a parameter update.  With `camera_calib` the per-frame calibration
     is a graph input like the images (a static device tensor, copied into before the replay): the table build and the gather are
-    part of the capture, nothing is built on the host."""
+    part of the capture, nothing is built on the host.  A model with temporal fusion is always captured with the warp: `prev_bev`
+    and `ego_motion` are static inputs of the same kind (zeros and the identity when the capture gets none), and a call without
+    prev_bev zeroes the static history, which gives the bits of the eager first-frame path."""
 
-    def __init__(self, model: "FlexibleMultiModal3DDetector", camera_imgs, lidar_points, radar_points, camera_calib=None):
+    def __init__(self, model: "FlexibleMultiModal3DDetector", camera_imgs, lidar_points, radar_points, camera_calib=None,
+                 prev_bev=None, ego_motion=None):
         assert not model.training, "capture the inference forward: call model.eval() first"
         E.require_cuda(camera_imgs, lidar_points)
         self.model = model
@@ -516,19 +583,54 @@ class GraphedDetector:
         self.static_calib = None if calib is None else (calib[0].to(camera_imgs.device).clone().contiguous(), calib[1])
         c = lambda t: t.clone() if t is not None else None
         self.static_in = (c(camera_imgs), c(lidar_points), [r.clone() for r in radar_points] if radar_points else None)
+        self.static_history = self._capture_history(prev_bev, ego_motion)
+        args = (self.static_calib,) if self.static_history is None else (self.static_calib, self.static_history)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
             for _ in range(2):                                   # packs weights, sizes workspaces, sets kernel attributes
-                model._forward_inference(*self.static_in, self.static_calib)
+                model._forward_inference(*self.static_in, *args)
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), torch.no_grad():
-            self.static_out = model._forward_inference(*self.static_in, self.static_calib)
+            self.static_out = model._forward_inference(*self.static_in, *args)
+
+    def _capture_history(self, prev_bev, ego_motion):
+        """The static (prev_bev, ego, None) of a model with temporal fusion -- zeros / identities where the capture got none --, None
+        for any other model (either argument then raises)."""
+        model, (si, sp, sr) = self.model, self.static_in
+        history = model._history(si, sp, sr, prev_bev, ego_motion)
+        if history is None:
+            return None
+        fus = model.fusion
+        first = next(t[0] if isinstance(t, list) else t for t in (si if model.use_camera else None, sp if model.use_lidar else None,
+                                                                   sr if model.use_radar else None) if t is not None)
+        B, dev = first.shape[0], first.device
+        prev = (torch.zeros(B, fus.bev_h, fus.bev_w, fus.bev_channels, dtype=fus._eng().dtype, device=dev).permute(0, 3, 1, 2)
+                if history[0] is None else history[0].clone(memory_format=torch.channels_last))
+        ego = torch.eye(4, dtype=torch.float64, device=dev).repeat(B, 1, 1) if history[1] is None else history[1].clone()
+        return prev, ego, None
+
+    def _set_history(self, prev_bev, ego_motion) -> None:
+        if self.static_history is None:
+            if prev_bev is not None or ego_motion is not None:
+                self.model._history(*self.static_in, prev_bev, ego_motion)           # raises: no temporal fusion
+            return
+        prev, ego, _ = self.static_history
+        history = self.model._history(*self.static_in, prev_bev, ego_motion)
+        if history[0] is None:
+            prev.zero_()
+            return
+        if history[0].data_ptr() != prev.data_ptr():
+            prev.copy_(history[0])
+        if history[1].data_ptr() != ego.data_ptr():
+            ego.copy_(history[1])
 
     @torch.no_grad()
-    def __call__(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None) -> Dict[str, torch.Tensor]:
+    def __call__(self, camera_imgs=None, lidar_points=None, radar_points=None, camera_calib=None, prev_bev=None,
+                 ego_motion=None) -> Dict[str, torch.Tensor]:
         si, sp, sr = self.static_in
+        self._set_history(prev_bev, ego_motion)
         if camera_calib is not None:
             if self.static_calib is None:
                 raise E.L.BevfError("GraphedDetector: captured without camera_calib; capture again with one")
@@ -555,13 +657,16 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
                     lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
-                    **kwargs) -> FlexibleMultiModal3DDetector:
+                    temporal: Optional[bool] = None, **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
     camera_view_transform: 'project' selects the camera -> BEV projection branch, 'lift' its learned-depth variant, 'frustum' the
     lift-splat branch, 'mean' the reference's camera average (None: the config's model.bev_fusion.camera_view_transform, else
-    'mean')."""
+    'mean').
+    temporal: True adds the history slot of temporal BEV fusion (None: the config's model.bev_fusion.temporal.enable, else off)."""
+    if temporal is not None:
+        kwargs["temporal"] = temporal
     config = _cfg(config, config_path)
     if config is not None and modality_config is None:
         modality_config = config.get("model", {}).get("modality_config", "all")

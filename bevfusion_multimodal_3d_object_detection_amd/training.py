@@ -1373,6 +1373,33 @@ class RadarBranchTape(_FusionBranchTape):
         return self.rp.backward(drv.contiguous(), sink)
 
 
+class HistoryBranchTape(_FusionBranchTape):
+    """Temporal fusion.  Input (prev_bev (B, bev_channels, H, W) fp32 or None, ego fp64 [B][4][4] on the device, its
+    host copy or None): the ego-motion warp straight into the slot (zeros for a first frame); the backward is the pull kernel, run
+    only when the caller wants the gradient of prev_bev (want_grad).  No parameters, no ReLU."""
+
+    is_history = True
+    want_grad = False
+
+    def forward(self, x, B, concat, ccs, slot, *_) -> None:
+        self.B, self.ccs, self.slot = B, ccs, slot
+        prev, self.ego, self.ego_host = x
+        from .encoders import pillar_grid
+        self.grid = pillar_grid(self.fus.pc_range, self.H, self.W)[:4]
+        if prev is None:
+            self._slot(concat).zero_()
+            return
+        rows = prev.detach().permute(0, 2, 3, 1).contiguous()          # (a view of channels-last memory)
+        L.bev_warp(rows, concat[slot * self.bc:], self.ego, B, self.H, self.W, self.bc, self.bc, ccs, self.grid)
+
+    def backward(self, dconcat, sink):
+        if not self.want_grad or self.ego is None:
+            return None
+        dx = _new(self.B * self.H * self.W * self.bc, dconcat.device)
+        L.bev_warp_bwd(dconcat[self.slot * self.bc:], dx, self.ego, self.B, self.H, self.W, self.bc, self.ccs, self.grid, self.ego_host)
+        return dx
+
+
 class FusionTape:
     """FlexibleBEVFusion (ref src/fusion.py:209-297): NHWC camera features [B*ncam*Hc*Wc*C] with cam_geom = (B, ncam, Hc, Wc),
     LiDAR (B, C_l) vectors or the PointPillars NHWC canvas on the fusion grid, radar (B, C_r) vectors -> fused NHWC map
@@ -1388,21 +1415,28 @@ class FusionTape:
     def __init__(self, fus):
         self.fus = fus
         self.branches = [self.BRANCHES[fus.camera_view_transform](fus) if fus.use_camera else None,
-                         self.BRANCHES[fus.lidar_kind](fus) if fus.use_lidar else None, RadarBranchTape(fus) if fus.use_radar else None]
+                         self.BRANCHES[fus.lidar_kind](fus) if fus.use_lidar else None, RadarBranchTape(fus) if fus.use_radar else None,
+                         HistoryBranchTape(fus) if getattr(fus, "temporal", False) else None]
 
-    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None, depth_sup=None):
+    def forward(self, cam_feat, cam_geom, lid_feat, rad_feat, B, camera_calib=None, depth_sup=None, history=None,
+                history_grad: bool = False):
         """camera_calib ('project' / 'frustum' branches): (fp64 [B, ncam, 4, 4], image_size), see CameraProjectBranchTape.
         depth_sup ('frustum' / 'lift' branches): (points, counts) of the LiDAR depth supervision, see DepthLossTape; the camera
-        branch then keeps its loss in .depth."""
+        branch then keeps its loss in .depth.
+        history (temporal fusion): the triple of temporal.check_history, None = a first frame; history_grad: the backward computes
+        the gradient of prev_bev (.dhistory)."""
         fus = self.fus
         if depth_sup is not None:
             self.branches[0].depth_sup = depth_sup
+        if self.branches[3] is not None:
+            history = (None, None, None) if history is None else history
+            self.branches[3].want_grad = history_grad
         self.B, self.H, self.W, self.cout = B, fus.bev_h, fus.bev_w, fus.bev_channels
-        feats = (cam_feat, lid_feat, rad_feat)
+        feats = (cam_feat, lid_feat, rad_feat, history)
         present, ccs, B = E.concat_slots(fus, self.branches, feats,
                                          "expected input to have {cin} channels, but got {ccs} channels instead", B)
         concat = _new(B * self.H * self.W * ccs, present[0][1].device)
-        names = {tape: name for tape, name in zip(self.branches, ("camera", "lidar", "radar")) if tape is not None}
+        names = {tape: name for tape, name in zip(self.branches, ("camera", "lidar", "radar", "history")) if tape is not None}
         self.present = [(names[tape], tape) for tape, _ in present]
         for slot, (tape, x) in enumerate(present):
             tape.forward(x, B, concat, ccs, slot, cam_geom, camera_calib)
@@ -1415,14 +1449,17 @@ class FusionTape:
     def backward(self, dfused, sink: GradSink, pre=None, on_radar=None, on_lidar=None, on_camera=None):
         """pre: BatchNorm-backward partials for f2 that arrive with dfused (or None).  Each modality's input gradient (radar (B*C_r),
         LiDAR (B*C_l) or the pillar canvas, camera NHWC) goes to its callback as soon as it exists -- the detector continues into
-        that encoder there -- and is returned as well: (drad, dlid, dcam)."""
+        that encoder there -- and is returned as well: (drad, dlid, dcam).  The history slot, the last one, goes first; its gradient
+        (NHWC, or None when nobody asked for it) stays in .dhistory."""
         da1, _, pre_f1 = self.f2.backward(dfused, sink, fuse_next=self.f1, pre=pre)
         dconcat, _ = self.f1.backward(da1, sink, pre=pre_f1)
-        hooks, grads = dict(camera=on_camera, lidar=on_lidar, radar=on_radar), dict(camera=None, lidar=None, radar=None)
+        hooks = dict(camera=on_camera, lidar=on_lidar, radar=on_radar, history=None)
+        grads = dict(camera=None, lidar=None, radar=None, history=None)
         for name, tape in reversed(self.present):
             grads[name] = tape.backward(dconcat, sink)
             if hooks[name] is not None:
                 hooks[name](grads[name])
+        self.dhistory = grads["history"]
         return grads["radar"], grads["lidar"], grads["camera"]
 
 
@@ -1481,8 +1518,9 @@ class DetectorTape:
     the order radar, camera, LiDAR (RELU_TRACE follows it), then fusion and head.  The backward walks them in reverse and marks
     where gradients become final for the data-parallel all-reduce (sink.ready())."""
 
-    def __init__(self, model, camera_calib=None, depth_sup=None):
+    def __init__(self, model, camera_calib=None, depth_sup=None, history=None):
         self.m = model
+        self.history = history                    # temporal fusion: (prev_bev, ego, host ego), a constant of the step (no gradient)
         self.camera_calib = camera_calib          # per-frame calibration of the 'project' camera branch (FusionTape.forward)
         self.depth_sup = depth_sup                # (points, counts): LiDAR depth supervision of the 'frustum' / 'lift' branch, a sixth output
 
@@ -1517,7 +1555,12 @@ class DetectorTape:
             lid_feat = self.lidar.forward(pts)
             B = self.lidar.B
         self.fusion = FusionTape(m.fusion)
-        fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None, self.depth_sup)
+        if self.history is None:
+            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None, self.depth_sup)
+        else:
+            fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None,
+                                        self.depth_sup, self.history)
+            self.bev = (fused, B)                 # the 'bev' output is copied from it (detector_train_forward)
         self.head = HeadTape(m.det_head)
         outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
         if self.depth_sup is None:
@@ -1615,14 +1658,20 @@ def wants_train_path(module: nn.Module) -> bool:
     return any_bn_training(module) or torch.is_grad_enabled()
 
 
-def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_sup=None) -> Dict[str, torch.Tensor]:
+def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_sup=None, history=None) -> Dict[str, torch.Tensor]:
     """depth_sup = (points, counts): the LiDAR depth supervision of the 'frustum' / 'lift' camera branch (DepthLossTape); the
-    result then carries 'depth_loss', a sixth output of the same autograd node, and 'depth_pixels', the supervised pixels."""
-    tape = DetectorTape(model, camera_calib, depth_sup)
+    result then carries 'depth_loss', a sixth output of the same autograd node, and 'depth_pixels', the supervised pixels.
+    history = (prev_bev, ego, host ego) of a model with temporal fusion (temporal.check_history): a constant of the step; the result
+    then carries 'bev', a detached owned copy of the fused map."""
+    tape = DetectorTape(model, camera_calib, depth_sup, history)
     outs = _TapeFn.apply("detector", tape.forward, tape.backward, _GRAD_REDUCER, 3, imgs, pts, radars, *_trainable(model))
     res = dict(zip(E.HEAD_BRANCHES, outs))
     if depth_sup is not None:
         res["depth_loss"], res["depth_pixels"] = outs[5], tape.depth_out[1].clone()
+    if history is not None:
+        from .temporal import own_bev
+        fus = model.fusion
+        res["bev"] = own_bev(tape.bev[0], tape.bev[1], fus.bev_h, fus.bev_w, fus.bev_channels)
     return res
 
 
@@ -1760,9 +1809,11 @@ def radar_train_forward(enc, radar_list) -> torch.Tensor:
     return out
 
 
-def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_features=None, camera_calib=None) -> torch.Tensor:
+def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_features=None, camera_calib=None,
+                         history=None) -> torch.Tensor:
     """FlexibleBEVFusion.forward under train-mode BatchNorm (ref src/fusion.py:209-297) -> (B, bev_channels, bev_h, bev_w), with
-    gradients for the parameters AND for the three feature inputs."""
+    gradients for the parameters AND for the three feature inputs -- and, with temporal fusion, for prev_bev = history[0] (history:
+    the triple of temporal.check_history)."""
     cam = camera_features if fus.use_camera else None
     lid = lidar_features if fus.use_lidar else None
     rad = radar_features if fus.use_radar else None
@@ -1775,8 +1826,12 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
     if cam is not None:
         geom = (B, cam.shape[1], cam.shape[3], cam.shape[4]) if cam.dim() == 5 else (B, 1, cam.shape[2], cam.shape[3])
     tape = FusionTape(fus)
+    prev = None if history is None else history[0]
+    if prev is not None:
+        E.require_cuda(prev)
+    prev_grad = prev is not None and prev.requires_grad and torch.is_grad_enabled()
 
-    def fwd(cam, lid, rad):
+    def fwd(cam, lid, rad, prev=None):
         cam_nhwc = None
         if cam is not None:
             _, n, h, w = geom
@@ -1784,8 +1839,9 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
         lid_in = None if lid is None else lid.detach().float().contiguous()
         if lid_in is not None and pillars:                             # NCHW pillar canvas -> NHWC
             lid_in = _nhwc(lid_in)
+        extra = () if history is None else (None, (prev,) + tuple(history[1:]), prev_grad)
         fused = tape.forward(cam_nhwc, geom, lid_in, None if rad is None else rad.detach().float().contiguous(), B,
-                             camera_calib if cam_nhwc is not None else None)
+                             camera_calib if cam_nhwc is not None else None, *extra)
         return (E.to_nchw(fused, B, tape.cout, tape.H, tape.W),)
 
     def bwd(douts, sink):
@@ -1799,9 +1855,17 @@ def fusion_train_forward(fus, camera_features=None, lidar_features=None, radar_f
             dlid = dlid.reshape(-1)[:lid.numel()].view(lid.shape)
         if drad is not None:
             drad = drad.reshape(-1)[:rad.numel()].view(rad.shape)
-        return [dcam, dlid, drad]
+        if history is None:
+            return [dcam, dlid, drad]
+        dprev = tape.dhistory
+        if dprev is not None:                                          # NHWC rows -> (B, C, H, W), channels-last memory
+            dprev = dprev[:prev.numel()].view(B, tape.H, tape.W, tape.cout).permute(0, 3, 1, 2)
+        return [dcam, dlid, drad, dprev]
 
-    (out,) = _TapeFn.apply("module", fwd, bwd, None, 3, cam, lid, rad, *_trainable(fus))
+    if history is None:
+        (out,) = _TapeFn.apply("module", fwd, bwd, None, 3, cam, lid, rad, *_trainable(fus))
+    else:
+        (out,) = _TapeFn.apply("module", fwd, bwd, None, 4, cam, lid, rad, prev, *_trainable(fus))
     return out
 
 

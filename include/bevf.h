@@ -931,6 +931,31 @@ int bevf_paste_points_f32(const float* points, const int32_t* n_in, const float*
                           const float* bank_boxes, const int32_t* cand, const int32_t* accepted, const int32_t* prefix, float* out,
                           int32_t* count, int32_t* work, int B, int N, int C, int K, int bank_ncol, int Kc, int capacity, void* stream);
 
+/* ==========================================================================================
+ * Ego-motion BEV warp (temporal fusion; csrc/bev_warp.hip).
+ * ========================================================================================== */
+
+/* y[b][i][j][0:C] (row stride y_cs) = the previous frame's map x [B][H][W] rows of C channels (row stride x_cs) sampled bilinearly
+ * at the point current cell (row i = y, column j = x) had in the previous frame.  ego: DEVICE fp64 [B][4][4], M = ego[b] maps a point
+ * of the current frame to the previous one, in metres; only M[0:2, 0:2] and M[0:2, 3] are read.  All in fp64:
+ *   xc = x0 + (j + 0.5) vx, yc = y0 + (i + 0.5) vy;  (xp, yp) = M[0:2,0:2] (xc, yc) + M[0:2,3]
+ *   qj = (xp - x0) / vx - 0.5, qi = (yp - y0) / vy - 0.5;  j0 = floor(qj), fj = qj - j0, i0 = floor(qi), fi = qi - i0
+ * weights (1-fi)(1-fj), (1-fi)fj, fi(1-fj), fi fj, each rounded once to fp32; a corner outside [0,H) x [0,W) contributes zero
+ * (grid_sample, padding_mode='zeros', align_corners=False), a non-finite q gives a zero row; the sum is fp32 in the corner order
+ * (i0,j0), (i0,j0+1), (i0+1,j0), (i0+1,j0+1).  bf16 storage computes in fp32.  Every output row is written.  C, x_cs, y_cs
+ * multiples of 4; B * H * W * max(x_cs, y_cs) < 2^31.                                                                           */
+int bevf_bev_warp_f32(const float* x, float* y, const double* ego, int B, int H, int W, int C, int x_cs, int y_cs, float x0,
+                      float y0, float vx, float vy, void* stream);
+int bevf_bev_warp_bf16(const void* x, void* y, const double* ego, int B, int H, int W, int C, int x_cs, int y_cs, float x0,
+                       float y0, float vx, float vy, void* stream);
+/* The transpose: dx [B][H][W][C] (dense) from dy (row stride dy_cs).  A pull without atomics: source cell (u, v) sums w * dy over the
+ * targets whose sample point lies within one cell of it, in row-major target order, the weight recomputed by the forward's own
+ * expression; the candidates are the integer bounding box, widened by one cell, of the inverse affine image of
+ * [v-1, v+1] x [u-1, u+1].  Every element of dx is written.  The caller keeps the index-space map away from singular (the Python
+ * wrapper refuses singular values outside [1/4, 4]).                                                                              */
+int bevf_bev_warp_bwd_f32(const float* dy, float* dx, const double* ego, int B, int H, int W, int C, int dy_cs, float x0, float y0,
+                          float vx, float vy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,390 @@
+"""Temporal BEV fusion on the GPU: the ego-motion warp kernels against tests/bev_warp_ref.py with derived bounds,
+the fusion module with a history slot against the fp64 composition (eval and train), and the detector carrying 'bev' from frame to
+frame, eager and as a replayed graph."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from bevfusion_multimodal_3d_object_detection_amd import _lib as L
+from bevfusion_multimodal_3d_object_detection_amd import engine, fusion, synth, temporal
+from bevfusion_multimodal_3d_object_detection_amd.encoders import pillar_grid
+from tests import bev_warp_ref as R
+from tests.conftest import rel_err
+
+pytestmark = pytest.mark.gpu
+
+# pc_range per grid (H, W): cell sizes are exact binary fractions, so flips and integer-cell translations give weights of exactly 0 / 1
+PCS = {(6, 5): [-5.0, -3.0, -5.0, 5.0, 3.0, 3.0], (12, 9): [-4.5, -6.0, -5.0, 4.5, 6.0, 3.0], (8, 8): [-4.0, -4.0, -5.0, 4.0, 4.0, 3.0]}
+EPS = 2.0 ** -24
+
+
+def _affine(a, b, c, d, tx=0.0, ty=0.0):
+    M = np.eye(4)
+    M[:2, :2], M[:2, 3] = [[a, b], [c, d]], [tx, ty]
+    return M
+
+
+def _general(deg, s, tx, ty):
+    c, sn = math.cos(math.radians(deg)) * s, math.sin(math.radians(deg)) * s
+    return _affine(c, -sn, sn, c, tx, ty)
+
+
+def _maps(name, H, W):
+    """B = 2 matrices per case, a different one per frame."""
+    _, _, vx, vy = pillar_grid(PCS[(H, W)], H, W)[:4]
+    return np.stack(dict(
+        identity_shift=[np.eye(4), _affine(1, 0, 0, 1, 2 * vx, -1 * vy)],
+        flip=[_affine(-1, 0, 0, 1), _affine(1, 0, 0, -1)],
+        quarter=[_affine(0, -1, 1, 0), _affine(0, 1, -1, 0)],
+        general=[_general(17.0, 1.05, 0.7, -0.4), _general(-17.0, 1 / 1.05, -1.1, 0.3)],
+        far=[_affine(1, 0, 0, 1, 3.0 * W * vx, 0.0), _affine(1, 0, 0, 1, 0.0, -2.5 * H * vy)])[name])
+
+
+def _run_forward(x_rows, ego, H, W, C, x_cs, dtype, sentinel=777.0):
+    """x_rows [B*H*W][x_cs] (padding columns included) -> (slot [B][H][W][C], the whole [B*H*W][3C] concat-like buffer)."""
+    B = ego.shape[0]
+    y = torch.full((B * H * W, 3 * C), sentinel, dtype=dtype, device="cuda")
+    L.bev_warp(x_rows.view(-1), y.view(-1)[2 * C:], torch.from_numpy(ego).cuda(), B, H, W, C, x_cs, 3 * C, pillar_grid(PCS[(H, W)], H, W)[:4])
+    torch.cuda.synchronize()
+    assert (y[:, :2 * C] == sentinel).all(), "the warp wrote outside its slot"
+    return y[:, 2 * C:].float().cpu().numpy().astype(np.float64).reshape(B, H, W, C), y
+
+
+def _x(B, H, W, C, x_cs, dtype, seed):
+    rows = synth.normal((B * H * W, x_cs), seed).to(dtype)
+    return rows, rows[:, :C].float().numpy().astype(np.float64).reshape(B, H, W, C)
+
+
+CASES = [(H, W, C, pad) for (H, W) in ((6, 5), (12, 9)) for C in (4, 68, 260) for pad in (0, 8)]
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_exact_maps_are_bit_exact_permutations(gpu, dtype):
+    checked = 0
+    for H, W, C, pad in CASES + [(8, 8, 68, 0), (8, 8, 260, 8)]:
+        for name in (("quarter",) if (H, W) == (8, 8) else ("identity_shift", "flip")):
+            ego = _maps(name, H, W)
+            rows, x = _x(2, H, W, C, C + pad, dtype, 3)
+            got, _ = _run_forward(rows.cuda(), ego, H, W, C, C + pad, dtype)
+            w = R.corners(ego, PCS[(H, W)], H, W)[2]
+            assert set(np.unique(w)) <= {0.0, 1.0}, (name, H, W)              # the case is what it claims: a permutation / copy
+            ref, _ = R.warp(x, ego, PCS[(H, W)])
+            assert np.array_equal(got, ref), (name, H, W, C, pad)
+            assert (ref == 0).all(-1).any() or name in ("flip", "quarter")     # the shift has zero-filled cells ...
+            assert (ref != 0).any()
+            if name == "identity_shift":
+                assert np.array_equal(got[0], x[0])                             # ... and frame 0 is a plain copy
+            checked += 1
+    assert checked == 26
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_translation_past_the_grid_writes_zero_rows_over_the_sentinel(gpu, dtype):
+    for H, W, C, pad in CASES:
+        rows, _ = _x(2, H, W, C, C + pad, dtype, 4)
+        got, y = _run_forward(rows.cuda(), _maps("far", H, W), H, W, C, C + pad, dtype)
+        assert (got == 0).all() and not (y[:, 2 * C:] == 777.0).any()
+    nan = np.eye(4)[None].repeat(2, 0)
+    nan[0, 0, 3], nan[1, 1, 1] = np.nan, np.inf                                   # a non-finite sample point: a zero row
+    got, _ = _run_forward(_x(2, 6, 5, 68, 68, dtype, 5)[0].cuda(), nan, 6, 5, 68, 68, dtype)
+    assert (got == 0).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+def test_general_map_within_the_derived_forward_bound(gpu, dtype):
+    """|y - ref| <= 8 * 2^-24 * max|corner| (four products of two roundings each -- the weight's and the product's -- and three
+    additions), plus 2^-8 |ref| for the bf16 output rounding; the reference sees the inputs as stored.  No element is left out."""
+    worst = 0.0
+    for H, W, C, pad in CASES:
+        ego = _maps("general", H, W)
+        rows, x = _x(2, H, W, C, C + pad, dtype, 6)
+        got, _ = _run_forward(rows.cuda(), ego, H, W, C, C + pad, dtype)
+        ref, vmax = R.warp(x, ego, PCS[(H, W)])
+        bound = 8 * EPS * vmax + (2.0 ** -8 * np.abs(ref) if dtype == torch.bfloat16 else 0.0)
+        inside = R.corners(ego, PCS[(H, W)], H, W)[3]
+        assert inside.all(0).any() and (~inside.any(0)).any() and (inside.any(0) & ~inside.all(0)).any()   # interior, outside, border
+        err = np.abs(got - ref)
+        assert err.shape == bound.shape and (err <= bound).all(), (H, W, C, pad, float((err / np.maximum(bound, 1e-300)).max()))
+        worst = max(worst, float((err[bound > 0] / bound[bound > 0]).max()))
+    print(f"bev_warp forward {dtype}: worst error / bound = {worst:.3f}")
+
+
+def _run_backward(dy_rows, ego, H, W, C, dy_cs, off):
+    B = ego.shape[0]
+    dx = torch.full((B * H * W * C,), 777.0, device="cuda")
+    L.bev_warp_bwd(dy_rows.view(-1)[off:], dx, torch.from_numpy(ego).cuda(), B, H, W, C, dy_cs, pillar_grid(PCS[(H, W)], H, W)[:4], ego)
+    torch.cuda.synchronize()
+    return dx
+
+
+_DY = {}
+
+
+def _dy(H, W, C):
+    """The backward's input, drawn once per shape: [B*H*W][3C] rows, the gradient in the last C columns."""
+    if (H, W, C) not in _DY:
+        _DY[(H, W, C)] = synth.normal((2 * H * W, 3 * C), 8)
+    return _DY[(H, W, C)]
+
+
+def test_backward_within_the_derived_bound_adjoint_and_deterministic(gpu):
+    """Per element |dx - ref| <= (n + 2) * 2^-24 * sum_k w_k |dy_k| with n the contributing targets of the cell (one rounding of
+    each weight, one per accumulation step); <warp(x), dy> = <x, warp_bwd(dy)> to 1e-5; two runs bit-identical."""
+    worst, worst_adj = 0.0, 0.0
+    for H, W, C, pad in CASES:
+        for name in ("general", "identity_shift", "flip"):
+            ego = _maps(name, H, W)
+            rows = _dy(H, W, C)
+            if pad:                                                        # the dense layout as well as the concat slice
+                dy_rows, dy_cs, off = rows[:, 2 * C:].contiguous(), C, 0
+            else:
+                dy_rows, dy_cs, off = rows, 3 * C, 2 * C
+            dy = rows[:, 2 * C:].numpy().astype(np.float64).reshape(2, H, W, C)
+            dx1 = _run_backward(dy_rows.cuda(), ego, H, W, C, dy_cs, off)
+            dx2 = _run_backward(dy_rows.cuda(), ego, H, W, C, dy_cs, off)
+            assert torch.equal(dx1, dx2)
+            got = dx1.cpu().numpy().astype(np.float64).reshape(2, H, W, C)
+            ref, mag, n = R.warp_bwd(dy, ego, PCS[(H, W)])
+            bound = (n[..., None] + 2) * EPS * mag
+            err = np.abs(got - ref)
+            assert (err <= bound).all(), (name, H, W, C, float((err / np.maximum(bound, 1e-300)).max()))
+            assert (got[n == 0] == 0).all()                               # every element is written, zeros included
+            if name == "general":
+                worst = max(worst, float((err[bound > 0] / bound[bound > 0]).max()))
+                xr, x = _x(2, H, W, C, C, torch.float32, 9)
+                y, _ = _run_forward(xr.cuda(), ego, H, W, C, C, torch.float32)
+                a, b = float((y * dy).sum()), float((x * got).sum())
+                assert abs(a - b) <= 1e-5 * max(abs(a), abs(b)), (a, b)
+                worst_adj = max(worst_adj, abs(a - b) / max(abs(a), abs(b)))
+    print(f"bev_warp backward: worst error / bound = {worst:.3f}, worst adjoint mismatch = {worst_adj:.2e}")
+
+
+def test_public_bev_warp_autograd_and_layouts(gpu):
+    H, W, C = 12, 9, 68
+    ego = _maps("general", H, W)
+    x = synth.normal((2, C, H, W), 10)
+    ref, _ = R.warp(x.permute(0, 2, 3, 1).numpy(), ego, PCS[(H, W)])
+    outs = []
+    for xin, e in ((x.cuda(), torch.from_numpy(ego)), (x.cuda().contiguous(memory_format=torch.channels_last), torch.from_numpy(ego).cuda())):
+        xin.requires_grad_(True)
+        y = temporal.bev_warp(xin, e, PCS[(H, W)])
+        assert y.shape == x.shape and y.is_contiguous(memory_format=torch.channels_last)
+        g = synth.normal((2, C, H, W), 11).cuda()
+        (y * g).sum().backward()
+        dref = R.warp_bwd(g.cpu().permute(0, 2, 3, 1).numpy(), ego, PCS[(H, W)])[0]
+        assert rel_err(y.detach().cpu().permute(0, 2, 3, 1), ref) <= 1e-6 and rel_err(xin.grad.cpu().permute(0, 2, 3, 1), dref) <= 1e-6
+        outs.append((y.detach(), xin.grad))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    yb = temporal.bev_warp(x.cuda().bfloat16(), ego, PCS[(H, W)])             # forward-only bf16
+    assert yb.dtype == torch.bfloat16 and rel_err(yb.float().cpu().permute(0, 2, 3, 1), ref) <= 2e-2
+
+
+def test_entry_points_refuse_what_they_cannot_address(gpu):
+    """B * H * W * stride past 2^31, C or a stride that is no multiple of 4: an error code and nothing launched (the C ABI itself;
+    the Python wrapper checks buffer sizes first)."""
+    lib = L.lib()
+    buf, ego = torch.zeros(64, device="cuda"), torch.zeros(16, dtype=torch.float64, device="cuda")
+    x, y, e, s = buf.data_ptr(), buf.data_ptr() + 128, ego.data_ptr(), torch.cuda.current_stream().cuda_stream
+    assert lib.bevf_bev_warp_f32(x, y, e, 1, 1 << 15, 1 << 15, 4, 4, 4, 0.0, 0.0, 1.0, 1.0, s) != 0
+    assert b"32-bit offsets" in lib.bevf_last_error()
+    assert lib.bevf_bev_warp_bwd_f32(x, y, e, 2, 1 << 14, 1 << 14, 4, 4, 0.0, 0.0, 1.0, 1.0, s) != 0
+    assert b"32-bit offsets" in lib.bevf_last_error()
+    assert lib.bevf_bev_warp_f32(x, y, e, 1, 2, 2, 6, 8, 8, 0.0, 0.0, 1.0, 1.0, s) != 0
+    assert lib.bevf_bev_warp_bf16(x, y, e, 1, 2, 2, 4, 6, 8, 0.0, 0.0, 1.0, 1.0, s) != 0
+    with pytest.raises(L.BevfError, match="multiples of 4"):
+        L.bev_warp(buf, buf.clone(), ego, 1, 2, 2, 4, 4, 6, (0.0, 0.0, 1.0, 1.0))
+    torch.cuda.synchronize()
+
+
+# ---- the fusion module with a history slot ------------------------------------------------------------------------------------------
+
+S, BC, PC = 12, 32, [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
+MTOL = 1e-4                                    # test_gpu_parity's model-level tolerance
+
+
+def _fusion_pair(seed=3):
+    ref = R.TemporalFusionRef(32, 32, S, S, BC, PC)
+    synth.fill_state_dict_(ref, seed)
+    mod = fusion.FlexibleBEVFusion(use_radar=False, camera_channels=32, lidar_channels=32, bev_h=S, bev_w=S, bev_channels=BC,
+                                   lidar_encoder_type="PointPillars", temporal=True)
+    mod.load_state_dict(ref.state_dict())
+    return ref.double(), mod.cuda()
+
+
+def _fusion_inputs():
+    cam, lid = synth.normal((2, 2, 32, 4, 6), 21).abs(), synth.normal((2, 32, S, S), 22).abs()
+    prev = synth.normal((2, BC, S, S), 23)
+    ego = np.stack([_general(9.0, 1.0, 11.0, -6.0), _general(-14.0, 1.0, -4.0, 17.0)])
+    return cam, lid, prev, ego
+
+
+_FREF = {}
+
+
+def _fusion_eval_reference():
+    """Computed once, shared, never modified."""
+    if "eval" not in _FREF:
+        ref, _ = _fusion_pair()
+        ref.eval()
+        cam, lid, prev, ego = _fusion_inputs()
+        with torch.no_grad():
+            _FREF["eval"] = (ref(cam.double(), lid.double(), prev.double(), ego).clone(), ref(cam.double(), lid.double()).clone())
+    return _FREF["eval"]
+
+
+def test_fusion_eval_against_the_fp64_composition(gpu):
+    _, mod = _fusion_pair()
+    mod.eval()
+    cam, lid, prev, ego = _fusion_inputs()
+    want, want_first = _fusion_eval_reference()
+    first = mod(cam.cuda(), lid.cuda())
+    out = mod(cam.cuda(), lid.cuda(), prev_bev=prev.cuda(), ego_motion=torch.from_numpy(ego))
+    e1, e0 = rel_err(out.cpu(), want), rel_err(first.cpu(), want_first)
+    print(f"temporal fusion eval: rel_err {e1:.3e} with history, {e0:.3e} first frame")
+    assert e1 <= MTOL and e0 <= MTOL
+    assert rel_err(want, want_first) > 1e-2                                  # the history really feeds the output
+    # None == explicit zeros, bit for bit; and nothing of the previous call's history is left in the reused concat buffer
+    zeros = mod(cam.cuda(), lid.cuda(), prev_bev=torch.zeros_like(prev).cuda(), ego_motion=torch.from_numpy(ego).cuda())
+    again = mod(cam.cuda(), lid.cuda())
+    assert torch.equal(zeros, first) and torch.equal(again, first)
+    cl = mod(cam.cuda(), lid.cuda(), prev_bev=prev.cuda().contiguous(memory_format=torch.channels_last), ego_motion=torch.from_numpy(ego).cuda())
+    assert torch.equal(cl, out)
+
+
+def _grad_check(named, ref_named, what, hard=2e-2, tight=2e-3, most=8):
+    """test_gpu_sparse_lidar._grad_metric restated: relative L2 per tensor against the reference gradients (plus a floor of 5e-5 of
+    the whole gradient norm), every tensor within `hard`, all but max(2, n / most) within `tight`."""
+    gref = dict(ref_named)
+    gn = float(torch.sqrt(sum((g.double() ** 2).sum() for g in gref.values())))
+    worst = []
+    for name, g in named:
+        r = gref[name].double().cpu()
+        worst.append((round(float((g.cpu().double() - r).norm() / (r.norm() + 5e-5 * gn)), 6), name))
+    worst.sort(reverse=True)
+    print(f"{what}: worst gradients {worst[:4]}")
+    assert worst and worst[0][0] <= hard, worst[:6]
+    loose = sum(w > tight for w, _ in worst)
+    assert loose <= max(2, len(worst) // most), (loose, worst[:6])
+    return worst
+
+
+@pytest.fixture
+def exact_convs():
+    """Conv mode "f32" (the exact kernel), as test_gpu_standalone_train: forward values within 1e-7 of the reference, so ReLU
+    decisions agree and the gradient comparison can be tight."""
+    old = engine.conv_mode()
+    engine.set_conv_mode("f32")
+    yield
+    engine.set_conv_mode(old)
+
+
+def test_fusion_train_gradients_against_fp64_autograd(gpu, exact_convs, monkeypatch):
+    ref, mod = _fusion_pair(seed=5)
+    ref.train(), mod.train()
+    cam, lid, prev, ego = _fusion_inputs()
+    w = synth.normal((2, BC, S, S), 24)
+    rin = [t.double().requires_grad_(True) for t in (cam, lid, prev)]
+    want = ref(rin[0], rin[1], rin[2], ego)
+    (want * w.double()).sum().backward()
+    gin = [t.cuda().requires_grad_(True) for t in (cam, lid, prev)]
+    out = mod(gin[0], gin[1], prev_bev=gin[2], ego_motion=torch.from_numpy(ego))
+    assert rel_err(out.detach().cpu(), want.detach()) <= MTOL
+    (out * w.cuda()).sum().backward()
+    _grad_check([(n, p.grad) for n, p in mod.named_parameters()], [(n, p.grad) for n, p in ref.named_parameters()], "temporal fusion parameters")
+    for (n, b), (_, rb) in zip(mod.named_buffers(), ref.named_buffers()):
+        assert rel_err(b.cpu().double(), rb.double()) <= 2e-5, n
+    names = ("camera", "lidar", "prev_bev")
+    _grad_check([(n, t.grad) for n, t in zip(names, gin)], [(n, t.grad) for n, t in zip(names, rin)], "temporal fusion inputs", most=1)
+    assert gin[2].grad.shape == prev.shape and gin[2].grad.abs().sum() > 0
+    # the backward kernel runs only when the caller wants the gradient of prev_bev
+    calls, real = [], L.bev_warp_bwd
+    monkeypatch.setattr(L, "bev_warp_bwd", lambda *a, **k: calls.append(1) or real(*a, **k))
+    mod(cam.cuda(), lid.cuda(), prev_bev=prev.cuda(), ego_motion=torch.from_numpy(ego)).sum().backward()
+    assert calls == []
+    mod(cam.cuda(), lid.cuda(), prev_bev=prev.cuda().requires_grad_(True), ego_motion=torch.from_numpy(ego)).sum().backward()
+    assert calls == [1]
+
+
+# ---- the detector -------------------------------------------------------------------------------------------------------------------
+
+def _config(temporal_on=True):
+    return {"model": {"camera_encoder": {"pretrained": False},
+                      "lidar_encoder": {"type": "PointPillars", "input_channels": 4, "pfn_channels": 32},
+                      "bev_fusion": {"bev_channels": 64, "temporal": {"enable": temporal_on}}},
+            "dataset": {"bev_h": S, "bev_w": S}}
+
+
+def _detector(temporal_on=True, seed=7):
+    m = fusion.create_detector("camera+lidar", "bev", "centernet", config=_config(temporal_on))
+    synth.fill_state_dict_(m, seed)
+    return m.cuda()
+
+
+def _frames(n, seed=40):
+    out = []
+    for t in range(n):
+        imgs, pts, _ = synth.frame_inputs(2, 1, 64, 96, 400, 4, seed=seed + t)
+        ego = np.stack([_general(3.0 + t, 1.0, 6.0, -2.0 * t), _general(-5.0, 1.0, -3.0 - t, 4.0)])
+        out.append((imgs.cuda(), pts.cuda(), torch.from_numpy(ego)))
+    return out
+
+
+def test_detector_train_step_equals_the_composition_of_module_tapes(gpu):
+    m = _detector().train()
+    assert m.fusion.temporal and m.fusion.bev_fusion[0].weight.shape[1] == 64 * 3
+    (imgs, pts, ego), = _frames(1)
+    prev = synth.normal((2, 64, S, S), 31).cuda()
+    out = m(imgs, pts, None, prev_bev=prev, ego_motion=ego)
+    assert set(out) == set(engine.HEAD_BRANCHES) | {"bev"}
+    bev = out["bev"]
+    assert bev.shape == (2, 64, S, S) and not bev.requires_grad and bev.is_contiguous(memory_format=torch.channels_last)
+    Gs = {k: synth.normal(tuple(out[k].shape), 50 + i).cuda() for i, k in enumerate(engine.HEAD_BRANCHES)}
+    loss = sum((out[k] * Gs[k]).sum() for k in Gs)
+    assert torch.isfinite(loss)
+    loss.backward()
+    got = [(n, p.grad.clone()) for n, p in m.named_parameters()]
+    assert all(torch.isfinite(g).all() for _, g in got)
+    m.zero_grad(set_to_none=True)
+    fused = m.fusion(m.camera_encoder(imgs), m.lidar_encoder(pts), None, prev_bev=prev, ego_motion=ego)
+    pred = m.det_head(fused)
+    sum((pred[k] * Gs[k]).sum() for k in Gs).backward()
+    assert rel_err(bev.cpu(), fused.detach().cpu()) <= 1e-6
+    for k in Gs:
+        assert rel_err(out[k].detach().cpu(), pred[k].detach().cpu()) <= 1e-6, k
+    # the same kernels on the same values, except where the detector fuses a BatchNorm backward into the layer after it:
+    # summation-order noise only, far inside the metric the fp64 comparisons use
+    _grad_check(got, [(n, p.grad) for n, p in m.named_parameters()], "detector vs module tapes", hard=2e-3, tight=2e-4)
+    with pytest.raises(L.BevfError, match="no gradient path"):
+        m(imgs, pts, None, prev_bev=prev.clone().requires_grad_(True), ego_motion=ego)
+
+
+def test_three_frames_eager_equal_graph_replay_bit_for_bit(gpu):
+    m = _detector().eval()
+    frames = _frames(3)
+    eager, prev = [], None
+    for imgs, pts, ego in frames:
+        out = m(imgs, pts, None, prev_bev=prev, ego_motion=None if prev is None else ego)
+        eager.append({k: v.clone() for k, v in out.items()})
+        prev = out["bev"]
+    assert not torch.equal(eager[1]["bev"], m(frames[1][0], frames[1][1], None)["bev"])      # the history matters
+    g = m.make_graphed(frames[0][0], frames[0][1], None)
+    prev = None
+    for t, (imgs, pts, ego) in enumerate(frames):
+        out = g(imgs, pts, None, prev_bev=prev, ego_motion=None if prev is None else ego)
+        for k, v in eager[t].items():
+            assert torch.equal(out[k], v), (t, k)
+        prev = out["bev"]                                                  # the static output itself: copied before the replay
+    first = g(frames[0][0], frames[0][1], None)                            # a new sequence after one with history: no leftover
+    assert all(torch.equal(first[k], v) for k, v in eager[0].items())
+
+
+def test_model_without_temporal_is_unchanged(gpu):
+    m = _detector(temporal_on=False).eval()
+    (imgs, pts, ego), = _frames(1)
+    out = m(imgs, pts, None)
+    assert set(out) == set(engine.HEAD_BRANCHES) and len(m.fusion._eng().branches) == 4 and m.fusion._eng().branches[3] is None
+    with pytest.raises(L.BevfError, match="temporal=True"):
+        m(imgs, pts, None, prev_bev=torch.zeros(2, 64, S, S, device="cuda"), ego_motion=ego)
+    m.train()
+    assert set(m(imgs, pts, None)) == set(engine.HEAD_BRANCHES)

@@ -269,6 +269,14 @@ SIGNATURES = {
     "bevf_bev_warp_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_void_p]),
     "bevf_bev_warp_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_void_p]),
     "bevf_bev_warp_bwd_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_float] * 4 + [C.c_void_p]),
+    # ---- BEV map-segmentation head: grid resample, focal loss, IoU counts ----
+    "bevf_bev_grid_resample_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 8 + [C.c_double] * 8 + [C.c_void_p]),
+    "bevf_bev_grid_resample_bf16": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 8 + [C.c_double] * 8 + [C.c_void_p]),
+    "bevf_bev_grid_resample_bwd_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_double] * 8 + [C.c_void_p]),
+    "bevf_seg_focal_work_doubles": (C.c_size_t, [C.c_int]),
+    "bevf_seg_focal_loss_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p] * 3),
+    "bevf_seg_focal_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p]),
+    "bevf_seg_iou_counts": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
 }
 
 
@@ -1720,3 +1728,79 @@ def bev_warp_bwd(dy, dx, ego, B: int, H: int, W: int, Cc: int, dy_cs: int, grid,
         raise BevfError(f"bev_warp_bwd: the ego-motion map must be finite with index-space singular values within [1/4, 4], got "
                         f"{sv.tolist()}")
     _call("bevf_bev_warp_bwd_f32", _p(dy), _p(dx), _pc(ego, torch.float64), B, H, W, Cc, dy_cs, *(float(v) for v in grid))
+
+
+# ---- BEV map-segmentation head: grid resample, focal loss, IoU counts (csrc/bev_seg.hip) ----
+
+def _grids(what: str, in_grid, out_grid):
+    g = tuple(float(v) for v in in_grid) + tuple(float(v) for v in out_grid)
+    if len(g) != 8 or any(g[k] == 0.0 for k in (2, 3, 6, 7)):
+        raise BevfError(f"{what}: grids are (x0, y0, vx, vy) with non-zero cell sizes, got {tuple(in_grid)} and {tuple(out_grid)}")
+    return g
+
+
+def bev_grid_resample(x, y, B: int, Hi: int, Wi: int, Ho: int, Wo: int, Cc: int, x_cs: int, y_cs: int, in_grid, out_grid) -> None:
+    """y [B][Ho][Wo] rows of Cc channels at stride y_cs, on out_grid = (ox0, oy0, ovx, ovy), = x [B][Hi][Wi] (stride x_cs) on
+    in_grid = (x0, y0, vx, vy) sampled bilinearly at the output cell centres (bevf_bev_grid_resample): zeros outside the input,
+    every output row written.  fp32 or bf16 storage; the geometry is fp64."""
+    g = _grids("bev_grid_resample", in_grid, out_grid)
+    if x.dtype != y.dtype:
+        raise BevfError(f"bev_grid_resample: x is {x.dtype}, y is {y.dtype}")
+    if x_cs < Cc or y_cs < Cc:
+        raise BevfError(f"bev_grid_resample: channel strides {x_cs}, {y_cs} below C = {Cc}")
+    _need("bev_grid_resample", x=(x, _strided(B * Hi * Wi, Cc, x_cs)), y=(y, _strided(B * Ho * Wo, Cc, y_cs)))
+    if x.untyped_storage().data_ptr() == y.untyped_storage().data_ptr():
+        raise BevfError("bev_grid_resample: x and y share storage")
+    _call("bevf_bev_grid_resample_" + _sfx(x), _p(x, x.dtype), _p(y, x.dtype), B, Hi, Wi, Ho, Wo, Cc, x_cs, y_cs, *g)
+
+
+def bev_grid_resample_bwd(dy, dx, B: int, Hi: int, Wi: int, Ho: int, Wo: int, Cc: int, dy_cs: int, in_grid, out_grid) -> None:
+    """dx [B][Hi][Wi][Cc] = the transpose of bev_grid_resample applied to dy [B][Ho][Wo] (stride dy_cs): a deterministic pull, every
+    element written (bevf_bev_grid_resample_bwd_f32, fp32)."""
+    g = _grids("bev_grid_resample_bwd", in_grid, out_grid)
+    if dy_cs < Cc:
+        raise BevfError(f"bev_grid_resample_bwd: channel stride {dy_cs} below C = {Cc}")
+    _need("bev_grid_resample_bwd", dy=(dy, _strided(B * Ho * Wo, Cc, dy_cs)), dx=(dx, B * Hi * Wi * Cc))
+    _call("bevf_bev_grid_resample_bwd_f32", _p(dy), _pc(dx), B, Hi, Wi, Ho, Wo, Cc, dy_cs, *g)
+
+
+def seg_focal_work_doubles(K: int) -> int:
+    """fp64 elements of seg_focal_loss's partials buffer for K classes."""
+    return int(lib().bevf_seg_focal_work_doubles(K))
+
+
+def _seg_shape(what: str, B: int, P: int, K: int, cs: int) -> None:
+    if not (B > 0 and P > 0 and 0 < K <= 64 and cs >= K):
+        raise BevfError(f"{what}: bad shape B = {B}, P = {P}, K = {K}, row stride {cs} (1 <= K <= 64 <= stride)")
+
+
+def seg_focal_loss(logits, cs: int, targets, B: int, P: int, K: int, alpha: float, gamma: float, partials, out) -> None:
+    """out[k] = the mean over the B * P pixels of the sigmoid focal loss of class k, out[K] = their sum (bevf_seg_focal_loss_f32).
+    logits fp32 rows of K classes at stride cs, targets uint8 [B][K][P], partials fp64 [seg_focal_work_doubles(K)], out fp32 [K + 1];
+    alpha < 0: no alpha weighting."""
+    _seg_shape("seg_focal_loss", B, P, K, cs)
+    _need("seg_focal_loss", logits=(logits, _strided(B * P, K, cs)), targets=(targets, B * K * P),
+          partials=(partials, seg_focal_work_doubles(K)), out=(out, K + 1))
+    _call("bevf_seg_focal_loss_f32", _p(logits), cs, _pc(targets, torch.uint8), B, P, K, float(alpha), float(gamma),
+          _pc(partials, torch.float64), _pc(out))
+
+
+def seg_focal_loss_bwd(logits, cs: int, targets, g, dlogit, B: int, P: int, K: int, alpha: float, gamma: float) -> None:
+    """dlogit rows (stride cs, all cs columns written, zeros from K on) = g[0] * d out[K] / d logits (bevf_seg_focal_loss_bwd_f32);
+    g: one fp32 on the device."""
+    _seg_shape("seg_focal_loss_bwd", B, P, K, cs)
+    _need("seg_focal_loss_bwd", logits=(logits, _strided(B * P, K, cs)), targets=(targets, B * K * P), g=(g, 1),
+          dlogit=(dlogit, B * P * cs))
+    _call("bevf_seg_focal_loss_bwd_f32", _p(logits), cs, _pc(targets, torch.uint8), _pc(g), _p(dlogit), B, P, K, float(alpha),
+          float(gamma))
+
+
+def seg_iou_counts(logits, cs: int, targets, thr, counts, B: int, P: int, K: int) -> None:
+    """counts int64 [T][K][3] = (TP, FP, FN) of logits[r][k] >= thr[t] against targets uint8 [B][K][P] (bevf_seg_iou_counts);
+    thr: T <= 32 fp32 logit thresholds on the device."""
+    _seg_shape("seg_iou_counts", B, P, K, cs)
+    T = thr.numel()
+    if not 0 < T <= 32:
+        raise BevfError(f"seg_iou_counts: {T} thresholds (1 .. 32)")
+    _need("seg_iou_counts", logits=(logits, _strided(B * P, K, cs)), targets=(targets, B * K * P), counts=(counts, T * K * 3))
+    _call("bevf_seg_iou_counts", _p(logits), cs, _pc(targets, torch.uint8), _pc(thr), T, _pc(counts, torch.int64), B, P, K)

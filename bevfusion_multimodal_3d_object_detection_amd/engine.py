@@ -1242,6 +1242,45 @@ class HeadEngine(_Engine):
         return dict(zip(HEAD_BRANCHES, outs))
 
 
+# ---- BEV map-segmentation head (seg_head.BEVSegmentationHead) ---------------------------------------------
+
+class SegHeadEngine(_Engine):
+    """Eval mode: the grid resample onto the map grid, the classifier's two conv3x3 + folded BN + ReLU, and its 1x1 layer padded
+    with zero rows to depth_net_width (pad_depth_net: the width the convolution kernels take for any class count), then the
+    NHWC -> NCHW copy of the first num_classes columns.  fp32 or bf16 storage; the logits come out fp32."""
+
+    def pack(self) -> None:
+        cl = self.module.classifier
+        self.c1 = pack_conv(cl[0], cl[1], True)
+        self.c2 = pack_conv(cl[3], cl[4], True)
+        self.Kp = depth_net_width(self.module.num_classes)
+        w, b = pad_depth_net(cl[6], self.Kp)
+        self.c3 = _finish_pack(w.permute(0, 2, 3, 1).contiguous().view(-1), torch.ones(self.Kp, device=w.device), b, w.shape[1],
+                               self.Kp, 1, 1, 0, False, split_ok=False, wino_ok=False)
+
+    def run(self, bev_nhwc: torch.Tensor, B: int) -> torch.Tensor:
+        """bev_nhwc: the flat NHWC map [B][bev_h][bev_w][in_channels] in the storage dtype -> logits (B, K, Ho, Wo) fp32."""
+        self.ensure_packed()
+        m = self.module
+        (Ho, Wo), Cc, K = m.output_size, m.in_channels, m.num_classes
+        P = Ho * Wo
+        if bev_nhwc.dtype != self.dtype or bev_nhwc.numel() < B * m.bev_h * m.bev_w * Cc:
+            raise L.BevfError(f"BEVSegmentationHead: expected a {self.dtype} NHWC map of {B} x {m.bev_h} x {m.bev_w} x {Cc} elements, "
+                              f"got {bev_nhwc.dtype} x {bev_nhwc.numel()}")
+        r = self.buf("seg_in", B * P * Cc)
+        with _span("bev_grid_resample", nbytes=float(r.element_size()) * B * Cc * (m.bev_h * m.bev_w + P)):
+            L.bev_grid_resample(bev_nhwc, r, B, m.bev_h, m.bev_w, Ho, Wo, Cc, Cc, Cc, m.in_grid, m.out_grid)
+        a1 = self.buf("seg_1", B * P * self.c1.cout)
+        _run_conv(self.c1, r, a1, B, Ho, Wo)
+        a2 = self.buf("seg_2", B * P * self.c2.cout)
+        _run_conv(self.c2, a1, a2, B, Ho, Wo)
+        logits = self.buf("seg_logits", B * P * self.Kp)
+        _run_conv(self.c3, a2, logits, B, Ho, Wo)
+        out = torch.empty(B, K, Ho, Wo, device=bev_nhwc.device)
+        L.nhwc_to_nchw(logits.float(), out, B, K, P, self.Kp)
+        return out
+
+
 # ---- layout helpers at the API surface ----------------------------------------------------------------------
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import engine as E
 from . import camera_rig as CR
+from . import seg_head as SH
 from . import temporal as T
 from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, SparseLiDAREncoder,  # noqa: F401
                        _cfg, lidar_encoder_kind, load_config)
@@ -376,7 +377,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  fusion_type: Optional[str] = None, detection_head: Optional[str] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
-                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None):
+                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None, seg_head=None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -440,6 +441,13 @@ class FlexibleMultiModal3DDetector(nn.Module):
             self.det_head = CenterNetHead(in_channels=self.fusion.bev_channels, num_classes=num_classes, config=config)
         else:
             self.det_head = MLPDetectionHead()
+        # opt-in second task on the fused map: seg_head=True / dict, or model.seg_head.enable; adds the keys
+        # seg_head.classifier.* and the 'seg' output, nothing else
+        self.seg_head = None
+        seg = SH.seg_head_settings(seg_head, config)
+        if seg is not None:
+            self.seg_head = SH.BEVSegmentationHead(in_channels=self.fusion.bev_channels, pc_range=self.fusion.pc_range,
+                                                   bev_h=self.fusion.bev_h, bev_w=self.fusion.bev_w, **seg)
 
     def camera_calib_tensor(self, camera_imgs, camera_calib):
         """`camera_calib=` of forward checked against the camera input (FlexibleBEVFusion.camera_calib_tensor); None without
@@ -484,6 +492,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
         current -> previous frame map of temporal.ego_motion (host or device); prev_bev None = the first frame of a sequence.  A model
         with temporal fusion returns 'bev' as well: an owned (B, bev_channels, H, W) channels-last copy of the fused map (detached in
         train mode, where the history is a constant), to hand back as prev_bev for the next frame.
+        A model built with seg_head= returns 'seg' as well, in eval and train mode: the map-segmentation logits
+        (B, num_classes, Ho, Wo) in fp32 of seg_head.BEVSegmentationHead on the fused map.
         camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame.
@@ -543,13 +553,16 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        if history is None:
+        if history is None and self.seg_head is None:
             fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
             return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
         fus = self.fusion
         fused, B = fus.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None, history)
         out = self.det_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
-        out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
+        if self.seg_head is not None:                                   # the fused map's second consumer
+            out["seg"] = self.seg_head.forward_nhwc(fused, B)
+        if history is not None:
+            out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
         return out
 
     def get_config_str(self) -> str:
@@ -657,16 +670,20 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
                     lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
-                    temporal: Optional[bool] = None, **kwargs) -> FlexibleMultiModal3DDetector:
+                    temporal: Optional[bool] = None, seg_head=None, **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
     camera_view_transform: 'project' selects the camera -> BEV projection branch, 'lift' its learned-depth variant, 'frustum' the
     lift-splat branch, 'mean' the reference's camera average (None: the config's model.bev_fusion.camera_view_transform, else
     'mean').
-    temporal: True adds the history slot of temporal BEV fusion (None: the config's model.bev_fusion.temporal.enable, else off)."""
+    temporal: True adds the history slot of temporal BEV fusion (None: the config's model.bev_fusion.temporal.enable, else off).
+    seg_head: True, or a dict of {num_classes | classes, output_range, output_size, hidden_channels}, adds the BEV map-segmentation
+    head (seg_head.BEVSegmentationHead) on the fused map and the 'seg' output (None: the config's model.seg_head.enable, else off)."""
     if temporal is not None:
         kwargs["temporal"] = temporal
+    if seg_head is not None:
+        kwargs["seg_head"] = seg_head
     config = _cfg(config, config_path)
     if config is not None and modality_config is None:
         modality_config = config.get("model", {}).get("modality_config", "all")

@@ -1511,12 +1511,52 @@ class HeadTape:
         return conv_dgrad(dhid, hw.w3, B, H, W, cin, c5, 3, 1, 1), None
 
 
+class SegHeadTape:
+    """BEVSegmentationHead (seg_head.py) on an NHWC map [B*H*W*Cin]: the grid resample onto the map grid, the
+    classifier's two conv + BN + ReLU, and its 1x1 layer padded to engine.depth_net_width (_PaddedDepthNet: the data gradient reads
+    the layer's output channels as its Cin) -> logits (B, K, Ho, Wo).  The backward ends in the resample's pull kernel."""
+
+    def __init__(self, head):
+        self.head = head
+
+    def forward(self, x, B):
+        h = self.head
+        (Ho, Wo), Cc, K = h.output_size, h.in_channels, h.num_classes
+        self.B, self.Kp = B, E.depth_net_width(K)
+        r = _new(B * Ho * Wo * Cc, x.device)
+        L.bev_grid_resample(x, r, B, h.bev_h, h.bev_w, Ho, Wo, Cc, Cc, Cc, h.in_grid, h.out_grid)
+        cl = h.classifier
+        self.c1, self.c2 = ConvBNLayer(cl[0], cl[1], True), ConvBNLayer(cl[3], cl[4], True)
+        self.padded = _PaddedDepthNet(cl[6], self.Kp)
+        self.c3 = ConvBNLayer(self.padded, None, relu=False)
+        a1, _, _ = self.c1.forward(r, B, Ho, Wo)
+        a2, _, _ = self.c2.forward(a1, B, Ho, Wo)
+        logits, _, _ = self.c3.forward(a2, B, Ho, Wo)
+        out = torch.empty(B, K, Ho, Wo, device=x.device)
+        L.nhwc_to_nchw(logits, out, B, K, Ho * Wo, self.Kp)
+        return out
+
+    def backward(self, dout, sink: GradSink):
+        """dout (B, K, Ho, Wo) -> the gradient of the input NHWC map."""
+        h, B = self.head, self.B
+        (Ho, Wo), Cc, K = h.output_size, h.in_channels, h.num_classes
+        dlogit = torch.zeros(B * Ho * Wo * self.Kp, device=dout.device)         # the padding columns carry no gradient
+        L.nchw_to_nhwc(dout.contiguous().float(), dlogit, B, K, Ho * Wo, self.Kp)
+        da2, _ = self.c3.backward(dlogit, self.padded.sink(sink))
+        da1, _ = self.c2.backward(da2, sink)
+        dr, _ = self.c1.backward(da1, sink)
+        dx = _new(B * h.bev_h * h.bev_w * Cc, dout.device)
+        L.bev_grid_resample_bwd(dr, dx, B, h.bev_h, h.bev_w, Ho, Wo, Cc, Cc, h.in_grid, h.out_grid)
+        return dx
+
+
 # ---- the detector ------------------------------------------------------------------------------------------------------------------
 
 class DetectorTape:
     """FlexibleMultiModal3DDetector (bev + centernet) as a composition of module tapes: the encoders of the modalities present, in
     the order radar, camera, LiDAR (RELU_TRACE follows it), then fusion and head.  The backward walks them in reverse and marks
-    where gradients become final for the data-parallel all-reduce (sink.ready())."""
+    where gradients become final for the data-parallel all-reduce (sink.ready()).  A model with a seg head has
+    two consumers of the fused map: SegHeadTape runs after the head, and the backward sums the two gradients before the fusion."""
 
     def __init__(self, model, camera_calib=None, depth_sup=None, history=None):
         self.m = model
@@ -1563,15 +1603,26 @@ class DetectorTape:
             self.bev = (fused, B)                 # the 'bev' output is copied from it (detector_train_forward)
         self.head = HeadTape(m.det_head)
         outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
-        if self.depth_sup is None:
-            return outs
-        self.depth_out = self.fusion.branches[0].depth.out
-        return outs + [self.depth_out[0]]
+        if self.depth_sup is not None:
+            self.depth_out = self.fusion.branches[0].depth.out
+            outs = outs + [self.depth_out[0]]
+        self.seg = None
+        if getattr(m, "seg_head", None) is not None:  # the fused map's second consumer; 'seg' is appended: the positions above stay
+            self.seg = SegHeadTape(m.seg_head)
+            outs = outs + [self.seg.forward(fused, B)]
+        return outs
 
     def backward(self, douts: List[torch.Tensor], sink: GradSink) -> list:
         if self.depth_sup is not None:
             self.fusion.branches[0].depth_grad = douts[5]
-        dfused, pre_f2 = self.head.backward(douts[:5], sink, fuse_next=self.fusion.f2)
+        if self.seg is None:
+            dfused, pre_f2 = self.head.backward(douts[:5], sink, fuse_next=self.fusion.f2)
+        else:
+            # two consumers of `fused`: the head's fused BatchNorm-backward partials would cover its own share only, so the head
+            # returns a plain data gradient, the seg head's is added, and f2 runs its own BatchNorm backward over the sum
+            dfused, pre_f2 = self.head.backward(douts[:5], sink)
+            if douts[-1] is not None:
+                add_(dfused, self.seg.backward(douts[-1], sink), self.fusion.B * self.fusion.H * self.fusion.W * self.fusion.cout)
 
         def camera(dfeat):
             sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
@@ -1668,6 +1719,8 @@ def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_su
     res = dict(zip(E.HEAD_BRANCHES, outs))
     if depth_sup is not None:
         res["depth_loss"], res["depth_pixels"] = outs[5], tape.depth_out[1].clone()
+    if tape.seg is not None:
+        res["seg"] = outs[-1]
     if history is not None:
         from .temporal import own_bev
         fus = model.fusion
@@ -1884,6 +1937,22 @@ def head_train_forward(head, x: torch.Tensor) -> Dict[str, torch.Tensor]:
 
     outs = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
     return dict(zip(E.HEAD_BRANCHES, outs))
+
+
+def seg_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:
+    """BEVSegmentationHead.forward under train-mode BatchNorm -> logits (B, K, Ho, Wo), with gradients for the parameters and for
+    the BEV map `x` (B, C, H, W)."""
+    B, Cin, H, W = x.shape
+    tape = SegHeadTape(head)
+
+    def fwd(x):
+        return (tape.forward(_nhwc(x.detach()), B),)
+
+    def bwd(douts, sink):
+        return [E.to_nchw(tape.backward(douts[0], sink), B, Cin, H, W)]
+
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
+    return out
 
 
 

@@ -956,6 +956,45 @@ int bevf_bev_warp_bf16(const void* x, void* y, const double* ego, int B, int H, 
 int bevf_bev_warp_bwd_f32(const float* dy, float* dx, const double* ego, int B, int H, int W, int C, int dy_cs, float x0, float y0,
                           float vx, float vy, void* stream);
 
+/* ==========================================================================================
+ * BEV map-segmentation head (csrc/bev_seg.hip).
+ * ========================================================================================== */
+
+/* y[b][i][j][0:C] (row stride y_cs), a map [B][Ho][Wo] on the grid (ox0, oy0, ovx, ovy), = x [B][Hi][Wi] rows of C channels (row
+ * stride x_cs) on the grid (x0, y0, vx, vy), sampled bilinearly at the output cell's centre; row i is y, column j is x.  All in fp64:
+ *   xo = ox0 + (j + 0.5) ovx, qj = (xo - x0) / vx - 0.5, j0 = floor(qj), fj = qj - j0;  the same along y for qi, i0, fi
+ * weights (1-fi)(1-fj), (1-fi)fj, fi(1-fj), fi fj, each rounded once to fp32; a corner outside [0,Hi) x [0,Wi) contributes zero
+ * (grid_sample, padding_mode='zeros', align_corners=False), a non-finite q gives a zero row; the sum is fp32 in the corner order
+ * (i0,j0), (i0,j0+1), (i0+1,j0), (i0+1,j0+1).  bf16 storage computes in fp32.  Every element of the B * Ho * Wo output rows' C
+ * channels is written and nothing else.  Any C and strides >= C: 16-byte accesses where bases and strides are multiples of 16
+ * bytes, a scalar tail for the rest.  B * Hi * Wi and B * Ho * Wo below 2^31.                                                     */
+int bevf_bev_grid_resample_f32(const float* x, float* y, int B, int Hi, int Wi, int Ho, int Wo, int C, int x_cs, int y_cs, double x0,
+                               double y0, double vx, double vy, double ox0, double oy0, double ovx, double ovy, void* stream);
+int bevf_bev_grid_resample_bf16(const void* x, void* y, int B, int Hi, int Wi, int Ho, int Wo, int C, int x_cs, int y_cs, double x0,
+                                double y0, double vx, double vy, double ox0, double oy0, double ovx, double ovy, void* stream);
+/* The transpose: dx [B][Hi][Wi][C] (dense) from dy [B][Ho][Wo] rows at stride dy_cs.  A pull without atomics: source cell (r, c)
+ * sums w * dy over the output rows and columns whose sample has it as a neighbour -- contiguous index ranges, from the inverse of
+ * the scalar map -- in row-major target order, the weight recomputed by the forward's own expression.  Every element of dx is
+ * written; bit-reproducible.                                                                                                      */
+int bevf_bev_grid_resample_bwd_f32(const float* dy, float* dx, int B, int Hi, int Wi, int Ho, int Wo, int C, int dy_cs, double x0,
+                                   double y0, double vx, double vy, double ox0, double oy0, double ovx, double ovy, void* stream);
+
+/* Sigmoid focal loss on logits.  logits: B * P rows of K classes at row stride cs (NHWC); targets uint8 [B][K][P], non-zero = 1.
+ * With p = sigmoid(x), p_t = t p + (1 - t)(1 - p), BCE = max(x, 0) - x t + log1p(exp(-|x|)), a_t = alpha t + (1 - alpha)(1 - t) for
+ * alpha >= 0 and 1 for alpha < 0:  out[k] = (1 / (B P)) sum a_t (1 - p_t)^gamma BCE over class k, out[K] = sum_k out[k].
+ * Elements in fp32, sums in fp64: `partials` (bevf_seg_focal_work_doubles(K) doubles) takes fixed-grid partial sums, a second
+ * launch adds them in a fixed order.  K <= 64, gamma >= 0.                                                                       */
+size_t bevf_seg_focal_work_doubles(int K);
+int bevf_seg_focal_loss_f32(const float* logits, int cs, const uint8_t* targets, int B, int P, int K, float alpha, float gamma,
+                            double* partials, float* out, void* stream);
+/* dlogit[r][k] (row stride cs) = g[0] * d out[K] / d logits[r][k] for k < K, 0 for K <= k < cs; g: one fp32 on the DEVICE.       */
+int bevf_seg_focal_loss_bwd_f32(const float* logits, int cs, const uint8_t* targets, const float* g, float* dlogit, int B, int P,
+                                int K, float alpha, float gamma, void* stream);
+/* counts int64 [T][K][3] = (TP, FP, FN) over the B * P pixels with the prediction logits[r][k] >= thr[t] (thr: T fp32 on the
+ * device, T <= 32) against targets as above.  Integer sums: deterministic.                                                      */
+int bevf_seg_iou_counts(const float* logits, int cs, const uint8_t* targets, const float* thr, int T, int64_t* counts, int B, int P,
+                        int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

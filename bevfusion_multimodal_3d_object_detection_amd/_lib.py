@@ -277,6 +277,10 @@ SIGNATURES = {
     "bevf_seg_focal_loss_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p] * 3),
     "bevf_seg_focal_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] * 2 + [C.c_void_p]),
     "bevf_seg_iou_counts": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    # ---- segmentation targets rasterised from map polygons and polylines ----
+    "bevf_map_raster_work_bytes": (C.c_size_t, [C.c_int] * 2),
+    "bevf_map_raster_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int]
+                           + [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_double] * 4 + [C.c_void_p] * 3),
 }
 
 
@@ -1804,3 +1808,31 @@ def seg_iou_counts(logits, cs: int, targets, thr, counts, B: int, P: int, K: int
         raise BevfError(f"seg_iou_counts: {T} thresholds (1 .. 32)")
     _need("seg_iou_counts", logits=(logits, _strided(B * P, K, cs)), targets=(targets, B * K * P), counts=(counts, T * K * 3))
     _call("bevf_seg_iou_counts", _p(logits), cs, _pc(targets, torch.uint8), _pc(thr), T, _pc(counts, torch.int64), B, P, K)
+
+
+# ---- segmentation targets rasterised from map polygons and polylines (csrc/map_raster.hip) ----
+
+def map_raster_work_bytes(S: int, V: int) -> int:
+    """Bytes of map_raster's workspace for S shapes with V vertices in all."""
+    return int(lib().bevf_map_raster_work_bytes(S, V))
+
+
+def map_raster(vertices, ring_offsets, shape_offsets, shape_class, shape_kind, shape_width, frame_offsets, mat, scale, work, out,
+               B: int, K: int, Ho: int, Wo: int, grid) -> None:
+    """out uint8 [B][K][Ho][Wo] = the class masks of the packed shapes (bevf_map_raster_u8; the rules: include/bevf.h) on
+    grid = (x0, y0, vx, vy) of seg_head.range_grid.  vertices fp32 [V][2], ring_offsets int32 [R + 1], shape_offsets int32 [S + 1],
+    shape_class / shape_kind int32 [S], shape_width fp32 [S], frame_offsets int32 [B + 1]; mat fp32 [B][12] or None (identity), scale
+    fp32 [B] or None (1); work: uint8 [map_raster_work_bytes(S, V)].  Every byte of out is written."""
+    I32, U8 = torch.int32, torch.uint8
+    S, V, R = shape_class.numel(), vertices.numel() // 2, ring_offsets.numel() - 1
+    if not (B > 0 and Ho > 0 and Wo > 0 and 1 <= K <= 64):
+        raise BevfError(f"map_raster: bad shape B = {B}, K = {K}, Ho = {Ho}, Wo = {Wo} (1 <= K <= 64)")
+    g = tuple(float(v) for v in grid)
+    if len(g) != 4:
+        raise BevfError(f"map_raster: the grid is (x0, y0, vx, vy), got {tuple(grid)}")
+    _need("map_raster", vertices=(vertices, 2 * V), ring_offsets=(ring_offsets, 1), shape_offsets=(shape_offsets, S + 1),
+          shape_class=(shape_class, S), shape_kind=(shape_kind, S), shape_width=(shape_width, S), frame_offsets=(frame_offsets, B + 1), mat=(mat, B * 12),
+          scale=(scale, B), work=(work, map_raster_work_bytes(S, V)), out=(out, B * K * Ho * Wo))
+    _call("bevf_map_raster_u8", _pc(vertices), V, _pc(ring_offsets, I32), R, _pc(shape_offsets, I32), _pc(shape_class, I32),
+          _pc(shape_kind, I32), _pc(shape_width), S, _pc(frame_offsets, I32), B, _pc(mat), _pc(scale), K, Ho, Wo, *g,
+          _pc(work, U8), _pc(out, U8))

@@ -18,7 +18,8 @@ This module reads that section and applies the BEVFusion-style pair -- one world
 
 Random numbers are drawn on the host from a `numpy.random.Generator` (a few dozen scalars per step); the radar noise is `torch.randn`
 on the device.  `augment_batch(..., paste=, bank=)` runs the GT-paste of `gt_paste.py` in front of the world
-transform.  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' and 'frustum' camera branches.  No
+transform; `augment_batch(..., map_shapes=, map_grid=)` rasterises the map's polygons and polylines into the segmentation head's
+target masks after the world transform (`map_targets.py`).  `augmented_calib` returns the matching `camera_calib=` tensor of the 'project' and 'frustum' camera branches.  No
 CPU fallback.
 """
 from __future__ import annotations
@@ -460,7 +461,7 @@ def augment_batch(frames_u8: Optional[torch.Tensor], lidar: Optional[torch.Tenso
                   gt_velocities: Optional[torch.Tensor], params: AugmentParams, settings: AugmentSettings, base_calib=None,
                   max_points: int = 35000, pc_range: Sequence[float] = PC_RANGE, lidar_vel_ch: Optional[Sequence[int]] = None,
                   radar_vel_ch: Optional[Sequence[int]] = None, generator: Optional[torch.Generator] = None,
-                  image_size: Optional[Tuple[int, int]] = None, *, paste=None, bank=None) -> Dict:
+                  image_size: Optional[Tuple[int, int]] = None, *, paste=None, bank=None, map_shapes=None, map_grid=None) -> Dict:
     """One augmented training batch, everything on the device:
 
     frames_u8 (B, ncam, Hs, Ws, 3) uint8; lidar (B, N, C) fp32 with lidar_counts (B,) valid points per frame (None = N); radar: a
@@ -473,10 +474,16 @@ def augment_batch(frames_u8: Optional[torch.Tensor], lidar: Optional[torch.Tenso
     the GT-paste of `gt_paste.paste` first, before the world transform (ObjectSample, then GlobalRotScaleTrans): lidar, gt_boxes and
     gt_labels are then required, the paste's outputs take their place (Kc more GT rows per frame), and the result gains
     paste_accepted int32 (B, Kc).  With a camera branch the pasted objects are NOT drawn into the images, as in BEVFusion's own
-    recipe.  Without the two arguments the function takes exactly the path it takes without them."""
+    recipe.  Without the two arguments the function takes exactly the path it takes without them.
+
+    map_shapes= (a `map_targets.MapShapes`) and map_grid= (a `BEVSegmentationHead`, or (output_range, output_size)), given together,
+    add seg_targets uint8 (B, K, Ho, Wo): the map's polygons and polylines moved through the step's T and rasterised after it
+    (`map_targets.rasterize`), the masks `SegFocalLoss` takes.  Without the two arguments the result has no such key."""
     accepted = None
     if (paste is None) != (bank is None):
         raise L.BevfError("augment_batch: paste= and bank= go together")
+    if (map_shapes is None) != (map_grid is None):
+        raise L.BevfError("augment_batch: map_shapes= and map_grid= go together")
     if paste is not None and paste.Kc > 0:
         if lidar is None or gt_boxes is None or gt_labels is None:
             raise L.BevfError("augment_batch: paste= needs lidar, gt_boxes and gt_labels")
@@ -502,4 +509,14 @@ def augment_batch(frames_u8: Optional[torch.Tensor], lidar: Optional[torch.Tenso
         out["camera_calib"] = augmented_calib(base_calib, params, image_size)
     if accepted is not None:
         out["paste_accepted"] = accepted
+    if map_shapes is not None:
+        from . import map_targets
+        if isinstance(map_grid, torch.nn.Module):
+            out["seg_targets"] = map_targets.rasterize_for(map_grid, map_shapes, params)
+        else:
+            try:
+                rng, size = map_grid
+            except (TypeError, ValueError):
+                raise L.BevfError("augment_batch: map_grid= is a BEVSegmentationHead or (output_range, output_size)") from None
+            out["seg_targets"] = map_targets.rasterize(map_shapes, rng, size, params)
     return out

@@ -995,6 +995,33 @@ int bevf_seg_focal_loss_bwd_f32(const float* logits, int cs, const uint8_t* targ
 int bevf_seg_iou_counts(const float* logits, int cs, const uint8_t* targets, const float* thr, int T, int64_t* counts, int B, int P,
                         int K, void* stream);
 
+/* ==========================================================================================
+ * Map polygons and polylines rasterised into segmentation targets (csrc/map_raster.hip).
+ * ========================================================================================== */
+
+/* out uint8 [B][K][Ho][Wo] = 1 where a shape of frame b with class k contains (polygon) or hits (polyline) the centre of cell
+ * (row i = y, column j = x), px = x0 + (j + 0.5) vx, py = y0 + (i + 0.5) vy, else 0: the union over the frame's shapes.  The shapes of
+ * the whole batch are one CSR set on the DEVICE: vertices fp32 [V][2] in metres, ring_offsets [R + 1] into vertices, shape_offsets
+ * [S + 1] into rings, shape_class [S] in 0 .. K-1, shape_kind [S] (0 = polygon: ring 0 the exterior, further rings holes; 1 =
+ * polyline: exactly one open ring), shape_width fp32 [S] (a polyline's full width in metres), frame_offsets [B + 1] into shapes.
+ * mat: fp32 [B][12], rows 0-2 of the frame's world transform, or NULL = identity; scale: fp32 [B], or NULL = 1.  All in fp64, no
+ * contraction, transformed vertices never rounded to fp32:
+ *   vertex   x' = (m00 x + m01 y) + m03, y' = (m10 x + m11 y) + m13;  half width hw = 0.5 width scale[b]
+ *   polygon  inside = odd number of crossed edges over ALL rings (even-odd).  An edge with equal endpoint y is skipped; otherwise a =
+ *            the endpoint with the smaller y, and the edge is crossed when a.y <= py < b.y and
+ *            (b.x - a.x) (py - a.y) - (px - a.x) (b.y - a.y) > 0
+ *   polyline segment a -> b: e = b - a, u = p - a, w = p - b, t = u.e, l2 = e.e, c = e.x u.y - e.y u.x (dot products x x' + y y');
+ *            t <= 0: hit when u.u <= hw^2;  else t >= l2: hit when w.w <= hw^2;  else hit when c c <= hw^2 l2
+ * A shape with a non-finite transformed vertex, a ring below 3 vertices (polygon) or 2 (polyline), or an offset or class outside its
+ * array contributes nothing (checked on the device; nothing is read out of bounds).  Every byte of out is written; no atomics; two
+ * launches on `stream`.  1 <= K <= 64; S = 0 (then the shape arrays may be NULL) writes zeros.  work:
+ * bevf_map_raster_work_bytes(S, V) bytes, 16-byte aligned (one 64-byte record per shape, one 32-byte fp64 edge per vertex).      */
+size_t bevf_map_raster_work_bytes(int S, int V);
+int bevf_map_raster_u8(const float* vertices, int V, const int32_t* ring_offsets, int R, const int32_t* shape_offsets,
+                       const int32_t* shape_class, const int32_t* shape_kind, const float* shape_width, int S,
+                       const int32_t* frame_offsets, int B, const float* mat, const float* scale, int K, int Ho, int Wo, double x0,
+                       double y0, double vx, double vy, void* work, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

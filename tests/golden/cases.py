@@ -212,3 +212,198 @@ def draw_gaussian_canvas(c):
 
 
 CONFIG1_CASE = dict(h=448, w=800, bev=128, stride=4, seed=901)
+
+
+# ---- CenterNet target / loss / decode kernels at their edge shapes (tests/centernet_ref.py, test_*centernet_kernels*) -----------
+# Decode cases.  `kind` names the score map, `masked` the 3x3 keep mask (False = the raw top-K path).  `ties` names the cuts ("class": the
+# per-class top-K, "pool": the top-K of the C*K pool) at which scores equal to the K-th are left out; () = tie-free (asserted on the host); `fixture`: the drop-in functions are
+# also compared with decode_{ct,fd}_<name>.npz minted from the imported reference.
+CN_DECODE_CASES = [
+    dict(name="base", B=2, C=10, H=50, W=50, K=100, kind="cont", masked=True, thresh=0.3, seed=1101, ties=(), fixture=True),
+    dict(name="one", B=1, C=1, H=1, W=1, K=1, kind="cont", masked=True, thresh=0.3, seed=1102, ties=(), fixture=True),
+    # one class: the pool is the class's own top-K, so every per-class winner, the K-th included, reaches the output
+    dict(name="c1", B=2, C=1, H=40, W=37, K=100, kind="cont", masked=True, thresh=0.3, seed=1113, ties=(), fixture=True),
+    dict(name="row37", B=2, C=3, H=1, W=37, K=37, kind="cont", masked=True, thresh=0.3, seed=1103, ties=(), fixture=True),
+    dict(name="row37_raw", B=2, C=3, H=1, W=37, K=37, kind="cont", masked=False, thresh=0.3, seed=1103, ties=()),
+    dict(name="k1023", B=1, C=2, H=33, W=31, K=1023, kind="cont", masked=True, thresh=0.3, seed=1104, ties=('pool',)),
+    dict(name="k1023_raw", B=1, C=2, H=33, W=31, K=1023, kind="cont", masked=False, thresh=0.3, seed=1104, ties=()),
+    dict(name="k4096", B=1, C=2, H=64, W=64, K=4096, kind="cont", masked=True, thresh=0.3, seed=1105, ties=('pool',)),
+    dict(name="k4096_raw", B=1, C=2, H=64, W=64, K=4096, kind="cont", masked=False, thresh=0.3, seed=1105, ties=()),
+    dict(name="const", B=2, C=10, H=40, W=72, K=20, kind="const", masked=True, thresh=0.3, seed=1106, ties=('class', 'pool')),
+    dict(name="const_ulp", B=2, C=10, H=40, W=72, K=20, kind="const_ulp", masked=True, thresh=0.3, seed=1107, ties=('class',)),
+    dict(name="quant_k7", B=3, C=10, H=24, W=40, K=7, kind="quant4", masked=False, thresh=0.5, seed=1108, ties=('class', 'pool')),
+    dict(name="quant_k100", B=3, C=10, H=24, W=40, K=100, kind="quant4", masked=False, thresh=0.5, seed=1108, ties=('class', 'pool')),
+    # K past the top level's ~240 cells: scores above the K-th and scores equal to it in one selection
+    dict(name="quant_k300", B=3, C=10, H=24, W=40, K=300, kind="quant4", masked=False, thresh=0.5, seed=1108, ties=('class', 'pool')),
+    # C * K = 9600 pads to a 16384-key pool, past the 8192 keys of the LDS sort: the entry point refuses it
+    dict(name="quant_k960", B=3, C=10, H=24, W=40, K=960, kind="quant4", masked=False, thresh=0.5, seed=1108, ties=('pool',),
+         refused=True),
+    dict(name="quant_c8_k960", B=3, C=8, H=24, W=40, K=960, kind="quant4", masked=False, thresh=0.5, seed=1108, ties=('pool',)),
+    dict(name="peaks", B=2, C=4, H=30, W=30, K=200, kind="peaks", masked=True, thresh=0.3, seed=1109, ties=('class', 'pool')),
+    dict(name="special", B=2, C=3, H=9, W=11, K=40, kind="special", masked=False, thresh=0.0, seed=1110, ties=('class', 'pool')),
+    dict(name="thresh_eq", B=2, C=10, H=24, W=40, K=20, kind="cont", masked=True, thresh_rank=(1, 7), seed=1111, ties=(),
+         fixture=True),
+    dict(name="stride2", B=1, C=20, H=324, W=324, K=50, kind="cont", masked=True, thresh=0.3, seed=1112, ties=(),
+         fixture=True),
+]
+CN_DENORMAL = 1.0e-41                # a float32 denormal
+CN_SPECIAL_VALUES = (float("-inf"), -1.0, -0.0, 0.0, CN_DENORMAL, 1.0, float("inf"))
+
+
+def cn_decode_predictions(c):
+    """The five head maps of a decode case (float32, CPU)."""
+    B, C, H, W = c["B"], c["C"], c["H"], c["W"]
+    s = c["seed"] * 104729
+    kind = c["kind"]
+    if kind == "cont":
+        heat = torch.sigmoid(synth.normal((B, C, H, W), s + 1, 0.0, 1.5))
+    elif kind in ("const", "const_ulp"):
+        heat = torch.full((B, C, H, W), 0.625)
+        if kind == "const_ulp":
+            heat[:, 6] = torch.nextafter(torch.tensor(0.625), torch.tensor(1.0))
+    elif kind == "quant4":
+        heat = 0.2 + 0.2 * synth.randint((B, C, H, W), s + 1, 0, 4).float()
+    elif kind == "peaks":
+        heat = torch.zeros(B, C, H * W)
+        for b in range(B):                       # 50 isolated peaks per frame on the even-row / even-column lattice
+            cell = torch.argsort(synth.uniform((15 * 15,), s + 10 + b))[:50]
+            pos = (cell // 15) * 2 * W + (cell % 15) * 2
+            heat[b, synth.randint((50,), s + 20 + b, 0, C).long(), pos] = synth.uniform((50,), s + 30 + b, 0.05, 1.0)
+        heat = heat.view(B, C, H, W)
+    elif kind == "special":
+        heat = torch.tensor(CN_SPECIAL_VALUES)[synth.randint((B, C, H, W), s + 1, 0, len(CN_SPECIAL_VALUES)).long()]
+    else:
+        raise ValueError(kind)
+    return dict(heatmap=heat.contiguous(), offset=synth.uniform((B, 2, H, W), s + 2),
+                size=synth.uniform((B, 3, H, W), s + 3, 0.5, 5), rot=synth.normal((B, 2, H, W), s + 4),
+                vel=synth.normal((B, 2, H, W), s + 5))
+
+
+# Target cases.  "lattice" boxes take every value from a small set (0.1 m positions, 0.25 m sizes, yaw in steps of pi/8,
+# 0.5 m/s velocities) so that the fixtures of the many-object cases stay small; "synth" boxes are continuous.
+CN_TARGET_CASES = [
+    dict(name="cap700_40x72", kind="lattice", frames=[(700, 9), (700, 9)], bev_size=(40, 72), seed=1201),
+    dict(name="dense300_17x9", kind="lattice", frames=[(300, 7), (300, 7)], bev_size=(17, 9), seed=1202),
+    dict(name="mixed_16x24", kind="synth", frames=[(30, 9), (30, 7), (30, 9)], bev_size=(16, 24), seed=1203),
+    dict(name="border_8x8", kind="border", frames=[(64, 7)], bev_size=(8, 8), seed=1204),
+    dict(name="border_ulp_8x8", kind="border_ulp", frames=[(64, 7)], bev_size=(8, 8), seed=1204),
+    dict(name="grid_1x1", kind="synth", frames=[(10, 9), (10, 9)], bev_size=(1, 1), seed=1205),
+    dict(name="grid_1x7", kind="synth", frames=[(10, 9), (10, 9)], bev_size=(1, 7), seed=1206),
+    dict(name="onecls_12x12", kind="synth", frames=[(10, 9), (10, 9)], bev_size=(12, 12), num_classes=1, seed=1207),
+    dict(name="own300_1x1", kind="lattice", frames=[(300, 9)], bev_size=(1, 1), seed=1208),
+    dict(name="lds4096_32x32", kind="lattice", frames=[(4096, 9)], bev_size=(32, 32), max_objects=4096, seed=1209),
+]
+CN_TARGET_OVER = dict(name="over4097", kind="lattice", frames=[(4097, 9)], bev_size=(32, 32), max_objects=4097, seed=1210)
+
+
+def cn_target_kwargs(c):
+    return dict(bev_size=c["bev_size"], num_classes=c.get("num_classes", 10), max_objects=c.get("max_objects", 500))
+
+
+def cn_target_inputs(c):
+    """(list of (M,7|9) float32 boxes, list of (M,) int64 labels); yaw stays within +-float32(pi) and the first three boxes of
+    every frame carry exactly 0, +pi and -pi."""
+    pi32 = float(torch.tensor(math.pi, dtype=torch.float32))
+    boxes, labels = [], []
+    for f, (n, width) in enumerate(c["frames"]):
+        s = c["seed"] * 7919 + f * 1000
+        kind = c["kind"]
+        if kind in ("border", "border_ulp"):
+            H, W = c["bev_size"]
+            b = torch.zeros(n, 9)
+            i = torch.arange(n)
+            b[:, 0] = (-51.2 + (i % W).double() * (102.4 / W)).float()       # centres exactly on the cell borders
+            b[:, 1] = (-51.2 + (i // W).double() * (102.4 / H)).float()
+            if kind == "border_ulp":
+                b[:, 0] = torch.nextafter(b[:, 0], torch.tensor(-1000.0))
+            b[:, 2] = -1.0
+            b[:, 3:6] = synth.uniform((n, 3), s + 4, 0.5, 5.0)
+            b[:, 6] = synth.uniform((n,), s + 5, -pi32, pi32)
+            l = synth.randint((n,), s + 7, 0, 10)
+        elif kind == "lattice":
+            b = torch.zeros(n, 9)
+            b[:, 0] = (-51.2 + 0.1 * synth.randint((n,), s + 1, 0, 1024).double()).float()
+            b[:, 1] = (-51.2 + 0.1 * synth.randint((n,), s + 2, 0, 1024).double()).float()
+            b[:, 2] = -1.0
+            b[:, 3:6] = 0.25 * synth.randint((n, 3), s + 4, 2, 21).float()
+            b[:, 6] = (synth.randint((n,), s + 5, -8, 9).double() * (math.pi / 8)).float()
+            b[:, 7:9] = 0.5 * synth.randint((n, 2), s + 6, -8, 9).float()
+            l = synth.randint((n,), s + 7, 0, 10)
+            l[5::50] = -1                                                     # padding labels in the middle of a frame
+        else:
+            b, l = synth.gt_boxes(1, n, seed=s)
+            b, l = b[0].clone(), l[0].clone()
+            if c.get("num_classes", 10) == 1:
+                l = l % 2                                                     # about half the boxes are of the one class
+        b[:, 6] = b[:, 6].clamp(-pi32, pi32)
+        b[0, 6], b[1, 6], b[2, 6] = 0.0, pi32, -pi32
+        boxes.append(b[:, :width].contiguous())
+        labels.append(l.to(torch.int64))
+    return boxes, labels
+
+
+# Loss cases: predictions and targets built directly, so that `ind` may repeat a cell any number of times.
+CN_LOSS_CASES = [
+    dict(name="one", B=1, C=1, H=1, W=1, K=1, seed=1301),
+    dict(name="n250", B=1, C=10, H=5, W=5, K=3, seed=1302),
+    dict(name="k500", B=2, C=10, H=16, W=24, K=500, seed=1303),
+    dict(name="no_positive", B=2, C=10, H=16, W=24, K=40, seed=1304, positives=0),
+    dict(name="mask_zero", B=2, C=10, H=16, W=24, K=40, seed=1305, mask="zero"),
+    dict(name="clamp", B=2, C=10, H=16, W=24, K=40, seed=1306, clamp=True),
+    dict(name="near_one", B=2, C=10, H=16, W=24, K=40, seed=1307, near_one=True),
+    dict(name="four_in_cell", B=1, C=10, H=8, W=12, K=8, seed=1308, four=True),
+]
+CN_CLAMP_LOGITS = (9.0, -9.0, 9.3, -9.3, 20.0, -20.0)       # |x| > 9.21 is where sigmoid leaves [1e-4, 1 - 1e-4]
+
+
+def cn_loss_inputs(c):
+    """(pred, tgt) float32 / int64 / uint8 CPU tensors.  The heatmap prediction holds logits (the loss applies the sigmoid)."""
+    B, C, H, W, K = c["B"], c["C"], c["H"], c["W"], c["K"]
+    s = c["seed"] * 104729
+    n = B * C * H * W
+    pred = dict(heatmap=synth.normal((B, C, H, W), s + 1, 0.0, 1.5), offset=synth.normal((B, 2, H, W), s + 2),
+                size=synth.normal((B, 3, H, W), s + 3), rot=synth.normal((B, 2, H, W), s + 4),
+                vel=synth.normal((B, 2, H, W), s + 5))
+    heat = synth.uniform((n,), s + 6) ** 8                                   # mostly small, like a splatted map
+    npos = c.get("positives", max(1, n // 40))
+    pos = torch.argsort(synth.uniform((n,), s + 7))[:npos]
+    heat[pos] = 1.0
+    if c.get("positives") == 0:
+        heat = heat.clamp(max=0.95)
+    below = torch.nextafter(torch.tensor(1.0), torch.tensor(0.0))
+    if c.get("near_one"):
+        heat[torch.argsort(synth.uniform((n,), s + 8))[:max(1, n // 40)]] = below
+        heat[pos] = 1.0
+    if c.get("clamp"):
+        flat = pred["heatmap"].view(-1)
+        where = torch.argsort(synth.uniform((n,), s + 9))[:48]
+        flat[where] = torch.tensor(CN_CLAMP_LOGITS).repeat(8)
+        heat[where[:12]] = 1.0                                               # every logit twice on a positive, six times elsewhere
+    ind = synth.randint((B, K), s + 10, 0, H * W).to(torch.int64)
+    mask = (synth.uniform((B, K), s + 11) < 0.8).to(torch.uint8)
+    if c.get("mask") == "zero":
+        mask.zero_()
+    if c.get("four"):
+        ind[0] = torch.tensor([5, 17, 5, 40, 5, 17, 5, 63])
+        mask.fill_(1)
+    if K == 1:
+        mask.fill_(1)
+    tgt = dict(heatmap=heat.view(B, C, H, W).contiguous(), ind=ind, mask=mask.clone(), reg_mask=mask,
+               target_offset=synth.uniform((B, K, 2), s + 12), target_size=synth.uniform((B, K, 3), s + 13, 0.5, 5.0),
+               target_rot=synth.normal((B, K, 2), s + 14), target_vel=synth.normal((B, K, 2), s + 15))
+    if c.get("four"):                                                        # channel 0 of `offset`: all four terms push one way
+        pred["offset"][0, 0].view(-1)[5] = 10.0
+    return pred, tgt
+
+
+# keep-mask planes (planes, H, W): 1x1, 1xW, Hx1, an odd plane, and 17 x 256 x 256 = 1 114 112 values, more than the
+# 4096 x 256 threads of the kernel's grid, so its grid-stride loop takes a second trip
+CN_NMS_CASES = [(1, 1, 1), (3, 1, 37), (2, 41, 1), (5, 13, 19), (17, 256, 256)]
+
+
+def cn_nms_plane(case):
+    """Values on a coarse grid (plateaus, ties between neighbours), negative ones and both zeros included."""
+    p, H, W = case
+    v = 0.25 * synth.randint((p, H, W), 1400 + p * H * W, -3, 4).float()
+    v[synth.uniform((p, H, W), 1401 + p * H * W) < 0.1] = -0.0
+    return v.contiguous()

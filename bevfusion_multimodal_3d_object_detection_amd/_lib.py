@@ -1315,7 +1315,9 @@ def resize_normalize_u8(x, out, n: int, H: int, W: int, Ho: int, Wo: int, bounds
 
 def lidar_filter_pad(points, out, count, work, choice, N: int, Cc: int, max_points: int, pc_range: Sequence[float]) -> None:
     """One sweep [N][C] -> the in-range points, in order, zero-padded (or picked by `choice`, max_points int64) to out
-    [max_points][C]; count: 1 int32; work: N*C + ceil(N / 1024) floats."""
+    [max_points][C]; count: 1 int32; work: N*C + ceil(N / 1024) floats.  `choice` is used only when count >= max_points
+    (with fewer survivors it is ignored: survivors in order, then zero rows); an entry that is negative or >= count reads no
+    survivor and gives a zero row."""
     _need("lidar_filter_pad", points=(points, N * Cc), out=(out, max_points * Cc), count=(count, 1),
           work=(work, N * Cc + -(-N // 1024)), choice=(choice, max_points))
     _call("bevf_lidar_filter_pad_f32", _pc(points), _pc(out), _pc(count, torch.int32), _pc(work), _pc(choice, torch.int64), N, Cc,

@@ -293,9 +293,16 @@ extern "C" int bevf_voxelize_f32(const bevf_voxelize_desc* d, void* stream) {
   a.x0 = d->pc_range[0]; a.y0 = d->pc_range[1]; a.z0 = d->pc_range[2];
   a.vx = d->voxel_size[0]; a.vy = d->voxel_size[1]; a.vz = d->voxel_size[2];
   BEVF_REQUIRE(a.vx > 0 && a.vy > 0 && a.vz > 0, "voxelize: voxel sizes must be positive");
-  a.gx = (int)lroundf((d->pc_range[3] - d->pc_range[0]) / a.vx);
-  a.gy = (int)lroundf((d->pc_range[4] - d->pc_range[1]) / a.vy);
-  a.gz = (int)lroundf((d->pc_range[5] - d->pc_range[2]) / a.vz);
+  // a whole number of voxels per axis: half a voxel has no agreed rounding (lroundf: half away from zero, numpy: half to even)
+  const float ratio[3] = {(d->pc_range[3] - d->pc_range[0]) / a.vx, (d->pc_range[4] - d->pc_range[1]) / a.vy,
+                          (d->pc_range[5] - d->pc_range[2]) / a.vz};
+  for (int i = 0; i < 3; ++i)
+    BEVF_REQUIRE(fabsf(ratio[i] - roundf(ratio[i])) <= 0.01f,
+                 "voxelize: (max - min) / voxel_size on axis %c is %.9g, further than 0.01 from a whole number of voxels", "xyz"[i],
+                 (double)ratio[i]);
+  a.gx = (int)lroundf(ratio[0]);
+  a.gy = (int)lroundf(ratio[1]);
+  a.gz = (int)lroundf(ratio[2]);
   BEVF_REQUIRE(a.gx > 0 && a.gy > 0 && a.gz > 0 && (long long)a.gx * a.gy * a.gz < 0xFFFFFFFFll, "voxelize: bad grid");
   a.max_points = d->max_points; a.max_voxels = d->max_voxels;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -312,7 +312,10 @@ def voxelize(points: torch.Tensor, point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 
     """Hard voxelisation feeding `VFELayer` / `VoxelNetLiDAREncoder` (their docstrings, ref src/encoders.py:313-321,
     describe exactly this input; the reference never builds it).  Defaults are the grid of configs/base.yaml:48-55
     (50 x 50 pillars) and the reference's "32 points, 12000 voxels".  points (B,N,C) ->
-    voxel_features (B,Nv,P,C) zero padded, voxel_coords (B,Nv,3) int64 (z,y,x), num_points (B,Nv), num_voxels (B,)."""
+    voxel_features (B,Nv,P,C) zero padded, voxel_coords (B,Nv,3) int64 (z,y,x), num_points (B,Nv), num_voxels (B,).
+    The range must be a whole number of voxels on every axis: (max - min) / voxel_size, in fp32, further than 0.01 from an
+    integer raises BevfError naming the axis (half a voxel has no agreed rounding); a voxel size derived as range / cells in
+    fp32, as `pillar_grid` / `sparse_grid` do, is always accepted."""
     E.require_cuda(points)
     return L.voxelize(points.float().contiguous(), point_cloud_range, voxel_size, max_points_per_voxel, max_voxels)
 

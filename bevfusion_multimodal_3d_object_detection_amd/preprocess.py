@@ -98,7 +98,9 @@ def filter_pad_lidar(points: torch.Tensor, max_points: int = 35000,
                      pc_range: Sequence[float] = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                      choice: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(N, C>=3) fp32 cuda sweep -> ((max_points, C) fp32, number of points inside the range (int32 scalar tensor)).
-    ref src/train_detect.py:145-161, 181-189."""
+    ref src/train_detect.py:145-161, 181-189.  `choice` (max_points indices into the survivors) is used only when at least
+    max_points points survive; with fewer it is ignored (survivors in order, then zero rows).  A choice entry that is negative
+    or >= the survivor count gives a zero row (numpy would wrap or raise; the kernel reads nothing out of range)."""
     if points.dim() != 2 or points.shape[1] < 3 or points.dtype != torch.float32:
         raise L.BevfError("filter_pad_lidar: expected fp32 (N, C>=3)")
     if not points.is_cuda:

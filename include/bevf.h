@@ -321,7 +321,10 @@ int bevf_centernet_loss_f32(const bevf_loss_desc* d, void* stream);
  * assignment, so the semantics are the usual deterministic ones: cell = floor((p - range_min) / voxel_size)
  * in fp32, out-of-grid points dropped, voxels numbered by first point, first max_points points per voxel in
  * input order, zero padding.  Outputs must be zero-filled by the caller.  voxel_coords are (z, y, x) = the
- * (D, H, W) index order of ref :399-410.  Grid dims = round((max - min) / voxel_size).
+ * (D, H, W) index order of ref :399-410.  Grid dims = round((max - min) / voxel_size), and the grid must be a whole
+ * number of voxels: an axis whose fp32 ratio (max - min) / voxel_size lies further than 0.01 from an integer is refused
+ * (BEVF_ERR_ARG, the message names the axis) -- there is no agreed rounding for half a voxel, and a voxel size derived
+ * as range / cells in fp32 is an integer ratio to a few ulps.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   const float* points;       /* [B][N][C], x y z first */

@@ -2,13 +2,16 @@
 __version__ = "0.1.0"
 
 _MAP_TARGETS = ("MapShapes", "pack_shapes", "rasterize", "rasterize_for")
-__all__ = ["map_targets", *_MAP_TARGETS]
+_SWEEPS = ("SweepMerger", "merge_sweeps", "pack_sweeps", "sweep_transforms", "time_lags")
+_LAZY = {"map_targets": _MAP_TARGETS, "sweeps": _SWEEPS}
+__all__ = ["map_targets", *_MAP_TARGETS, "sweeps", *_SWEEPS]
 
 
 def __getattr__(name):
-    """`map_targets` and its public names, imported on first use (importing the package stays free of torch)."""
-    if name == "map_targets" or name in _MAP_TARGETS:
-        from importlib import import_module
-        mod = import_module(".map_targets", __name__)
-        return mod if name == "map_targets" else getattr(mod, name)
+    """`map_targets`, `sweeps` and their public names, imported on first use (importing the package stays free of torch)."""
+    for module, names in _LAZY.items():
+        if name == module or name in names:
+            from importlib import import_module
+            mod = import_module("." + module, __name__)
+            return mod if name == module else getattr(mod, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

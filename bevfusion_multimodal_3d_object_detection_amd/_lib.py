@@ -281,6 +281,10 @@ SIGNATURES = {
     "bevf_map_raster_work_bytes": (C.c_size_t, [C.c_int] * 2),
     "bevf_map_raster_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int]
                            + [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_double] * 4 + [C.c_void_p] * 3),
+    # ---- multi-sweep LiDAR accumulation ----
+    "bevf_sweeps_merge_work_bytes": (C.c_size_t, [C.c_int] * 3),
+    "bevf_sweeps_merge_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float, C.POINTER(C.c_float), C.c_void_p]),
+    "bevf_sweep_pose_chain_f64": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
 }
 
 
@@ -1838,3 +1842,40 @@ def map_raster(vertices, ring_offsets, shape_offsets, shape_class, shape_kind, s
     _call("bevf_map_raster_u8", _pc(vertices), V, _pc(ring_offsets, I32), R, _pc(shape_offsets, I32), _pc(shape_class, I32),
           _pc(shape_kind, I32), _pc(shape_width), S, _pc(frame_offsets, I32), B, _pc(mat), _pc(scale), K, Ho, Wo, *g,
           _pc(work, U8), _pc(out, U8))
+
+
+# ---- multi-sweep LiDAR accumulation (csrc/sweeps.hip) ----
+
+def sweeps_merge_work_bytes(B: int, S: int, N: int) -> int:
+    """Bytes of sweeps_merge's workspace (two int32 per tile of 1024 rows)."""
+    return int(lib().bevf_sweeps_merge_work_bytes(B, S, N))
+
+
+def sweeps_merge(points, counts, sweep_to_key, time_lag, out, count, sweep_count, work, B: int, S: int, N: int, Cc: int, max_points: int,
+                 close_radius: float, pc_range: Sequence[float]) -> None:
+    """points [B][S][N][C] (counts [B][S] int32 valid rows) through sweep_to_key fp64 [B][S][4][4], close-point and range filter, merged
+    in sweep order with time_lag [B][S] as channel C: out [B][max_points][C + 1], count [B] and sweep_count [B][S] int32
+    (bevf_sweeps_merge_f32; the rules: include/bevf.h).  work: int32 [ceil(sweeps_merge_work_bytes(B, S, N) / 4)]."""
+    if not (B > 0 and S > 0 and N >= 0 and 3 <= Cc <= 8 and max_points > 0):
+        raise BevfError(f"sweeps_merge: bad shape B = {B}, S = {S}, N = {N}, C = {Cc}, max_points = {max_points} (3 <= C <= 8)")
+    if len(pc_range) != 6:
+        raise BevfError(f"sweeps_merge: pc_range is (x0, y0, z0, x1, y1, z1), got {tuple(pc_range)}")
+    i32 = torch.int32
+    _need("sweeps_merge", points=(points, B * S * N * Cc), counts=(counts, B * S), sweep_to_key=(sweep_to_key, B * S * 16),
+          time_lag=(time_lag, B * S), out=(out, B * max_points * (Cc + 1)), count=(count, B), sweep_count=(sweep_count, B * S),
+          work=(work, -(-sweeps_merge_work_bytes(B, S, N) // 4)))
+    _call("bevf_sweeps_merge_f32", _pc(points), _pc(counts, i32), _pc(sweep_to_key, torch.float64), _pc(time_lag), _pc(out),
+          _pc(count, i32), _pc(sweep_count, i32), _pc(work, i32), B, S, N, Cc, max_points, float(close_radius), (C.c_float * 6)(*pc_range))
+
+
+def sweep_pose_chain(key_lidar2ego, key_ego2global, sweep_lidar2ego, sweep_ego2global, sweep_to_key, B: int, S: int) -> None:
+    """sweep_to_key [B][S][4][4] = inv(L_k) . inv(E_k) . E_s . L_s from key_lidar2ego / key_ego2global [B][4][4] and sweep_lidar2ego /
+    sweep_ego2global [B][S][4][4], all fp64 on the device (bevf_sweep_pose_chain_f64)."""
+    if not (B > 0 and S > 0):
+        raise BevfError(f"sweep_pose_chain: bad shape B = {B}, S = {S}")
+    f64 = torch.float64
+    _need("sweep_pose_chain", key_lidar2ego=(key_lidar2ego, B * 16), key_ego2global=(key_ego2global, B * 16),
+          sweep_lidar2ego=(sweep_lidar2ego, B * S * 16), sweep_ego2global=(sweep_ego2global, B * S * 16),
+          sweep_to_key=(sweep_to_key, B * S * 16))
+    _call("bevf_sweep_pose_chain_f64", _pc(key_lidar2ego, f64), _pc(key_ego2global, f64), _pc(sweep_lidar2ego, f64),
+          _pc(sweep_ego2global, f64), _pc(sweep_to_key, f64), B, S)

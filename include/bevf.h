@@ -1025,6 +1025,33 @@ int bevf_map_raster_u8(const float* vertices, int V, const int32_t* ring_offsets
                        const int32_t* frame_offsets, int B, const float* mat, const float* scale, int K, int Ho, int Wo, double x0,
                        double y0, double vx, double vy, void* work, uint8_t* out, void* stream);
 
+/* ==========================================================================================
+ * Multi-sweep LiDAR accumulation (csrc/sweeps.hip).
+ * ========================================================================================== */
+
+/* The key sweep and the preceding sweeps of B frames merged into one padded cloud per frame.  points [B][S][N][C] (3 <= C <= 8),
+ * counts [B][S] valid rows per sweep (clamped to [0, N]; 0 = an absent sweep), sweep 0 the key sweep, later indices older.  A row is
+ * dropped when fabsf(x) < close_radius && fabsf(y) < close_radius on the sweep's own fp32 coordinates (close_radius <= 0: no such
+ * test).  The others go through sweep_to_key (DEVICE fp64 [B][S][4][4], only the top 3 x 4 is read) in fp64, rounded once to fp32:
+ *   x' = (float)(((m00 (double)x + m01 (double)y) + m02 (double)z) + m03), y' and z' alike, in this order, no fused multiply-add,
+ * then bevf_lidar_filter_pad_f32's strict range filter on the rounded coordinates (a NaN fails it).  out [B][max_points][C + 1]: a
+ * surviving row = x' y' z', channels 3 .. C-1 copied bit for bit, then time_lag[b][s] (fp32 [B][S]); sweep 0's survivors in point
+ * order, then sweep 1's, ...; the first max_points of that order are kept, the rows behind the last survivor are zeros.  count [B] =
+ * all survivors and sweep_count [B][S] = each sweep's, both untruncated.  No atomics (bit-reproducible), no allocation, four launches
+ * on `stream` whose grids depend on (B, S, N) only.  work: bevf_sweeps_merge_work_bytes(B, S, N) bytes, 4-byte aligned (two ints
+ * per tile of 1024 rows).  B, S < 65536; S * N < 2^31.                                                                          */
+size_t bevf_sweeps_merge_work_bytes(int B, int S, int N);
+int bevf_sweeps_merge_f32(const float* points, const int32_t* counts, const double* sweep_to_key, const float* time_lag, float* out,
+                          int32_t* count, int32_t* sweep_count, void* work, int B, int S, int N, int C, int max_points,
+                          float close_radius, const float* pc_range6, void* stream);
+/* sweep_to_key [B][S][4][4] = inv(L_k) . inv(E_k) . E_s . L_s, all DEVICE fp64: key_lidar2ego L_k and key_ego2global E_k [B][4][4],
+ * sweep_lidar2ego L_s and sweep_ego2global E_s [B][S][4][4]; only the top 3 x 4 of each is read, the bottom rows count as 0 0 0 1.
+ * inv = the rigid inverse (R^T, -(R^T t)) with each element of R^T t = ((r0 t0 + r1 t1) + r2 t2); a product element =
+ * (((a0 b0 + a1 b1) + a2 b2) + a3 b3); products right to left (E_s . L_s first); no fused multiply-add; the bottom row is written as
+ * 0 0 0 1.  A sweep whose L_s and E_s equal L_k and E_k element for element (the key sweep itself) gets the exact identity.      */
+int bevf_sweep_pose_chain_f64(const double* key_lidar2ego, const double* key_ego2global, const double* sweep_lidar2ego,
+                              const double* sweep_ego2global, double* sweep_to_key, int B, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

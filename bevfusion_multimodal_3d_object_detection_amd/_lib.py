@@ -231,7 +231,7 @@ SIGNATURES = {
     "bevf_stem_im2col_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_smallk_wgrad_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_grad_norm_f32": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
-    "bevf_adamw_step_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
+    "bevf_adamw_step_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t] + [C.c_double] * 5 + [C.c_int, C.c_void_p]),
     "bevf_csr_gather_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
                             + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_csr_gather_bf16": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]

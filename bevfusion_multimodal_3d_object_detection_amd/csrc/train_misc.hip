@@ -578,19 +578,21 @@ __global__ void norm_finalize(const double* __restrict__ part, int G, float max_
   const float coef = max_norm / (norm + 1e-6f);
   out[1] = coef < 1.f ? coef : 1.f;
 }
-// torch.optim.AdamW (amsgrad off, maximize off): p *= 1 - lr*wd; m,v update; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+// torch.optim.AdamW (amsgrad off, maximize off): p *= 1 - lr*wd; m,v update; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).
+// Every scalar arrives formed in double and rounded once, as torch forms them from Python floats: decay = 1 - lr*wd,
+// omb1 = 1 - beta1, omb2 = 1 - beta2, step_size = lr / bc1 (1 - 0.999f in float is 1.3e-5 off 0.001: that was v's error).
 __global__ __launch_bounds__(256) void adamw_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ clip, long long n,
-                                                   float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                   float decay, float omb1, float b2, float omb2, float eps, float step_size,
                                                    float bc2_sqrt) {
   const float coef = clip ? clip[1] : 1.f;
   GRID_STRIDE(i, n) {
     const float gi = g[i] * coef;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);             // lerp_, as torch's single-tensor path
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float pi = p[i] * decay;
+    const float mi = m[i] + (gi - m[i]) * omb1;                   // lerp_, as torch's single-tensor path
+    const float vi = v[i] * b2 + omb2 * gi * gi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi -= (lr / bc1) * (mi / denom);
+    pi -= step_size * (mi / denom);
     p[i] = pi; m[i] = mi; v[i] = vi;
   }
 }
@@ -735,6 +737,8 @@ extern "C" size_t bevf_linear_bwd_work_floats(int B, int K, int O) {
 extern "C" int bevf_linear_bwd_f32(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db,
                                    float* work, int B, int K, int O, int perm_inner, int perm_outer, void* stream) {
   BEVF_REQUIRE(dy && x && w && dw && work && B > 0 && B <= 64 && K > 0 && K % 4 == 0 && O > 0, "linear_bwd: bad arguments (B <= 64)");
+  BEVF_REQUIRE(perm_inner == 0 || (perm_outer > 0 && (long long)perm_inner * perm_outer == O),
+               "linear_bwd: perm_inner * perm_outer must equal O (%d * %d, O = %d)", perm_inner, perm_outer, O);
   int G, chunk, lanes;
   linear_bwd_geometry(K, O, &G, &chunk, &lanes);
   if (dx) {
@@ -751,6 +755,8 @@ extern "C" int bevf_head_tail_bwd_f32(const bevf_head_bwd_desc* d, void* stream)
   BEVF_REQUIRE(d && d->hid && d->w && d->out0 && d->dhid && d->dw && d->db, "head_tail_bwd: null pointer");
   BEVF_REQUIRE(d->B > 0 && d->P > 0 && d->hc > 0, "head_tail_bwd: empty shape");
   for (int k = 0; k < 5; ++k) BEVF_REQUIRE(d->c[k] >= 0 && d->c[k] <= 16, "head_tail_bwd: at most 16 outputs per branch");
+  BEVF_REQUIRE(d->n_sigmoid >= 0 && d->n_sigmoid <= d->c[0], "head_tail_bwd: n_sigmoid = %d outside [0, c[0] = %d]", d->n_sigmoid,
+               d->c[0]);
   HeadBwdArgs a;
   a.hid = d->hid; a.w = d->w; a.out0 = d->out0; a.dhid = d->dhid; a.dw = d->dw; a.db = d->db;
   a.B = d->B; a.P = d->P; a.hc = d->hc; a.n_sigmoid = d->n_sigmoid;
@@ -803,11 +809,12 @@ extern "C" int bevf_grad_norm_f32(const float* g, size_t n, double* work512, flo
   hipLaunchKernelGGL(norm_finalize, dim3(1), dim3(1), 0, ST, work512, (int)G, max_norm, out2);
   return bevf_check_launch("bevf_grad_norm_f32");
 }
-extern "C" int bevf_adamw_step_f32(float* p, const float* g, float* m, float* v, const float* clip2, size_t n, float lr,
-                                   float beta1, float beta2, float eps, float weight_decay, int step, void* stream) {
+extern "C" int bevf_adamw_step_f32(float* p, const float* g, float* m, float* v, const float* clip2, size_t n, double lr,
+                                   double beta1, double beta2, double eps, double weight_decay, int step, void* stream) {
   BEVF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw: bad arguments");
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);   // python floats in torch
-  hipLaunchKernelGGL(adamw_step, dim3(ew_grid((long long)n)), dim3(256), 0, ST, p, g, m, v, clip2, (long long)n, lr, beta1,
-                     beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2));
+  const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);                   // python floats in torch
+  hipLaunchKernelGGL(adamw_step, dim3(ew_grid((long long)n)), dim3(256), 0, ST, p, g, m, v, clip2, (long long)n,
+                     (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                     (float)(lr / bc1), (float)sqrt(bc2));
   return bevf_check_launch("bevf_adamw_step_f32");
 }

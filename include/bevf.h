@@ -812,6 +812,9 @@ int bevf_gmax_bn_backward_f32(const float* dg, const float* gmax, const int32_t*
 int bevf_gmax_bn_sums_f32(const float* dg, const float* gmax, const int32_t* idx, const float* x, const float* mean,
                           const float* invstd, float* dgm, float* dgamma, float* dbeta, int B, int P, int C, int cs, void* stream);
 size_t bevf_linear_bwd_work_floats(int B, int K, int O);
+/* Backward of bevf_linear_f32: dy [B][O] in the forward's stored order, i.e. read at perm(o).  perm_inner == 0: no permutation;
+ * otherwise perm_outer > 0 and perm_inner * perm_outer == O are required (only then is perm a permutation of [0, O)).
+ * dx and db may be NULL; B <= 64, K % 4 == 0.  Fixed summation order: bit-identical run to run.                                 */
 int bevf_linear_bwd_f32(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, float* work,
                         int B, int K, int O, int perm_inner, int perm_outer, void* stream);
 typedef struct {
@@ -820,7 +823,7 @@ typedef struct {
   float* dhid; float* dw; float* db;                     /* dw, db zero-filled by the caller */
   int32_t B, P, hc;
   int32_t c[5];
-  int32_t n_sigmoid;
+  int32_t n_sigmoid;                                     /* leading heatmap channels behind a sigmoid: 0 <= n_sigmoid <= c[0] */
 } bevf_head_bwd_desc;
 int bevf_head_tail_bwd_f32(const bevf_head_bwd_desc* d, void* stream);
 /* d total_loss / d predictions for CenterNetLoss (ref src/centernet_target.py:544-622); dpred[5] zero-filled;
@@ -833,9 +836,11 @@ int bevf_stem_wgrad_f32(const float* x, const float* dy, float* dw, int N, int H
 int bevf_smallk_wgrad_f32(const float* dy, const float* x, float* dw, int M, int K, int Cout, void* stream);
 /* clip_grad_norm_: out2 = {total L2 norm, min(1, max_norm/(norm+1e-6))}; work512: 512 doubles.                */
 int bevf_grad_norm_f32(const float* g, size_t n, double* work512, float max_norm, float* out2, void* stream);
-/* torch.optim.AdamW single step on a flat parameter range; gradients are scaled by clip2[1] when given.        */
-int bevf_adamw_step_f32(float* p, const float* g, float* m, float* v, const float* clip2, size_t n, float lr,
-                        float beta1, float beta2, float eps, float weight_decay, int step, void* stream);
+/* torch.optim.AdamW single step on a flat parameter range; gradients are scaled by clip2[1] when given.  The
+ * hyper-parameters are doubles, as torch's Python floats: 1 - beta, 1 - lr * weight_decay and lr / (1 - beta1^step)
+ * are formed in double and rounded once (1 - 0.999f formed in float would be 1.3e-5 off).                      */
+int bevf_adamw_step_f32(float* p, const float* g, float* m, float* v, const float* clip2, size_t n, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, int step, void* stream);
 
 /* ==========================================================================================
  * Input pipeline (ref src/train_detect.py:123-189, the dataset's per-sample host work)

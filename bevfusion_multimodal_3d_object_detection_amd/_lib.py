@@ -285,6 +285,8 @@ SIGNATURES = {
     "bevf_sweeps_merge_work_bytes": (C.c_size_t, [C.c_int] * 3),
     "bevf_sweeps_merge_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_float, C.POINTER(C.c_float), C.c_void_p]),
     "bevf_sweep_pose_chain_f64": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
+    # ---- multi-object tracking ----
+    "bevf_track_step_f32": (C.c_int, [C.c_void_p] * 21 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p]),
 }
 
 
@@ -1879,3 +1881,61 @@ def sweep_pose_chain(key_lidar2ego, key_ego2global, sweep_lidar2ego, sweep_ego2g
           sweep_to_key=(sweep_to_key, B * S * 16))
     _call("bevf_sweep_pose_chain_f64", _pc(key_lidar2ego, f64), _pc(key_ego2global, f64), _pc(sweep_lidar2ego, f64),
           _pc(sweep_ego2global, f64), _pc(sweep_to_key, f64), B, S)
+
+
+# ---- multi-object tracking (csrc/track.hip) ----
+
+TRACK_MAX_N, TRACK_MAX_T = 4096, 1024
+TRACK_STATE = (("track_box", torch.float32, (7,)), ("track_vel", torch.float32, (2,)), ("track_score", torch.float32, ()),
+               ("track_label", torch.int64, ()), ("track_id", torch.int64, ()), ("track_age", torch.int32, ()),
+               ("track_hits", torch.int32, ()))
+TRACK_OUT = (("det_track_id", torch.int64), ("det_hits", torch.int32), ("det_slot", torch.int32))
+
+
+def _track_want(name: str, t, dtype, shape) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise BevfError(f"track_step: {name} must be a {dtype} {tuple(shape)} tensor, got {got}")
+
+
+def track_step(boxes, velocities, scores, labels, count, ego_motion, dt, max_dist, state: dict, out: dict, max_age: int,
+               birth_score: float, class_aware: bool) -> None:
+    """One tracker step (bevf_track_step_f32; the rules: include/bevf.h).  Detections (B,N,7) / (B,N,2) / (B,N) / int64 (B,N) / int32
+    (B,); ego_motion float64 (B,4,4) current -> previous frame; dt (B,); max_dist (C,).  state: the TRACK_STATE tensors (B,T,...) plus
+    track_count int32 (B,) and next_id int64 (B,), updated in place; out: det_track_id int64 (B,N), det_hits / det_slot int32 (B,N) and
+    overflow int32 (B,), written.  Everything is checked before the launch; nothing is allocated or read back."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3 or boxes.shape[2] != 7 or boxes.shape[0] == 0:
+        got = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
+        raise BevfError(f"track_step: boxes must be a (B,N,7) tensor with B > 0, got {got}")
+    B, N = boxes.shape[0], boxes.shape[1]
+    tb = state.get("track_box")
+    if not isinstance(tb, torch.Tensor) or tb.dim() != 3 or tb.shape[1] == 0:
+        raise BevfError("track_step: state['track_box'] must be a (B,T,7) tensor with T > 0")
+    T = tb.shape[1]
+    if N > TRACK_MAX_N:
+        raise BevfError(f"track_step: N={N} exceeds the kernel's {TRACK_MAX_N} detections per stream")
+    if T > TRACK_MAX_T:
+        raise BevfError(f"track_step: T={T} exceeds the kernel's {TRACK_MAX_T} tracks per stream")
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    _track_want("boxes", boxes, f32, (B, N, 7))
+    _track_want("velocities", velocities, f32, (B, N, 2))
+    _track_want("scores", scores, f32, (B, N))
+    _track_want("labels", labels, i64, (B, N))
+    _track_want("count", count, i32, (B,))
+    _track_want("ego_motion", ego_motion, torch.float64, (B, 4, 4))
+    _track_want("dt", dt, f32, (B,))
+    if not isinstance(max_dist, torch.Tensor) or max_dist.dtype != f32 or max_dist.dim() != 1 or max_dist.numel() == 0:
+        raise BevfError("track_step: max_dist must be a non-empty float32 (C,) tensor of per-class limits in metres")
+    for name, dtype, tail in TRACK_STATE:
+        _track_want(f"state[{name!r}]", state.get(name), dtype, (B, T) + tail)
+    _track_want("state['track_count']", state.get("track_count"), i32, (B,))
+    _track_want("state['next_id']", state.get("next_id"), i64, (B,))
+    for name, dtype in TRACK_OUT:
+        _track_want(f"out[{name!r}]", out.get(name), dtype, (B, N))
+    _track_want("out['overflow']", out.get("overflow"), i32, (B,))
+    if int(max_age) < 0:
+        raise BevfError(f"track_step: max_age must be >= 0, got {max_age}")
+    _call("bevf_track_step_f32", _pc(boxes), _pc(velocities), _pc(scores), _pc(labels, i64), _pc(count, i32),
+          _pc(ego_motion, torch.float64), _pc(dt), _pc(max_dist), *[_pc(state[name], dtype) for name, dtype, _ in TRACK_STATE],
+          _pc(state["track_count"], i32), _pc(state["next_id"], i64), *[_pc(out[name], dtype) for name, dtype in TRACK_OUT],
+          _pc(out["overflow"], i32), B, N, T, max_dist.numel(), int(max_age), float(birth_score), int(bool(class_aware)))

@@ -4,6 +4,7 @@
   objects on the host and round-trips the heatmap device->numpy->device per object, ref :278-280).
 * `CenterNetLoss` -- focal + gather-L1 reductions on device, including the reference's second
   sigmoid on the already-sigmoided heatmap (ref :563).
+* `decode_padded` -- the same decode left on the device as padded records and a count (for `tracking.Tracker`).
 * `decode_centernet_predictions` -- keep mask, two-level top-K, gather and box assembly on device;
   voxel size 2.048 m (ref :389).  `labels` are always 0 exactly like the reference (ref :434);
   pass `true_labels=True` for the class of the winning heatmap plane.
@@ -23,9 +24,10 @@ from .box_ops import decode_settings  # noqa: F401
 PC_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
 
 
-def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
-            true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
-            nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+def _decode_device(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
+                   true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
+                   nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False):
+    """The decode's device half: padded (boxes, scores, labels, velocities) records and count, nothing read back."""
     box_ops.check_nms_args(nms_type, nms_iou_thresh, nms_radius, nms_pre_max, class_aware, true_labels)
     heat = predictions["heatmap"]
     E.require_cuda(heat)
@@ -35,10 +37,18 @@ def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detec
                                                             float(voxel_size), PC_RANGE[0], PC_RANGE[1], true_labels)
     if nms_type is not None:
         # box NMS over the count[b] candidates above score_thresh (already in descending score order); the survivors come back
-        # compacted and cut to max_detections, and their number replaces `count` in the one host sync below
+        # compacted and cut to max_detections, and their number replaces `count` (the one value `_decode` reads back)
         thresh = float(nms_radius) if nms_type == "circle" else float(nms_iou_thresh)
         _, count, boxes, scores, labels, vels = L.nms_boxes(boxes, count, nms_type, thresh, int(max_detections), scores=scores,
                                                             labels=labels, velocities=vels, class_aware=class_aware, gather=True)
+    return boxes, scores, labels, vels, count
+
+
+def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
+            true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
+            nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+    boxes, scores, labels, vels, count = _decode_device(predictions, score_thresh, max_detections, voxel_size, true_labels, nms_type,
+                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware)
     counts = count.cpu().tolist()                     # the reference syncs here too (mask.sum() == 0, ref :362)
     out = []
     for b, n in enumerate(counts):
@@ -49,6 +59,19 @@ def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detec
             out.append({"boxes": boxes[b, :n], "scores": scores[b, :n], "labels": labels[b, :n],
                         "velocities": vels[b, :n]})
     return out
+
+
+def decode_padded(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3, max_detections: int = 100,
+                  true_labels: bool = False, *, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
+                  nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False,
+                  voxel_size: float = 2.048) -> Dict[str, torch.Tensor]:
+    """`decode_centernet_predictions` without its host read: the padded device records the decode (and the box NMS) compute, as
+    {"boxes" (B,K,7), "velocities" (B,K,2), "scores" (B,K), "labels" int64 (B,K), "count" int32 (B,)} with K = max_detections
+    (nms_pre_max with an NMS), rows past count[b] not meaningful.  Same keywords and the same launches; nothing is synchronised, so
+    decode -> NMS -> `tracking.Tracker.step` runs without a round trip to the host."""
+    boxes, scores, labels, vels, count = _decode_device(predictions, score_thresh, max_detections, voxel_size, true_labels, nms_type,
+                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware)
+    return {"boxes": boxes, "velocities": vels, "scores": scores, "labels": labels, "count": count}
 
 
 def decode_centernet_predictions(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3,

@@ -1057,6 +1057,43 @@ int bevf_sweeps_merge_f32(const float* points, const int32_t* counts, const doub
 int bevf_sweep_pose_chain_f64(const double* key_lidar2ego, const double* key_ego2global, const double* sweep_lidar2ego,
                               const double* sweep_ego2global, double* sweep_to_key, int B, int S, void* stream);
 
+/* ==========================================================================================
+ * Multi-object tracking on the decode path (csrc/track.hip).
+ * ========================================================================================== */
+
+/* One step of CenterPoint's greedy centre-distance tracker for B independent streams (a stream = one batch row), one wave per stream.
+ * Detections, as bevf_centernet_decode_f32 / bevf_nms_boxes_f32 leave them (descending score): boxes [B][N][7], velocities [B][N][2],
+ * scores [B][N], labels int64 [B][N], count [B] (clamped to [0, N]; rows past it are never read).  ego_motion: DEVICE fp64 [B][4][4],
+ * current frame -> previous frame, rigid M = [R t] (the tensor bevf_bev_warp_* takes; only the top 3 x 4 is read); dt fp32 [B] seconds;
+ * max_dist fp32 [C] metres per label.  The state (capacity T per stream, overwritten in place, owned by the caller): track_box
+ * [B][T][7], track_vel [B][T][2], track_score [B][T], track_label / track_id int64 [B][T], track_age (steps since the last match) /
+ * track_hits int32 [B][T], track_count [B] (clamped to [0, T]), next_id int64 [B]; rows past track_count are zeros with id -1 and the
+ * state is in the sensor frame of the step that wrote it.  A fresh state is all zeros with track_id -1.  The step, per stream:
+ *  1. detections i < count in order; a detection is valid when x, y, z, vx, vy and score are finite.  In fp64, rounded once:
+ *       px = x - vx dt, py = y - vy dt;  qx = (float)(((m00 px + m01 py) + m02 z) + m03), qy = (float)(((m10 px + m11 py) + m12 z) + m13)
+ *     Among the tracks not taken yet (with track_label == label_i when class_aware) whose fp32 squared distance
+ *     d2 = (qx - tx)(qx - tx) + (qy - ty)(qy - ty) to the stored centre is <= max_dist[l]^2 (l = label_i inside [0, C), else 0), the
+ *     one with the smallest d2 is matched and taken; a tie goes to the lower slot.  NaN anywhere (q, max_dist) compares as no match;
+ *     max_dist^2 saturates at FLT_MAX, so a d2 that overflowed to +inf matches nothing.
+ *  2. a matched track takes the detection's box, velocity and score; label and id stay; age = 0, hits += 1.
+ *  3. an unmatched track: age += 1; dropped when age > max_age; else coasted into the current frame, fp64 mul / add, rounded once:
+ *       u = p - t;  v'x = r00 vx + r10 vy, v'y = r01 vx + r11 vy;  x' = (float)(((r00 ux + r10 uy) + r20 uz) + v'x dt),
+ *       y' = (float)(((r01 ux + r11 uy) + r21 uz) + v'y dt), z' = (float)((r02 ux + r12 uy) + r22 uz), velocity = (float)v',
+ *       yaw' = (float)((double)yaw - atan2(m10, m00)) (not wrapped); size, score, label, id, hits unchanged.
+ *  4. a valid unmatched detection with score >= birth_score starts a track in detection order: id = next_id++, hits = 1, age = 0;
+ *     with the state full it gets no track, consumes no id and is counted in overflow[b].
+ *  5. new state = surviving old tracks in their previous slot order, then the births in detection order; the rest is padding.
+ * Per detection: det_track_id int64 [B][N] (-1: rows >= count, neither matched nor born, overflow), det_hits int32 [B][N] (0 where
+ * there is no track), det_slot int32 [B][N] (slot in the new state or -1); overflow int32 [B].  No fused multiply-add: every column
+ * but the coasted yaw is reproducible bit for bit.  One launch on `stream`, no workspace, no atomics, no allocation, nothing read
+ * back (graph-capturable).  0 <= N <= 4096 (N = 0: the detection pointers may be NULL), 1 <= T <= 1024, C >= 1, max_age >= 0.   */
+int bevf_track_step_f32(const float* boxes, const float* velocities, const float* scores, const int64_t* labels,
+                        const int32_t* count, const double* ego_motion, const float* dt, const float* max_dist, float* track_box,
+                        float* track_vel, float* track_score, int64_t* track_label, int64_t* track_id, int32_t* track_age,
+                        int32_t* track_hits, int32_t* track_count, int64_t* next_id, int64_t* det_track_id, int32_t* det_hits,
+                        int32_t* det_slot, int32_t* overflow, int B, int N, int T, int C, int max_age, float birth_score,
+                        int class_aware, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,9 @@ SIGNATURES = {
     "bevf_version": (C.c_int, []),
     "bevf_last_error": (C.c_char_p, []),
     "bevf_conv2d_nhwc_f32": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
+    "bevf_conv2d_nhwc_f32_if": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bevf_conv2d_bound_f32x2": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bevf_prune_compact_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
     "bevf_stem_pool_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_stem_conv7x7_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "bevf_maxpool3x3s2_nhwc_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p]),
@@ -348,7 +351,10 @@ def _pc(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
 def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, scale, shift, y: Optional[torch.Tensor], *, N: int, H: int,
                 W: int, Cin: int, x_cs: int, Cout: int, y_cs: int, KH: int, KW: int, stride: int, pad: int,
                 relu: bool, res: Optional[torch.Tensor] = None, res_cs: int = 0,
-                colmax: Optional[torch.Tensor] = None, rows_per_group: int = 0, tile: int = 0) -> None:
+                colmax: Optional[torch.Tensor] = None, rows_per_group: int = 0, tile: int = 0,
+                run_if: Optional[torch.Tensor] = None, group_rows: Optional[torch.Tensor] = None) -> None:
+    """run_if: optional int32 device word; the launch does nothing when it reads 0 (decided on the stream, no host read).
+    group_rows: optional int32 [groups] with colmax: tiles whose rows all lie at or past group_rows[g] of their group are skipped."""
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
     M = N * Ho * Wo
@@ -369,8 +375,52 @@ def conv2d_nhwc(x: torch.Tensor, w: torch.Tensor, scale, shift, y: Optional[torc
     dt = x.dtype
     d = ConvDesc(_p(x, dt), _pc(w, w.dtype), _pc(scale), _pc(shift), _p(res, dt), _p(y, dt), _pc(colmax, torch.int32),
                  N, H, W, Cin, x_cs, Ho, Wo, Cout, y_cs, res_cs, KH, KW, stride, pad, int(relu), rows_per_group, tile)
+    if group_rows is not None and (colmax is None or group_rows.numel() < -(-M // rows_per_group)):
+        raise BevfError("conv: group_rows needs colmax and one entry per group")
+    if run_if is not None or group_rows is not None:
+        if split or x.dtype != torch.float32:
+            raise BevfError("conv: run_if / group_rows exist for the exact fp32 kernel only")
+        _call("bevf_conv2d_nhwc_f32_if", C.byref(d), _p(run_if, torch.int32), _pc(group_rows, torch.int32))
+        return
     fn = "bevf_conv2d_nhwc_f32x3" if split else "bevf_conv2d_nhwc_" + _sfx(x)
     _call(fn, C.byref(d))
+
+
+def conv2d_bound(x: torch.Tensor, planes: torch.Tensor, scale, shift, bound_g: torch.Tensor, thr: torch.Tensor,
+                 flag: Optional[torch.Tensor], *, M: int, Cin: int, Cout: int, rows_per_group: int, seed_stride: int = 0,
+                 tile: int = 0) -> None:
+    """Bound pass of the pruned column max over the pointwise layer x [M][Cin] -> Cout channels (bevf_conv2d_bound_f32x2):
+    raises thr [groups][Cout] (int32 bit patterns, zeroed by the caller); seed_stride = 0 also sets flag [M], seed_stride = k > 0
+    runs every k-th row tile and takes flag = None.  planes = split_weights_f32x3 of the layer's filter."""
+    if x.numel() < M * Cin:
+        raise BevfError("conv_bound: input buffer smaller than M*Cin")
+    if planes.dtype != torch.bfloat16 or planes.numel() != 3 * Cout * Cin:
+        raise BevfError(f"conv_bound: planes have {planes.numel()} elements, expected {3 * Cout * Cin} bf16")
+    for v in (scale, shift, bound_g):
+        if v is None or v.numel() != Cout:
+            raise BevfError("conv_bound: scale / shift / bound_g length != Cout")
+    if thr.numel() < -(-M // rows_per_group) * Cout:
+        raise BevfError("conv_bound: threshold buffer too small")
+    if (flag is None) != (seed_stride > 0):
+        raise BevfError("conv_bound: a seed launch takes no flags, a main launch needs them")
+    if flag is not None and flag.numel() < M:
+        raise BevfError("conv_bound: flag buffer smaller than M")
+    d = ConvDesc(_p(x), _pc(planes, torch.bfloat16), _pc(scale), _pc(shift), None, None, _pc(thr, torch.int32),
+                 M, 1, 1, Cin, Cin, 1, 1, Cout, Cout, 0, 1, 1, 1, 0, 1, rows_per_group, tile)
+    _call("bevf_conv2d_bound_f32x2", C.byref(d), _pc(bound_g), _pc(flag, torch.int32), seed_stride)
+
+
+def prune_compact(x: torch.Tensor, flag: torch.Tensor, rp: torch.Tensor, cand: torch.Tensor, rows: torch.Tensor,
+                  overflow: torch.Tensor, B: int, N: int, Cc: int, cap: int) -> None:
+    """flag [B][N] -> cand [B][cap][Cc]: each frame's flagged rows of x [B][N][Cc], then the frame's row 0 up to the next multiple
+    of 128 slots; rows [B] = min(flagged rows, cap) (conv2d_nhwc's group_rows); overflow (int32 word, zeroed by the caller) is set
+    when a frame has more than cap flagged rows.  rp: work, B*(N+1) int32."""
+    if x.numel() < B * N * Cc or flag.numel() < B * N:
+        raise BevfError("prune_compact: x / flag smaller than B*N rows")
+    if rp.numel() < B * (N + 1) or cand.numel() < B * cap * Cc or rows.numel() < B or overflow.numel() < 1:
+        raise BevfError("prune_compact: rp / cand / rows / overflow buffer too small")
+    _call("bevf_prune_compact_f32", _pc(x), _pc(flag, torch.int32), _pc(rp, torch.int32), _pc(cand), _pc(rows, torch.int32),
+          _pc(overflow, torch.int32), B, N, Cc, cap)
 
 
 def wino_filter_transform(w_ohwi: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:

@@ -30,6 +30,11 @@ struct ConvArgs {
   int M, K, tilesM, tilesN;
   int m_split, nbig, tilesN_big;   // hybrid launch: blocks [0,nbig) = big tiles over rows [0,m_split)
   unsigned div_hw_mul, div_hw_sh, div_w_mul, div_w_sh;   // m / (Ho*Wo) and r / Wo as multiply-high + shift
+  const int* run_if;               // optional device word: every workgroup returns at once when it reads 0
+  const int* group_rows;           // optional [groups] (colmax launches): a tile whose rows all lie at or past group_rows[g] of their group returns
+  const float* bound_g;            // bound pass (conv_split.hip): per-channel error factor, row flags, row-tile stride of a seed launch
+  int* flag;
+  int tm_stride;
 };
 
 constexpr int BK = 32;
@@ -87,6 +92,7 @@ static int conv_args_from_desc(const bevf_conv_desc* d, const char* who, int x_e
   a.relu = d->relu; a.rows_per_group = d->rows_per_group;
   a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.tilesM = a.tilesN = 0;
   a.m_split = 0; a.nbig = 0; a.tilesN_big = 0;
+  a.run_if = nullptr; a.group_rows = nullptr; a.bound_g = nullptr; a.flag = nullptr; a.tm_stride = 1;
   div_make(d->Ho * d->Wo, &a.div_hw_mul, &a.div_hw_sh);
   div_make(d->Wo, &a.div_w_mul, &a.div_w_sh);
   return BEVF_OK;

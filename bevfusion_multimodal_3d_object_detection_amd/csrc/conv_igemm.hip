@@ -55,6 +55,10 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& p, float* lds, const i
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);           // scalar: wave-uniform addresses stay in SGPRs
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int m0 = m_lo + tm * BM, n0 = tn * BN;
+  if (p.group_rows) {              // (the entry point made sure that no tile straddles two groups)
+    const int g = m0 / p.rows_per_group;
+    if (m0 - g * p.rows_per_group >= p.group_rows[g]) return;
+  }
 
   // ---- staging role: thread owns 16-B chunk `chunk` of rows srow + 32*j -------------------
   // The A part below is the text of ConvAWalker (conv_common.h), which conv_split uses, kept in place: through the walker hipcc emits
@@ -234,6 +238,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& p, float* lds, const i
 template <typename T, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void conv_igemm(const ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  if (p.run_if && *p.run_if == 0) return;
   const int sid = xcd_remap(blockIdx.x, gridDim.x);
   conv_tile<T, BM, BN, WM, WN>(p, lds, 0, p.M, sid / p.tilesN, sid % p.tilesN);
 }
@@ -242,6 +247,7 @@ __global__ __launch_bounds__(256) void conv_igemm(const ConvArgs p) {
 template <typename T, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void conv_igemm_hybrid(const ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  if (p.run_if && *p.run_if == 0) return;
   if ((int)blockIdx.x < p.nbig) {
     const int sid = xcd_remap(blockIdx.x, p.nbig);
     conv_tile<T, BM, BN, WM, WN>(p, lds, 0, p.m_split, sid / p.tilesN_big, sid % p.tilesN_big);
@@ -289,7 +295,7 @@ static int split_big_mtiles(long long M, int BM, int tilesN_big, int resident = 
 }  // namespace
 
 template <typename T>
-int conv_entry(const bevf_conv_desc* d, void* stream) {
+int conv_entry(const bevf_conv_desc* d, void* stream, const int32_t* run_if = nullptr, const int32_t* group_rows = nullptr) {
   constexpr int ES = (int)sizeof(T);
   ConvArgs a;
   if (const int rc = conv_args_from_desc(d, "conv", ES, ES, &a)) return rc;
@@ -299,6 +305,10 @@ int conv_entry(const bevf_conv_desc* d, void* stream) {
   BEVF_REQUIRE((long long)d->N * d->H * d->W < (1ll << 31), "conv: pixel count overflows int32");
   const long long M = a.M;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  BEVF_REQUIRE(!group_rows || (d->colmax && !d->y && d->rows_per_group % 128 == 0 && d->tile != 2 && d->tile != 6),
+               "conv: group_rows needs colmax without y, rows_per_group %% 128 == 0 and no 256-row tile");
+  a.run_if = run_if;
+  a.group_rows = group_rows;
 
   switch (d->tile) {
     case 0: break;
@@ -356,4 +366,7 @@ int conv_entry(const bevf_conv_desc* d, void* stream) {
 }
 
 extern "C" int bevf_conv2d_nhwc_f32(const bevf_conv_desc* d, void* stream) { return conv_entry<float>(d, stream); }
+extern "C" int bevf_conv2d_nhwc_f32_if(const bevf_conv_desc* d, const int32_t* run_if, const int32_t* group_rows, void* stream) {
+  return conv_entry<float>(d, stream, run_if, group_rows);
+}
 extern "C" int bevf_conv2d_nhwc_bf16(const bevf_conv_desc* d, void* stream) { return conv_entry<__bf16>(d, stream); }

@@ -13,6 +13,7 @@ An engine asked to fold a BatchNorm that is still in train mode (e.g. VFELayer, 
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -222,7 +223,8 @@ def _run_conv(pc: PackedConv, x, y, N, H, W, x_cs=None, y_cs=None, res=None, col
     return ho, wo
 
 
-def _conv_call(pc: PackedConv, x, y, N, H, W, x_cs=None, y_cs=None, res=None, colmax=None, rows_per_group=0, tile=0):
+def _conv_call(pc: PackedConv, x, y, N, H, W, x_cs=None, y_cs=None, res=None, colmax=None, rows_per_group=0, tile=0, run_if=None,
+               group_rows=None):
     if pc.wino:
         L.conv3x3_wino(x, pc.w, pc.scale, pc.shift, y, N=N, H=H, W=W, Cin=pc.cin, x_cs=x_cs or pc.cin, Cout=pc.cout,
                        y_cs=y_cs or pc.cout, relu=pc.relu, res=res, res_cs=pc.cout if res is not None else 0)
@@ -233,7 +235,8 @@ def _conv_call(pc: PackedConv, x, y, N, H, W, x_cs=None, y_cs=None, res=None, co
         return
     L.conv2d_nhwc(x, pc.w, pc.scale, pc.shift, y, N=N, H=H, W=W, Cin=pc.cin, x_cs=x_cs or pc.cin, Cout=pc.cout,
                   y_cs=y_cs or pc.cout, KH=pc.k, KW=pc.k, stride=pc.stride, pad=pc.pad, relu=pc.relu, res=res,
-                  res_cs=pc.cout if res is not None else 0, colmax=colmax, rows_per_group=rows_per_group, tile=tile)
+                  res_cs=pc.cout if res is not None else 0, colmax=colmax, rows_per_group=rows_per_group, tile=tile, run_if=run_if,
+                  group_rows=group_rows)
 
 
 # ---- camera encoder (ref src/encoders.py:133-172) -----------------------------------------------------
@@ -325,6 +328,81 @@ class CameraEncoderEngine(_Engine):
 FUSE_POINTNET_FRONT = True   # inference, fp32: conv1 -> conv2 -> conv3 as one kernel, activations in registers (csrc/pointnet_front.hip)
 
 
+PRUNE_POINTNET_MAX = True    # inference, fp32: conv5's max over points through a bf16 bound pass + the exact kernel on candidate rows only
+PRUNE_MIN_POINTS = 4096      # below this the exact launch over all points is already cheap
+PRUNE_SEED_STRIDE = 4        # the seed launch runs every 4th row tile
+PRUNE_CAP_SHARE = 0.16       # candidate slots per frame, as a share of its points (rounded up to 128)
+# The bound's constants (derivation: DESIGN 3.2a2); csrc/conv_split.hip holds the three that the kernel applies itself.
+PRUNE_REL_TRUNC = 4 * 2.0 ** -18     # two-plane truncation of both operands + the dropped mid*mid product
+PRUNE_REL_ACC = 7 * 2.0 ** -24       # per K: 3 products accumulated with <= 2^-23 each in the bf16 MFMA + the exact kernel's 2^-24
+PRUNE_NORM_INFLATE = 2.0 ** -10      # on |a_p| (kernel) and on bound_g (pack)
+PRUNE_NORM_FLOOR = 2.0 ** -58        # added to |a_p| (kernel)
+PRUNE_VAL_TERM = 2.0 ** -21          # eps += this * |val| (kernel): the fmaf and the +-eps roundings
+
+
+def prune_rel(K: int) -> float:
+    """|approximate - exact accumulator| <= prune_rel(K) * |a_p| * |w_c|."""
+    return PRUNE_REL_TRUNC + PRUNE_REL_ACC * K
+
+
+def prune_cap(N: int) -> int:
+    """Candidate slots per frame of N points: ceil(share * N), rounded up to 128."""
+    return -(-math.ceil(PRUNE_CAP_SHARE * N) // 128) * 128
+
+
+def prune_bound_g(w: torch.Tensor, scale: torch.Tensor, K: int) -> torch.Tensor:
+    """bound_g[c] = prune_rel(K) * |w_c| * |scale_c|, inflated and rounded up to fp32; w: [Cout][K] fp32."""
+    g = prune_rel(K) * w.double().norm(dim=1) * scale.double().abs() * (1.0 + PRUNE_NORM_INFLATE)
+    g32 = g.float()
+    return torch.nextafter(g32, torch.full_like(g32, float("inf"))).contiguous()
+
+
+class PrunedColMax:
+    """max over each frame's rows of relu(x @ w^T * scale + shift) for a pointwise fp32 layer, bit-identical to the layer's colmax
+    launch over all rows: a two-plane bf16 bound pass (seed launch on every k-th row tile, then all rows) flags the rows that can hold
+    a channel's maximum, they are compacted into `cap` slots per frame, and the exact kernel runs on those.  If a frame overflows its
+    slots, a device word lets the full launch run after all.  Nothing is read back and every launch has a fixed grid."""
+
+    def __init__(self, pc: PackedConv):
+        assert pc.k == 1 and pc.relu and not pc.wino and not pc.c3 and pc.w.dtype == torch.float32
+        self.pc = pc
+        self.planes = L.split_weights_f32x3(pc.w)
+        self.g = prune_bound_g(pc.w.view(pc.cout, pc.cin), pc.scale, pc.cin)
+        self._bufs: Dict[str, torch.Tensor] = {}
+
+    def _buf(self, name: str, numel: int, dtype) -> torch.Tensor:
+        t = self._bufs.get(name)
+        if t is None or t.numel() < numel:
+            t = torch.empty(numel, dtype=dtype, device=self.pc.w.device)
+            self._bufs[name] = t
+        return t
+
+    def run(self, x: torch.Tensor, gmax: torch.Tensor, B: int, N: int, cap: Optional[int] = None, tile: int = 0) -> torch.Tensor:
+        """x: [B*N][cin] fp32; gmax: [B][cout] int32, zeroed by the caller.  Returns the overflow word (device, int32).
+        cap / tile: the tests' overrides of the slots per frame and of the bound pass's tile (bevf_conv2d_bound_f32x2)."""
+        pc, M = self.pc, B * N
+        cap = prune_cap(N) if cap is None else cap
+        nthr, nb = B * pc.cout, -(-B // 4) * 4
+        work = self._buf("work", 4 + nb + nthr + M, torch.int32)[:4 + nb + nthr + M]
+        work.zero_()
+        ovf, rows, thr, flag = work[:1], work[4:4 + B], work[4 + nb:4 + nb + nthr], work[4 + nb + nthr:]
+        rp = self._buf("rp", B * (N + 1), torch.int32)
+        cand = self._buf("cand", B * cap * pc.cin, torch.float32)
+        geo = dict(M=M, Cin=pc.cin, Cout=pc.cout, rows_per_group=N, tile=tile)
+        with _span("pointnet_prune_bound"):
+            L.conv2d_bound(x, self.planes, pc.scale, pc.shift, self.g, thr, None, seed_stride=PRUNE_SEED_STRIDE, **geo)
+            L.conv2d_bound(x, self.planes, pc.scale, pc.shift, self.g, thr, flag, **geo)
+        with _span("pointnet_prune_compact"):
+            L.prune_compact(x, flag, rp, cand, rows, ovf, B, N, pc.cin, cap)
+        # the exact kernel on the candidate slots; it skips the tiles past a frame's candidates, so the rows it really multiplies are
+        # known on the device only: a span of its own, outside the roofline's FLOP accounting
+        with _span("pointnet_prune_exact"):
+            _conv_call(pc, cand, None, B * cap, 1, 1, colmax=gmax, rows_per_group=cap, group_rows=rows)
+        with _span("pointnet_prune_fallback"):
+            _conv_call(pc, x, None, M, 1, 1, colmax=gmax, rows_per_group=N, run_if=ovf)
+        return ovf
+
+
 class PointNetEngine(_Engine):
     def pack(self) -> None:
         m = self.module
@@ -341,6 +419,10 @@ class PointNetEngine(_Engine):
         if (FUSE_POINTNET_FRONT and self.dtype == torch.float32 and _CONV_MODE in ("f32", "wino") and self.cin <= 8
                 and len(convs) >= 4 and [c.weight.shape[0] for c in convs[:3]] == [64, 128, 256]):
             self.front = [L.pointnet_front_pack(c.weight.detach().reshape(c.weight.shape[0], -1)) for c in convs[1:3]]
+        # pruned max over points for the last layer (exact fp32 modes only; PRUNE_POINTNET_MAX is read at run time)
+        self.prune = None
+        if self.dtype == torch.float32 and _CONV_MODE in ("f32", "wino"):
+            self.prune = PrunedColMax(self.layers[-1])
 
     def run(self, pts: torch.Tensor, keep_last: bool = False):
         """pts: (B,N,C) contiguous -> (B, feat) global max feature [and the (B*N, feat) last activations].
@@ -380,6 +462,9 @@ class PointNetEngine(_Engine):
             _run_conv(pc, a, o, M, 1, 1)
             a = o
         last = self.layers[-1]
+        if self.prune is not None and PRUNE_POINTNET_MAX and not keep_last and N >= PRUNE_MIN_POINTS:
+            self.prune.run(a, gmax, B, N)
+            return None
         y = self.buf("l_last", M * last.cout) if keep_last else None
         _run_conv(last, a, y, M, 1, 1, colmax=gmax, rows_per_group=N)
         return y

@@ -85,6 +85,13 @@ typedef struct {
   const float* bnb_beta;
 } bevf_conv_desc;
 int bevf_conv2d_nhwc_f32(const bevf_conv_desc* d, void* stream);
+/* The same launch, decided on the device by results computed earlier on the stream, with no host round trip (both optional):
+ * run_if: device word; when it reads 0 every workgroup of the launch returns at once and nothing is written.
+ * group_rows: device array [groups], with colmax and no y only: rows at or past group_rows[g] inside group g are not wanted, and a
+ * tile that holds only such rows is skipped.  Every row of a tile that does run is read, so the caller fills the group's slots up to
+ * the next multiple of 128 with rows that may take part in the max.  rows_per_group % 128 == 0; not with the 256-row tile variants
+ * (tile = 2, 6).  (Arguments, not descriptor fields: the descriptor's layout is pinned by recorded launch traces.) */
+int bevf_conv2d_nhwc_f32_if(const bevf_conv_desc* d, const int32_t* run_if, const int32_t* group_rows, void* stream);
 
 /* The same convolution for the 3x3 / stride 1 / pad 1 layers (ResNet blocks, camera_proj, lidar_upsample, radar_refine,
  * bev_fusion, the fused CenterNet 3x3: ~90 % of the path's FLOPs) as fp32 Winograd F(2x2,3x3), fully fused, on
@@ -671,6 +678,21 @@ int bevf_debug_wino_workgroups(int n);
  * bevf_split_weights_f32x3: [3][Cout][KH][KW][Cin] bf16 (hi, mid, lo).  tile: 0 auto, 1 / 3 / 4 as above.      */
 int bevf_split_weights_f32x3(const float* w, void* planes, size_t n, void* stream);
 int bevf_conv2d_nhwc_f32x3(const bevf_conv_desc* d, void* stream);
+/* Bound pass of the pruned column max: the f32x3 kernel on two planes and three products (hi*hi + hi*mid + mid*hi;
+ * `w` = the planes of bevf_split_weights_f32x3), which stores no y.  For row p and channel c it brackets what bevf_conv2d_nhwc_f32
+ * would compute: val = fma(acc, scale[c], shift[c]), eps = |x_p| * bound_g[c] + 2^-21 |val| with |x_p| the row's Euclidean norm
+ * (summed while the row is staged, inflated by 2^-10), and bound_g[c] >= rel(K) * |w_c| * |scale[c]| from the caller.  It raises
+ * thr = d->colmax [ceil(M/rows_per_group)][Cout] (zeroed by the caller) to max(val - eps, 0) by atomicMax on the bit patterns.
+ * seed_stride = k > 0: only row tiles 0, k, 2k, ... run and only thresholds are written (flag = NULL).  seed_stride = 0: all rows;
+ * flag[p] [M] (zeroed by the caller) is set to 1 when !(val + eps < thr) and !(val + eps <= 0) for some channel, so a NaN or
+ * infinite bound flags the row.  Needs relu = 1, y = res = NULL.  tile: 0 auto, 1 128x128, 4 64x64.                          */
+int bevf_conv2d_bound_f32x2(const bevf_conv_desc* d, const float* bound_g, int32_t* flag, int seed_stride, void* stream);
+/* Compaction for the same: flag [B][N] -> cand [B][cap][C], the flagged rows of x [B][N][C] in order, the remaining slots filled
+ * with the frame's row 0 up to the next multiple of 128 (the rest of the slots is left as it is: group_rows of bevf_conv2d_nhwc_f32_if);
+ * rows[b] = min(flagged rows of frame b, cap); *overflow (zeroed by the caller) is set to 1 when a frame has more than cap
+ * flagged rows.  rp: work, [B][N + 1] int32.  C % 4 == 0, cap % 128 == 0.                                                    */
+int bevf_prune_compact_f32(const float* x, const int32_t* flag, int32_t* rp, float* cand, int32_t* rows, int32_t* overflow, int B,
+                           int N, int C, int cap, void* stream);
 int bevf_stem_conv7x7_bf16out(const float* x, const float* w, const float* scale, const float* shift, void* y, int N,
                               int H, int W, int relu, void* stream);
 /* bf16 stem on the bf16 MFMA (bf16-storage models): x fp32 NCHW (rounded to bf16 while it is staged), filter bank

@@ -123,6 +123,7 @@ SIGNATURES = {
     "bevf_bn_stats_from_partials_f32": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
     "bevf_centernet_decode_work_bytes": (C.c_size_t, [C.c_int] * 5),
     "bevf_centernet_decode_f32": (C.c_int, [C.POINTER(DecodeDesc), C.c_void_p]),
+    "bevf_centernet_decode_rectify_f32": (C.c_int, [C.POINTER(DecodeDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "bevf_centernet_targets_f32": (C.c_int, [C.POINTER(TargetsDesc), C.c_void_p]),
     "bevf_nms_keep_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_boxes_iou_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
@@ -130,6 +131,11 @@ SIGNATURES = {
     "bevf_nms_boxes_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_float] + [C.c_int] * 2 + [C.c_void_p] * 8),
     "bevf_centernet_loss_work_floats": (C.c_size_t, []),
     "bevf_centernet_loss_f32": (C.c_int, [C.POINTER(LossDesc), C.c_void_p]),
+    # ---- IoU-aware head: IoU targets, IoU / DIoU loss ----
+    "bevf_iou_targets_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_void_p]),
+    "bevf_iou_aware_loss_work_floats": (C.c_size_t, [C.c_int]),
+    "bevf_iou_aware_loss_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 4 + [C.c_float] * 6 + [C.c_void_p]),
+    "bevf_iou_aware_loss_bwd_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 4 + [C.c_float] * 6 + [C.c_void_p]),
     "bevf_voxelize_work_bytes": (C.c_size_t, [C.c_int] * 2),
     "bevf_voxelize_f32": (C.c_int, [C.POINTER(VoxelizeDesc), C.c_void_p]),
     "bevf_scatter_voxels_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
@@ -693,10 +699,19 @@ def fill(y: torch.Tensor, v: float):
 
 
 def centernet_decode(pred: dict, K: int, thresh: float, voxel: float, x_min: float, y_min: float,
-                     true_labels: bool = False, raw_scores: bool = False, pool_ind: Optional[torch.Tensor] = None):
+                     true_labels: bool = False, raw_scores: bool = False, pool_ind: Optional[torch.Tensor] = None,
+                     iou: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None):
+    """iou (B,1,H,W) and alpha [C] fp32 on the device: the score-rectifying entry point (bevf_centernet_decode_rectify_f32)."""
     heat = pred["heatmap"]
     B, Cn, H, W = heat.shape
     dev = heat.device
+    if (iou is None) != (alpha is None):
+        raise BevfError("decode: iou and alpha belong together")
+    if iou is not None:
+        if raw_scores:
+            raise BevfError("decode: raw_scores cannot be combined with score rectification")
+        if tuple(iou.shape) != (B, 1, H, W) or alpha.numel() != Cn:
+            raise BevfError(f"decode: iou has shape {tuple(iou.shape)} and alpha {alpha.numel()} entries, expected {(B, 1, H, W)} and {Cn}")
     for k, c in (("offset", 2), ("size", 3), ("rot", 2), ("vel", 2)):
         if tuple(pred[k].shape) != (B, c, H, W):
             raise BevfError(f"decode: {k} has shape {tuple(pred[k].shape)}, expected {(B, c, H, W)}")
@@ -710,7 +725,10 @@ def centernet_decode(pred: dict, K: int, thresh: float, voxel: float, x_min: flo
                    _p(boxes), _p(scores), _p(labels, torch.int64), _p(vels), _p(count, torch.int32),
                    _p(work, torch.uint8), _p(pool_ind, torch.int64), B, Cn, H, W, K, int(true_labels),
                    int(raw_scores), thresh, voxel, x_min, y_min)
-    _call("bevf_centernet_decode_f32", C.byref(d))
+    if iou is None:
+        _call("bevf_centernet_decode_f32", C.byref(d))
+    else:
+        _call("bevf_centernet_decode_rectify_f32", C.byref(d), _pc(iou), _pc(alpha))
     return boxes, scores, labels, vels, count
 
 
@@ -847,6 +865,69 @@ def centernet_loss(pred: dict, tgt: dict, weights) -> torch.Tensor:
     d.work, d.out = _pc(work), _pc(out)
     _call("bevf_centernet_loss_f32", C.byref(d))
     return out
+
+
+def _iou_aware_args(what: str, pred: dict, tgt: dict, pc_range, need_iou: bool, keep: list):
+    """Checked arguments shared by the three IoU-aware entry points: (pointers..., B, K, H, W, x_min, y_min, x_max, y_max); the fp32
+    copies made are appended to `keep`."""
+    off = pred["offset"]
+    if off.dim() != 4 or off.shape[1] != 2:
+        raise BevfError(f"{what}: offset must be (B,2,H,W), got {tuple(off.shape)}")
+    B, _, H, W = off.shape
+    K = tgt["ind"].shape[-1]
+    want = [("size", pred, (B, 3, H, W)), ("rot", pred, (B, 2, H, W)), ("target_offset", tgt, (B, K, 2)), ("target_size", tgt, (B, K, 3)),
+            ("target_rot", tgt, (B, K, 2)), ("ind", tgt, (B, K)), ("reg_mask", tgt, (B, K))]
+    if need_iou:
+        want.insert(0, ("iou", pred, (B, 1, H, W)))
+    for name, src, shp in want:
+        if tuple(src[name].shape) != shp:
+            raise BevfError(f"{what}: {name} has shape {tuple(src[name].shape)}, expected {shp}")
+    if len(pc_range) != 6:
+        raise BevfError(f"{what}: pc_range must be [xmin, ymin, zmin, xmax, ymax, zmax], got {list(pc_range)}")
+
+    def f32(t):
+        t = t.detach().float().contiguous()
+        keep.append(t)
+        return _pc(t)
+    ind = tgt["ind"].to(torch.int64).contiguous()
+    rm = tgt["reg_mask"].to(torch.uint8).contiguous()
+    keep += [ind, rm]
+    ptrs = ([f32(pred["iou"])] if need_iou else []) + [f32(pred[n]) for n in ("offset", "size", "rot")] + \
+        [f32(tgt[n]) for n in ("target_offset", "target_size", "target_rot")] + [_pc(ind, torch.int64), _pc(rm, torch.uint8)]
+    geom = (B, K, H, W, float(pc_range[0]), float(pc_range[1]), float(pc_range[3]), float(pc_range[4]))
+    return ptrs, geom
+
+
+def iou_targets(pred: dict, tgt: dict, pc_range) -> torch.Tensor:
+    """(B, K) fp32: 2 * IoU_bev(predicted box, GT box) - 1 where reg_mask is set, 0 elsewhere (bevf_iou_targets_f32)."""
+    keep = []
+    ptrs, geom = _iou_aware_args("iou_targets", pred, tgt, pc_range, False, keep)
+    out = torch.zeros(geom[0], geom[1], device=pred["offset"].device)
+    if out.numel():
+        _call("bevf_iou_targets_f32", *ptrs, _p(out), *geom)
+    return out
+
+
+def iou_aware_loss(pred: dict, tgt: dict, pc_range, w_iou: float, w_diou: float) -> torch.Tensor:
+    """(3,) device tensor: total, iou_loss, diou_loss (bevf_iou_aware_loss_f32); zeros for an empty batch."""
+    keep = []
+    ptrs, geom = _iou_aware_args("iou_aware_loss", pred, tgt, pc_range, True, keep)
+    dev = pred["offset"].device
+    out = torch.zeros(3, device=dev)
+    if geom[0] * geom[1]:
+        work = torch.empty(max(int(lib().bevf_iou_aware_loss_work_floats(geom[0])), 1), device=dev)
+        _call("bevf_iou_aware_loss_f32", *ptrs, _p(work), _p(out), *geom, float(w_iou), float(w_diou))
+    return out
+
+
+def iou_aware_loss_bwd(pred: dict, tgt: dict, pc_range, w_iou: float, w_diou: float, d_iou, d_offset, d_size) -> None:
+    """d total / d (iou, offset, size) into the zero-filled fp32 maps d_iou, d_offset, d_size (bevf_iou_aware_loss_bwd_f32)."""
+    keep = []
+    ptrs, geom = _iou_aware_args("iou_aware_loss_bwd", pred, tgt, pc_range, True, keep)
+    _need("iou_aware_loss_bwd", d_iou=(d_iou, pred["iou"].numel()), d_offset=(d_offset, pred["offset"].numel()),
+          d_size=(d_size, pred["size"].numel()))
+    if geom[0] * geom[1]:
+        _call("bevf_iou_aware_loss_bwd_f32", *ptrs, _p(d_iou), _p(d_offset), _p(d_size), *geom, float(w_iou), float(w_diou))
 
 
 def centernet_decode_raw(pred: dict, K: int):

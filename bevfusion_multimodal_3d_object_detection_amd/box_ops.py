@@ -170,7 +170,7 @@ def check_nms_args(nms_type, nms_iou_thresh, nms_radius, nms_pre_max, class_awar
 def decode_settings(config: Dict[str, Any], section: str = "inference") -> Dict[str, Any]:
     """Keyword arguments for `decode_centernet_predictions` from `<section>.post_processing` of a reference-style YAML (as a
     dict): score_threshold -> score_thresh, max_detections -> max_detections, nms_threshold -> nms_iou_thresh with
-    nms_type='rotate'.  Missing keys keep the decode's defaults."""
+    nms_type='rotate', iou_rectify -> iou_rectify (a float or a list of floats).  Missing keys keep the decode's defaults."""
     try:
         pp = config[section]["post_processing"]
     except (KeyError, TypeError):
@@ -180,4 +180,7 @@ def decode_settings(config: Dict[str, Any], section: str = "inference") -> Dict[
                             ("nms_threshold", "nms_iou_thresh", float)):
         if key in pp:
             out[name] = cast(pp[key])
+    if pp.get("iou_rectify") is not None:             # IoU-aware score rectification: one exponent, or one per class
+        r = pp["iou_rectify"]
+        out["iou_rectify"] = float(r) if isinstance(r, (int, float)) else [float(a) for a in r]
     return out

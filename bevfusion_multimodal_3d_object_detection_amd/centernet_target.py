@@ -26,15 +26,26 @@ PC_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
 
 def _decode_device(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
                    true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
-                   nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False):
+                   nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False, iou_rectify=None):
     """The decode's device half: padded (boxes, scores, labels, velocities) records and count, nothing read back."""
     box_ops.check_nms_args(nms_type, nms_iou_thresh, nms_radius, nms_pre_max, class_aware, true_labels)
     heat = predictions["heatmap"]
     E.require_cuda(heat)
     pred = {k: predictions[k].float().contiguous() for k in ("heatmap", "offset", "size", "rot", "vel")}
     K = max_detections if nms_type is None else int(nms_pre_max)
-    boxes, scores, labels, vels, count = L.centernet_decode(pred, K, float(score_thresh),
-                                                            float(voxel_size), PC_RANGE[0], PC_RANGE[1], true_labels)
+    if iou_rectify is None:
+        boxes, scores, labels, vels, count = L.centernet_decode(pred, K, float(score_thresh),
+                                                                float(voxel_size), PC_RANGE[0], PC_RANGE[1], true_labels)
+    else:
+        # IoU-aware score rectification (DESIGN.md 3.2m): fused into the decode's first kernel, no extra launch or map
+        from .iou_aware import rectify_alpha
+        alpha = rectify_alpha(iou_rectify, heat.shape[1])
+        if "iou" not in predictions:
+            raise L.BevfError("iou_rectify needs predictions['iou'] (build the detector with iou_head=True)")
+        E.require_cuda(predictions["iou"])
+        boxes, scores, labels, vels, count = L.centernet_decode(
+            pred, K, float(score_thresh), float(voxel_size), PC_RANGE[0], PC_RANGE[1], true_labels,
+            iou=predictions["iou"].float().contiguous(), alpha=torch.tensor(alpha, dtype=torch.float32, device=heat.device))
     if nms_type is not None:
         # box NMS over the count[b] candidates above score_thresh (already in descending score order); the survivors come back
         # compacted and cut to max_detections, and their number replaces `count` (the one value `_decode` reads back)
@@ -46,9 +57,10 @@ def _decode_device(predictions: Dict[str, torch.Tensor], score_thresh: float, ma
 
 def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detections: int, voxel_size: float,
             true_labels: bool = False, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
-            nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+            nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False,
+            iou_rectify=None) -> List[Dict[str, torch.Tensor]]:
     boxes, scores, labels, vels, count = _decode_device(predictions, score_thresh, max_detections, voxel_size, true_labels, nms_type,
-                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware)
+                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware, iou_rectify)
     counts = count.cpu().tolist()                     # the reference syncs here too (mask.sum() == 0, ref :362)
     out = []
     for b, n in enumerate(counts):
@@ -64,25 +76,28 @@ def _decode(predictions: Dict[str, torch.Tensor], score_thresh: float, max_detec
 def decode_padded(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3, max_detections: int = 100,
                   true_labels: bool = False, *, nms_type: Optional[str] = None, nms_iou_thresh: float = 0.5,
                   nms_radius: Optional[float] = None, nms_pre_max: int = 512, class_aware: bool = False,
-                  voxel_size: float = 2.048) -> Dict[str, torch.Tensor]:
+                  voxel_size: float = 2.048, iou_rectify=None) -> Dict[str, torch.Tensor]:
     """`decode_centernet_predictions` without its host read: the padded device records the decode (and the box NMS) compute, as
     {"boxes" (B,K,7), "velocities" (B,K,2), "scores" (B,K), "labels" int64 (B,K), "count" int32 (B,)} with K = max_detections
     (nms_pre_max with an NMS), rows past count[b] not meaningful.  Same keywords and the same launches; nothing is synchronised, so
     decode -> NMS -> `tracking.Tracker.step` runs without a round trip to the host."""
     boxes, scores, labels, vels, count = _decode_device(predictions, score_thresh, max_detections, voxel_size, true_labels, nms_type,
-                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware)
+                                                        nms_iou_thresh, nms_radius, nms_pre_max, class_aware, iou_rectify)
     return {"boxes": boxes, "velocities": vels, "scores": scores, "labels": labels, "count": count}
 
 
 def decode_centernet_predictions(predictions: Dict[str, torch.Tensor], score_thresh: float = 0.3,
                                  max_detections: int = 100, true_labels: bool = False, *, nms_type: Optional[str] = None,
                                  nms_iou_thresh: float = 0.5, nms_radius: Optional[float] = None, nms_pre_max: int = 512,
-                                 class_aware: bool = False) -> List[Dict[str, torch.Tensor]]:
+                                 class_aware: bool = False, iou_rectify=None) -> List[Dict[str, torch.Tensor]]:
     """ref src/centernet_target.py:326-413 (2.048 m cells).  nms_type 'rotate' | 'circle' (opt-in, not in the reference): decode the
     nms_pre_max best peaks, run box NMS over those above score_thresh (box_ops; rotated IoU > nms_iou_thresh, or centres closer
-    than nms_radius metres; class_aware: within a label only, needs true_labels) and return the first max_detections survivors."""
+    than nms_radius metres; class_aware: within a label only, needs true_labels) and return the first max_detections survivors.
+    iou_rectify (opt-in): alpha in [0, 1], or one per class -- a peak of class c that survives the 3x3 keep mask
+    is scored s^(1 - alpha_c) * q^alpha_c, q = clamp((predictions['iou'] + 1) / 2, 0, 1), before the top-K; the threshold, the NMS
+    order and the returned scores are the rectified ones.  None: the unrectified decode, launch for launch and bit for bit."""
     return _decode(predictions, score_thresh, max_detections, 2.048, true_labels, nms_type, nms_iou_thresh, nms_radius,
-                   nms_pre_max, class_aware)
+                   nms_pre_max, class_aware, iou_rectify)
 
 
 def _nms(heat: torch.Tensor, kernel: int = 3) -> torch.Tensor:

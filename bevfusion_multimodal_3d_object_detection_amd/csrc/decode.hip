@@ -43,12 +43,16 @@ struct DecArgs {
   long long* pool_ind;
   int B, C, H, W, K, Kp, poolp, true_labels, raw_scores;
   float thresh, voxel, x_min, y_min;
+  const float* iou; const float* alpha;   // score rectification (RECT kernels only): (B,1,H,W) map, [C] exponents
 };
 
 // stage A: one workgroup per (frame, class), 1024 threads (round 3: 256 before -- a map of 128^2 .. 256^2 scores is walked five times by ONE
 // workgroup and only B*C of them exist, so the walks are latency-bound and the wider workgroup is what parallelism there is)
 constexpr int NTA = 1024;
 // keep mask (ref _nms) -> order-preserving score bits, over the whole chip: a value survives iff it equals the 3x3 max around it, else 0
+// RECT (IoU-aware head): a survivor s of class c becomes s^(1 - alpha[c]) * q^alpha[c] with q = (iou + 1) / 2 clamped
+// to [0, 1] (NaN -> 0) before it is keyed, so every later stage ranks, counts and returns the rectified score; alpha[c] == 0 keeps s
+template <bool RECT>
 __global__ __launch_bounds__(256) void decode_keys(const DecArgs a) {
   const int n = a.H * a.W;
   const long long total = (long long)a.B * a.C * n;
@@ -67,7 +71,16 @@ __global__ __launch_bounds__(256) void decode_keys(const DecArgs a) {
         if ((unsigned)xx < (unsigned)a.W) m = fmaxf(m, hp[yy * a.W + xx]);
       }
     }
-    a.keys[e] = ord_bits(m == v ? v : 0.f);
+    float sc = m == v ? v : 0.f;
+    if constexpr (RECT) {
+      const float al = a.alpha[(int)(bc % a.C)];
+      if (m == v && al != 0.f) {
+        const float t = 0.5f * (a.iou[(size_t)(bc / a.C) * n + i] + 1.f);
+        const float q = (t > 0.f) ? fminf(t, 1.f) : 0.f;
+        sc = powf(v, 1.f - al) * powf(q, al);
+      }
+    }
+    a.keys[e] = ord_bits(sc);
   }
 }
 __global__ __launch_bounds__(NTA) void decode_class_topk(const DecArgs a) {
@@ -203,7 +216,8 @@ extern "C" size_t bevf_centernet_decode_work_bytes(int B, int C, int H, int W, i
   return (size_t)B * C * H * W * sizeof(uint32_t) + (size_t)B * C * K * sizeof(unsigned long long) + 64;
 }
 
-extern "C" int bevf_centernet_decode_f32(const bevf_decode_desc* d, void* stream) {
+// the launches of both entry points; iou == NULL: no rectification
+static int decode_launch(const bevf_decode_desc* d, const float* iou, const float* alpha, void* stream) {
   BEVF_REQUIRE(d && d->heat && d->offset && d->size && d->rot && d->vel, "decode: null prediction pointer");
   BEVF_REQUIRE(d->boxes && d->scores && d->labels && d->velocities && d->count && d->work, "decode: null output/work pointer");
   BEVF_REQUIRE(d->B > 0 && d->C > 0 && d->H > 0 && d->W > 0 && d->K > 0, "decode: empty shape");
@@ -216,6 +230,7 @@ extern "C" int bevf_centernet_decode_f32(const bevf_decode_desc* d, void* stream
   a.B = d->B; a.C = d->C; a.H = d->H; a.W = d->W; a.K = d->K; a.true_labels = d->true_labels; a.raw_scores = d->raw_scores;
   a.pool_ind = (long long*)d->pool_ind;
   a.thresh = d->thresh; a.voxel = d->voxel; a.x_min = d->x_min; a.y_min = d->y_min;
+  a.iou = iou; a.alpha = alpha;
   a.Kp = next_pow2(d->K);
   a.poolp = next_pow2(d->C * d->K);
   BEVF_REQUIRE(a.Kp <= 4096 && a.poolp <= 8192, "decode: K=%d / C*K=%d too large for the LDS sort", d->K, d->C * d->K);
@@ -226,9 +241,18 @@ extern "C" int bevf_centernet_decode_f32(const bevf_decode_desc* d, void* stream
   const size_t ldsA = (size_t)a.Kp * 8 + (256 + 8 + 16) * sizeof(int);
   {
     const long long total = (long long)d->B * d->C * d->H * d->W, g = (total + 255) / 256;
-    hipLaunchKernelGGL(decode_keys, dim3((unsigned)(g < 8192 ? g : 8192)), dim3(256), 0, st, a);
+    if (iou) hipLaunchKernelGGL(decode_keys<true>, dim3((unsigned)(g < 8192 ? g : 8192)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(decode_keys<false>, dim3((unsigned)(g < 8192 ? g : 8192)), dim3(256), 0, st, a);
   }
   hipLaunchKernelGGL(decode_class_topk, dim3(d->B * d->C), dim3(NTA), ldsA, st, a);
   hipLaunchKernelGGL(decode_frame, dim3(d->B), dim3(256), (size_t)a.poolp * 8, st, a);
-  return bevf_check_launch("bevf_centernet_decode_f32");
+  return bevf_check_launch(iou ? "bevf_centernet_decode_rectify_f32" : "bevf_centernet_decode_f32");
+}
+
+extern "C" int bevf_centernet_decode_f32(const bevf_decode_desc* d, void* stream) { return decode_launch(d, nullptr, nullptr, stream); }
+
+extern "C" int bevf_centernet_decode_rectify_f32(const bevf_decode_desc* d, const float* iou, const float* alpha, void* stream) {
+  BEVF_REQUIRE(iou && alpha, "decode_rectify: null iou / alpha pointer");
+  BEVF_REQUIRE(d && !d->raw_scores, "decode_rectify: raw_scores ranks the heatmap as given and cannot be combined with rectification");
+  return decode_launch(d, iou, alpha, stream);
 }

@@ -1366,6 +1366,37 @@ class SegHeadEngine(_Engine):
         return out
 
 
+# ---- IoU-aware head (iou_head.IoUHead) ---------------------------------------------------------------------
+
+class IoUHeadEngine(_Engine):
+    """Eval mode: the branch's conv3x3 + bias + ReLU as a packed convolution, its 1x1 layer padded with zero rows to
+    depth_net_width (the route of the seg head's last layer; bevf_head_tail_f32 is laid out for the five detection branches), then
+    the NHWC -> NCHW copy of the first column.  fp32 or bf16 storage; the map comes out fp32."""
+
+    def pack(self) -> None:
+        br = self.module.branch
+        self.c1 = pack_conv(br[0], None, True)
+        self.Kp = depth_net_width(1)
+        w, b = pad_depth_net(br[2], self.Kp)
+        self.c2 = _finish_pack(w.permute(0, 2, 3, 1).contiguous().view(-1), torch.ones(self.Kp, device=w.device), b, w.shape[1],
+                               self.Kp, 1, 1, 0, False, split_ok=False, wino_ok=False)
+
+    def run(self, bev_nhwc: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """bev_nhwc: the flat NHWC map [B][H][W][in_channels] in the storage dtype -> (B, 1, H, W) fp32."""
+        self.ensure_packed()
+        Cc, P = self.module.in_channels, H * W
+        if bev_nhwc.dtype != self.dtype or bev_nhwc.numel() < B * P * Cc:
+            raise L.BevfError(f"IoUHead: expected a {self.dtype} NHWC map of {B} x {H} x {W} x {Cc} elements, got {bev_nhwc.dtype} x "
+                              f"{bev_nhwc.numel()}")
+        hid = self.buf("iou_hid", B * P * self.c1.cout)
+        _run_conv(self.c1, bev_nhwc, hid, B, H, W)
+        cols = self.buf("iou_cols", B * P * self.Kp)
+        _run_conv(self.c2, hid, cols, B, H, W)
+        out = torch.empty(B, 1, H, W, device=bev_nhwc.device)
+        L.nhwc_to_nchw(cols.float(), out, B, 1, P, self.Kp)
+        return out
+
+
 # ---- layout helpers at the API surface ----------------------------------------------------------------------
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import engine as E
 from . import camera_rig as CR
+from . import iou_head as IH
 from . import seg_head as SH
 from . import temporal as T
 from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, SparseLiDAREncoder,  # noqa: F401
@@ -377,7 +378,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  fusion_type: Optional[str] = None, detection_head: Optional[str] = None,
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
-                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None, seg_head=None):
+                 camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None, seg_head=None,
+                 iou_head=None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -448,6 +450,12 @@ class FlexibleMultiModal3DDetector(nn.Module):
         if seg is not None:
             self.seg_head = SH.BEVSegmentationHead(in_channels=self.fusion.bev_channels, pc_range=self.fusion.pc_range,
                                                    bev_h=self.fusion.bev_h, bev_w=self.fusion.bev_w, **seg)
+        # opt-in IoU-aware head on the fused map: iou_head=True / dict, or model.iou_head.enable; adds the keys
+        # iou_head.branch.{0,2}.{weight,bias} and the 'iou' output, nothing else
+        self.iou_head = None
+        iou = IH.iou_head_settings(iou_head, config)
+        if iou is not None:
+            self.iou_head = IH.IoUHead(in_channels=self.fusion.bev_channels, config=config, **iou)
 
     def camera_calib_tensor(self, camera_imgs, camera_calib):
         """`camera_calib=` of forward checked against the camera input (FlexibleBEVFusion.camera_calib_tensor); None without
@@ -494,6 +502,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
         train mode, where the history is a constant), to hand back as prev_bev for the next frame.
         A model built with seg_head= returns 'seg' as well, in eval and train mode: the map-segmentation logits
         (B, num_classes, Ho, Wo) in fp32 of seg_head.BEVSegmentationHead on the fused map.
+        A model built with iou_head= returns 'iou' as well, in eval and train mode: the (B, 1, H, W) fp32 map of
+        iou_head.IoUHead, 2 * IoU - 1 of the box regressed at each cell (iou_aware.IoUAwareLoss, the decode's iou_rectify=).
         camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame.
@@ -553,7 +563,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        if history is None and self.seg_head is None:
+        if history is None and self.seg_head is None and self.iou_head is None:
             fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
             return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
         fus = self.fusion
@@ -561,6 +571,8 @@ class FlexibleMultiModal3DDetector(nn.Module):
         out = self.det_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
         if self.seg_head is not None:                                   # the fused map's second consumer
             out["seg"] = self.seg_head.forward_nhwc(fused, B)
+        if self.iou_head is not None:                                   # and the IoU-aware head
+            out["iou"] = self.iou_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
         if history is not None:
             out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
         return out
@@ -670,7 +682,7 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
                     lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
-                    temporal: Optional[bool] = None, seg_head=None, **kwargs) -> FlexibleMultiModal3DDetector:
+                    temporal: Optional[bool] = None, seg_head=None, iou_head=None, **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
@@ -679,7 +691,11 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
     'mean').
     temporal: True adds the history slot of temporal BEV fusion (None: the config's model.bev_fusion.temporal.enable, else off).
     seg_head: True, or a dict of {num_classes | classes, output_range, output_size, hidden_channels}, adds the BEV map-segmentation
-    head (seg_head.BEVSegmentationHead) on the fused map and the 'seg' output (None: the config's model.seg_head.enable, else off)."""
+    head (seg_head.BEVSegmentationHead) on the fused map and the 'seg' output (None: the config's model.seg_head.enable, else off).
+    iou_head: True, or a dict of {head_conv}, adds the IoU-aware head (iou_head.IoUHead) on the fused map and the 'iou' output
+    (None: the config's model.iou_head.enable, else off)."""
+    if iou_head is not None:
+        kwargs["iou_head"] = iou_head
     if temporal is not None:
         kwargs["temporal"] = temporal
     if seg_head is not None:

@@ -1550,6 +1550,35 @@ class SegHeadTape:
         return dx
 
 
+class IoUHeadTape:
+    """IoUHead (iou_head.py) on an NHWC map [B*H*W*Cin]: conv3x3 + bias + ReLU, then the 1x1 layer padded to
+    engine.depth_net_width (_PaddedDepthNet, as SegHeadTape's last layer) -> (B, 1, H, W)."""
+
+    def __init__(self, head):
+        self.head = head
+
+    def forward(self, x, B, H, W):
+        br = self.head.branch
+        self.B, self.H, self.W, self.Kp = B, H, W, E.depth_net_width(1)
+        self.c1 = ConvBNLayer(br[0], None, True)
+        self.padded = _PaddedDepthNet(br[2], self.Kp)
+        self.c2 = ConvBNLayer(self.padded, None, relu=False)
+        hid, _, _ = self.c1.forward(x, B, H, W)
+        cols, _, _ = self.c2.forward(hid, B, H, W)
+        out = torch.empty(B, 1, H, W, device=x.device)
+        L.nhwc_to_nchw(cols, out, B, 1, H * W, self.Kp)
+        return out
+
+    def backward(self, dout, sink: GradSink):
+        """dout (B, 1, H, W) -> the gradient of the input NHWC map."""
+        B, P = self.B, self.H * self.W
+        dcols = torch.zeros(B * P * self.Kp, device=dout.device)                 # the padding columns carry no gradient
+        L.nchw_to_nhwc(dout.contiguous().float(), dcols, B, 1, P, self.Kp)
+        dhid, _ = self.c2.backward(dcols, self.padded.sink(sink))
+        dx, _ = self.c1.backward(dhid, sink)
+        return dx
+
+
 # ---- the detector ------------------------------------------------------------------------------------------------------------------
 
 class DetectorTape:
@@ -1610,19 +1639,29 @@ class DetectorTape:
         if getattr(m, "seg_head", None) is not None:  # the fused map's second consumer; 'seg' is appended: the positions above stay
             self.seg = SegHeadTape(m.seg_head)
             outs = outs + [self.seg.forward(fused, B)]
+        self.iou = None
+        if getattr(m, "iou_head", None) is not None:  # one more consumer of the fused map; 'iou' is appended after 'seg'
+            self.iou = IoUHeadTape(m.iou_head)
+            outs = outs + [self.iou.forward(fused, B, self.fusion.H, self.fusion.W)]
         return outs
 
     def backward(self, douts: List[torch.Tensor], sink: GradSink) -> list:
         if self.depth_sup is not None:
             self.fusion.branches[0].depth_grad = douts[5]
-        if self.seg is None:
+        if self.seg is None and self.iou is None:
             dfused, pre_f2 = self.head.backward(douts[:5], sink, fuse_next=self.fusion.f2)
         else:
-            # two consumers of `fused`: the head's fused BatchNorm-backward partials would cover its own share only, so the head
-            # returns a plain data gradient, the seg head's is added, and f2 runs its own BatchNorm backward over the sum
+            # several consumers of `fused`: the head's fused BatchNorm-backward partials would cover its own share only, so the head
+            # returns a plain data gradient, the seg head's and the IoU head's are added, and f2 runs its own BatchNorm backward
+            # over the sum
             dfused, pre_f2 = self.head.backward(douts[:5], sink)
-            if douts[-1] is not None:
-                add_(dfused, self.seg.backward(douts[-1], sink), self.fusion.B * self.fusion.H * self.fusion.W * self.fusion.cout)
+            nf = self.fusion.B * self.fusion.H * self.fusion.W * self.fusion.cout
+            d_iou = douts[-1] if self.iou is not None else None
+            d_seg = None if self.seg is None else (douts[-2] if self.iou is not None else douts[-1])
+            if d_seg is not None:
+                add_(dfused, self.seg.backward(d_seg, sink), nf)
+            if d_iou is not None:
+                add_(dfused, self.iou.backward(d_iou, sink), nf)
 
         def camera(dfeat):
             sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
@@ -1720,7 +1759,9 @@ def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_su
     if depth_sup is not None:
         res["depth_loss"], res["depth_pixels"] = outs[5], tape.depth_out[1].clone()
     if tape.seg is not None:
-        res["seg"] = outs[-1]
+        res["seg"] = outs[-2] if tape.iou is not None else outs[-1]
+    if tape.iou is not None:
+        res["iou"] = outs[-1]
     if history is not None:
         from .temporal import own_bev
         fus = model.fusion
@@ -1955,6 +1996,22 @@ def seg_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+
+
+def iou_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:
+    """IoUHead.forward with a gradient path (no BatchNorm: the eval-mode values) -> (B, 1, H, W), with gradients for the parameters
+    and for the BEV map `x` (B, C, H, W)."""
+    B, Cin, H, W = x.shape
+    tape = IoUHeadTape(head)
+
+    def fwd(x):
+        return (tape.forward(_nhwc(x.detach()), B, H, W),)
+
+    def bwd(douts, sink):
+        return [E.to_nchw(tape.backward(douts[0], sink), B, Cin, H, W)]
+
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
+    return out
 
 
 # ---- loss with gradient ------------------------------------------------------------------------------------------------------------

@@ -238,6 +238,11 @@ typedef struct {
 } bevf_decode_desc;
 size_t bevf_centernet_decode_work_bytes(int B, int C, int H, int W, int K);
 int bevf_centernet_decode_f32(const bevf_decode_desc* d, void* stream);
+/* The same decode with IoU-aware score rectification (same descriptor, launches and work buffer; raw_scores must be 0): a cell
+ * of class c that survives the 3x3 keep mask is scored s^(1 - alpha[c]) * q^alpha[c], q = clamp((iou + 1) / 2, 0, 1) with
+ * NaN -> 0, before any top-K; alpha[c] == 0 leaves s bit for bit.  iou: (B,1,H,W) device map, alpha: [C] device floats in
+ * [0, 1] (the caller checks the range).  scores / count / order are those of the rectified score.                          */
+int bevf_centernet_decode_rectify_f32(const bevf_decode_desc* d, const float* iou, const float* alpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training targets, ref src/centernet_target.py:170-324 (+ gaussian_radius :128-150, gaussian_2d :118-125,
@@ -321,6 +326,39 @@ typedef struct {
 } bevf_loss_desc;
 size_t bevf_centernet_loss_work_floats(void);
 int bevf_centernet_loss_f32(const bevf_loss_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * IoU-aware head, training side (no counterpart in the reference; CenterPoint's IoU-aware variant).  For every object
+ * (b, k) with reg_mask set, at the cell ind = cy * W + cx, on cells of vx = (x_max - x_min) / W by vy = (y_max - y_min) / H:
+ *   predicted box: x = (cx + offset[0]) * vx + x_min, y likewise, w = size[0], l = size[1], yaw = atan2f(rot[0], rot[1]);
+ *   GT box: the same from target_offset / target_size / target_rot;
+ *   t = 2 * IoU_bev(pred, gt) - 1 (the rotated IoU of bevf_boxes_iou_f32 on the raw sizes: w <= 0 or l <= 0 gives IoU 0).
+ * bevf_iou_targets_f32: out[B][K] = t where reg_mask is set, else 0.
+ * bevf_iou_aware_loss_f32: out[3] = (w_iou * iou_loss + w_diou * diou_loss, iou_loss, diou_loss) with
+ *   iou_loss  = sum |iou_map[b][cell] - t| / (sum reg_mask + 1e-4)            (t is a constant),
+ *   diou_loss = sum (1 - d) / (sum reg_mask + 1e-4), d = inter / (union + 1e-6) - rho^2 / (c^2 + 1e-6) of the GT rectangle
+ *   and the predicted one taken parallel to it, both in the GT box's frame ((sin, cos) = target_rot), the predicted sizes
+ *   clamped below at 1e-3; rho = centre distance, c = diagonal of the smallest enclosing rectangle.
+ *   work: bevf_iou_aware_loss_work_floats(B) floats.
+ * bevf_iou_aware_loss_bwd_f32: d out[0] / d (iou map, offset, size) stored at the objects' cells of the zero-filled maps
+ *   d_iou (B,1,H,W), d_offset (B,2,H,W), d_size (B,3,H,W; channel 2 stays 0); nothing flows to rot.  K <= 2048.
+ * No float atomics: objects that share a cell are summed in ascending k, the loss sums in a fixed order -- two runs are
+ * bit-equal.  Objects whose ind lies outside [0, H*W) are skipped.  Nothing is read back; graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+int bevf_iou_targets_f32(const float* offset, const float* size, const float* rot, const float* target_offset,
+                         const float* target_size, const float* target_rot, const int64_t* ind, const uint8_t* reg_mask,
+                         float* out, int B, int K, int H, int W, float x_min, float y_min, float x_max, float y_max,
+                         void* stream);
+size_t bevf_iou_aware_loss_work_floats(int B);
+int bevf_iou_aware_loss_f32(const float* iou, const float* offset, const float* size, const float* rot,
+                            const float* target_offset, const float* target_size, const float* target_rot,
+                            const int64_t* ind, const uint8_t* reg_mask, float* work, float* out, int B, int K, int H, int W,
+                            float x_min, float y_min, float x_max, float y_max, float w_iou, float w_diou, void* stream);
+int bevf_iou_aware_loss_bwd_f32(const float* iou, const float* offset, const float* size, const float* rot,
+                                const float* target_offset, const float* target_size, const float* target_rot,
+                                const int64_t* ind, const uint8_t* reg_mask, float* d_iou, float* d_offset, float* d_size,
+                                int B, int K, int H, int W, float x_min, float y_min, float x_max, float y_max, float w_iou,
+                                float w_diou, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Hard voxelisation: points -> the (voxel_features, voxel_coords) layout of

@@ -4,6 +4,8 @@
 //                                      sample of cell k in fp64 (the kernel's own prologue -- nothing is built on the host, so the
 //                                      op sits inside a captured graph), then the wave walks the cells with each sample read back as
 //                                      scalars and the lanes move the channels 16 bytes at a time; a scalar tail takes C % (16 bytes).
+//                                      The axis samples and the candidate ranges are here; the stages shared with the ego-motion
+//                                      warp (forward skeleton, corner rows, channel walk, backward accumulation) in bev_resample.h.
 //   bevf_bev_grid_resample_bwd_f32     the transpose as a pull, no atomics: one wave per SOURCE cell; the contributing output rows and
 //                                      columns are contiguous ranges found from the inverse scalar map (widened by one, every candidate
 //                                      re-checked with the forward's own sample), summed in row-major target order.
@@ -12,12 +14,10 @@
 //   bevf_seg_iou_counts                TP / FP / FN per (threshold, class): wave ballots -> LDS counters -> one 64-bit integer atomic
 //                                      per counter and workgroup (integer sums: the same bits in any order).
 // All HBM-bound or tiny; no MFMA.
-#include "common.h"
+#include "bev_resample.h"
 
 namespace {
 
-constexpr int CELLS_PER_BLOCK = 4;   // waves per 256-thread block: one source cell each in the resample backward ...
-constexpr int CELLS_PER_WAVE = 4;    // ... and this many output cells each in the forward
 constexpr int FOCAL_MAX_BLOCKS = 1024;
 constexpr int SEG_MAX_CLASSES = 64;
 constexpr int IOU_MAX_THRESHOLDS = 32;
@@ -67,108 +67,21 @@ __device__ __forceinline__ double axis_factor(const AxisSample& s, int src) {
   return 0.0;
 }
 
-template <typename T, int Q>
-__device__ __forceinline__ void load_q(const T* p, float (&f)[Q]) {
-  if constexpr (Q == 1) {
-    f[0] = (float)p[0];
-  } else if constexpr (sizeof(T) == 4) {
-    static_assert(Q == 4, "fp32 moves as channel quads");
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < Q; ++k) f[k] = v[k];
-  } else {
-    static_assert(Q == 8, "bf16 moves as eight channels");
-    load16(p, f);
-  }
-}
-
-template <typename T, int Q>
-__device__ __forceinline__ void store_q(T* p, const float (&f)[Q]) {
-  if constexpr (Q == 1) {
-    p[0] = (T)f[0];
-  } else if constexpr (sizeof(T) == 4) {
-    f32x4 v;
-#pragma unroll
-    for (int k = 0; k < Q; ++k) v[k] = f[k];
-    // non-temporal: the 328 MB output of the 128^2 -> 200^2 map at B = 8 passes the 256 MiB cache (152 -> 93 us)
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-  } else {
-    store16(p, f);
-  }
-}
-
-// Channels [c0, c1) of one output row, Q at a time per lane: the four corner rows weighed and summed in the corner order
-// (i0,j0), (i0,j0+1), (i0+1,j0), (i0+1,j0+1), one product and three fmas in fp32 -- the arithmetic of bev_warp.
-template <typename T, int Q>
-__device__ __forceinline__ void resample_channels(const T* (&src)[4], const bool (&in)[4], const float (&w)[4], T* dst, int c0,
-                                                  int c1, int lane) {
-  for (int c = c0 + lane * Q; c < c1; c += 64 * Q) {
-    float v[4][Q], o[Q];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (in[k]) {
-        load_q<T, Q>(src[k] + c, v[k]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) v[k][q] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      float a = w[0] * v[0][q];
-      a = fmaf(w[1], v[1][q], a);
-      a = fmaf(w[2], v[2][q], a);
-      o[q] = fmaf(w[3], v[3][q], a);
-    }
-    store_q<T, Q>(dst + c, o);
-  }
-}
-
 // VEC: C's leading multiple of 16 bytes moves as 16-byte accesses (bases and strides allow it, checked by the entry point).
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void bev_grid_resample(const T* __restrict__ x, T* __restrict__ y, ResampleGeom g, int cells, int C,
                                                           int x_cs, int y_cs) {
-#pragma clang fp contract(off)
-  constexpr int Q = vec16<T>::N;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane = (int)(threadIdx.x & 63);
-  const int r0 = (xcd_remap((int)blockIdx.x, (int)gridDim.x) * CELLS_PER_BLOCK + wave) * CELLS_PER_WAVE;
-  if (r0 >= cells) return;
-  const int Ho = g.row.n_out, Wo = g.col.n_out, Hi = g.row.n_in, Wi = g.col.n_in;
-  const int P = Ho * Wo;
-  // lane k < CELLS_PER_WAVE: the samples and the four fp32 weights of cell r0 + k (the same instructions in every lane)
-  const int rl = min(r0 + (lane & (CELLS_PER_WAVE - 1)), cells - 1);
-  const int pl = rl % P;
-  const AxisSample sr = axis_sample(g.row, pl / Wo), sc = axis_sample(g.col, pl % Wo);
-  const bool okl = sr.ok && sc.ok;
-  float wl[4];
-  wl[0] = okl ? (float)((1.0 - sr.f) * (1.0 - sc.f)) : 0.f;
-  wl[1] = okl ? (float)((1.0 - sr.f) * sc.f) : 0.f;
-  wl[2] = okl ? (float)(sr.f * (1.0 - sc.f)) : 0.f;
-  wl[3] = okl ? (float)(sr.f * sc.f) : 0.f;
-  const int cv = VEC ? C / Q * Q : 0;
-#pragma unroll
-  for (int k = 0; k < CELLS_PER_WAVE; ++k) {
-    const int r = r0 + k;
-    if (r >= cells) break;
-    const int i0 = __builtin_amdgcn_readlane(sr.i0, k), j0 = __builtin_amdgcn_readlane(sc.i0, k);
-    const bool ok = __builtin_amdgcn_readlane((int)okl, k) != 0;
-    float w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl[q]), k));
-    const int b = r / P;
-    bool in[4];
-    const T* src[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ii = i0 + (q >> 1), jj = j0 + (q & 1);
-      in[q] = ok && ii >= 0 && ii < Hi && jj >= 0 && jj < Wi;
-      src[q] = x + (size_t)((b * Hi + (in[q] ? ii : 0)) * Wi + (in[q] ? jj : 0)) * (size_t)x_cs;
-    }
-    T* dst = y + (size_t)r * (size_t)y_cs;
-    if (VEC) resample_channels<T, Q>(src, in, w, dst, 0, cv, lane);
-    resample_channels<T, 1>(src, in, w, dst, cv, C, lane);
-  }
+  const int Wo = g.col.n_out, P = g.row.n_out * Wo;
+  resample_forward<T, VEC ? vec16<T>::N : 0, true, true>(x, y, cells, P, g.row.n_in, g.col.n_in, C, x_cs, y_cs, [&](int r) {
+    const int p = r % P;
+    const AxisSample sr = axis_sample(g.row, p / Wo), sc = axis_sample(g.col, p % Wo);
+    CornerSample s;
+    s.i0 = sr.i0, s.j0 = sc.i0;
+    s.ok = sr.ok && sc.ok;
+    s.w[0] = s.w[1] = s.w[2] = s.w[3] = 0.f;
+    if (s.ok) corner_weights(sr.f, sc.f, s.w);
+    return s;
+  });
 }
 
 // Candidate output indices for source index `src` along one axis: q(o) is affine in o, so the o with floor(q) in {src - 1, src} form
@@ -220,21 +133,10 @@ __global__ __launch_bounds__(256) void bev_grid_resample_bwd(const float* __rest
         const int lr = __builtin_ctzll(rmask);
         rmask &= rmask - 1;
         const double rfv = __shfl(rf, lr, 64);
-        const size_t rowbase = (size_t)(ilo + ib + lr) * (size_t)Wo;
+        const int rowbase = (ilo + ib + lr) * Wo + jlo;
         for (int jb = 0; jb < nj; jb += 64) {
           const double cf = jb == 0 ? cf0 : (jb + lane < nj ? axis_factor(axis_sample(g.col, jlo + jb + lane), v) : 0.0);
-          unsigned long long cmask = __ballot(cf != 0.0);
-          while (cmask) {
-            const int lc = __builtin_ctzll(cmask);
-            cmask &= cmask - 1;
-            const float w = (float)(rfv * __shfl(cf, lc, 64));
-            if (c < C) {
-              float d[Q];
-              load_q<float, Q>(dyb + (rowbase + (size_t)(jlo + jb + lc)) * (size_t)dy_cs + c, d);
-#pragma unroll
-              for (int q = 0; q < Q; ++q) acc[q] = fmaf(w, d[q], acc[q]);
-            }
-          }
+          accumulate_targets<Q>(__ballot(cf != 0.0), (float)(rfv * cf), rowbase + jb + lane, dyb, dy_cs, c, c < C, acc);
         }
       }
     }

@@ -197,6 +197,37 @@ def test_entry_points_refuse_what_they_cannot_address(gpu):
     torch.cuda.synchronize()
 
 
+def test_warp_and_grid_resample_agree_bit_for_bit_on_dyadic_shifts(gpu):
+    """The warp under M = identity + translation (tx, ty) is the grid resample onto the same grid moved by (tx, ty).  With origin,
+    cell size and translation all small dyadic rationals every fp64 quantity of both sample paths is exact, so both kernels get
+    the same fp32 weights and add in the same order (the shared stages of csrc/bev_resample.h): forward (fp32, bf16) and backward
+    must agree bit for bit.  Shifts of 0.75 / -1.25 cells and 2.5 / 0.25 cells, and one of 8 cells on the 5 wide grid: all zeros."""
+    B, H, W = 2, 6, 5
+    grid = (-1.5, -1.25, 0.5, 0.5)
+    for C in (4, 68):
+        dy = synth.normal((B * H * W * C,), 13).cuda()
+        for x_cs in (C, C + 8):
+            for tx, ty in ((0.375, -0.625), (1.25, 0.125), (4.0, 0.0)):
+                ego = np.stack([_affine(1, 0, 0, 1, tx, ty)] * B)
+                ego_dev = torch.from_numpy(ego).cuda()
+                out_grid = (grid[0] + tx, grid[1] + ty, grid[2], grid[3])
+                for dtype in (torch.float32, torch.bfloat16):
+                    x = _x(B, H, W, C, x_cs, dtype, 12)[0].cuda()
+                    yw, yr = (torch.full((B * H * W * C,), 777.0, dtype=dtype, device="cuda") for _ in range(2))
+                    L.bev_warp(x.view(-1), yw, ego_dev, B, H, W, C, x_cs, C, grid)
+                    L.bev_grid_resample(x.view(-1), yr, B, H, W, H, W, C, x_cs, C, grid, out_grid)
+                    assert torch.equal(yw, yr), (C, x_cs, tx, ty, dtype)
+                    if tx < 4.0:                                               # not vacuous: something lands, and it is no copy
+                        assert (yw != 0).any() and not torch.equal(yw.view(-1, C), x[:, :C])
+                    else:
+                        assert (yw == 0).all()
+                dxw, dxr = (torch.full((B * H * W * C,), 777.0, device="cuda") for _ in range(2))
+                L.bev_warp_bwd(dy, dxw, ego_dev, B, H, W, C, C, grid, ego)
+                L.bev_grid_resample_bwd(dy, dxr, B, H, W, H, W, C, C, grid, out_grid)
+                assert torch.equal(dxw, dxr), (C, x_cs, tx, ty)
+                assert (dxw != 0).any() if tx < 4.0 else (dxw == 0).all()
+
+
 # ---- the fusion module with a history slot ------------------------------------------------------------------------------------------
 
 S, BC, PC = 12, 32, [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]

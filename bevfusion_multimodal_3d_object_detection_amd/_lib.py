@@ -87,6 +87,12 @@ class LossDesc(C.Structure):
                [("weights", C.c_float * 5)]
 
 
+class DeconvDesc(C.Structure):
+    """bevf_deconv_desc."""
+    _fields_ = [(n, C.c_void_p) for n in ("x", "w", "scale", "shift", "y")] + \
+               [(n, C.c_int32) for n in ("N", "H", "W", "Cin", "x_cs", "Cout", "y_cs", "s", "relu")]
+
+
 _lib: Optional[C.CDLL] = None
 
 # name -> (restype, argtypes); tests/test_abi_and_host.py holds these, and the Structures above, equal to include/bevf.h
@@ -296,6 +302,12 @@ SIGNATURES = {
     "bevf_sweep_pose_chain_f64": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p]),
     # ---- multi-object tracking ----
     "bevf_track_step_f32": (C.c_int, [C.c_void_p] * 21 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p]),
+    # ---- BEV backbone / FPN neck: transposed convolution with kernel = stride (DeconvDesc goes in as an opaque pointer) ----
+    "bevf_deconv_pack_elems": (C.c_size_t, [C.c_int] * 4),
+    "bevf_deconv_pack_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_deconv_pack_bf16": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
+    "bevf_deconv_nhwc_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bevf_deconv_nhwc_bf16": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 
@@ -2070,3 +2082,48 @@ def track_step(boxes, velocities, scores, labels, count, ego_motion, dt, max_dis
           _pc(ego_motion, torch.float64), _pc(dt), _pc(max_dist), *[_pc(state[name], dtype) for name, dtype, _ in TRACK_STATE],
           _pc(state["track_count"], i32), _pc(state["next_id"], i64), *[_pc(out[name], dtype) for name, dtype in TRACK_OUT],
           _pc(out["overflow"], i32), B, N, T, max_dist.numel(), int(max_age), float(birth_score), int(bool(class_aware)))
+
+
+# ---- BEV backbone / FPN neck: transposed convolution with kernel = stride ------------------------------------------------------------
+
+def deconv_check_dims(N: int, H: int, W: int, x_cs: int, y_cs: int, s: int, elem_bytes: int = 4) -> None:
+    """The size rule of bevf_deconv_nhwc_* from the dimensions alone: the kernel addresses both maps with 32-bit offsets."""
+    x_elems, y_elems = N * H * W * x_cs, N * s * H * s * W * y_cs
+    if x_elems >= 1 << 31 or y_elems >= 1 << 31:
+        raise BevfError(f"deconv: N*H*W*x_cs = {x_elems} and N*sH*sW*y_cs = {y_elems} must stay below 2^31 (32-bit offsets)")
+    if max(x_elems, y_elems) * elem_bytes >= 1 << 31:
+        raise BevfError(f"deconv: input / output maps of {x_elems * elem_bytes} / {y_elems * elem_bytes} bytes must stay below 2 GiB "
+                        "(32-bit byte offsets)")
+
+
+def deconv_pack_elems(Cin: int, Cout: int, s: int, dtype=torch.float32) -> int:
+    return int(lib().bevf_deconv_pack_elems(Cin, Cout, s, int(dtype == BF16)))
+
+
+def deconv_pack(w: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """nn.ConvTranspose2d's fp32 (Cin, Cout, s, s) weight -> the packed filter of deconv_nhwc in storage type `dtype`
+    (once per weight version)."""
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise BevfError(f"deconv_pack: need an fp32 (Cin, Cout, s, s) weight, got {w.dtype} {tuple(w.shape)}")
+    if dtype not in (torch.float32, BF16):
+        raise BevfError(f"deconv_pack: unsupported storage dtype {dtype} (fp32 or bf16)")
+    Cin, Cout, s = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    w = w.contiguous()
+    src = _pc(w)
+    out = torch.empty(deconv_pack_elems(Cin, Cout, s, dtype), dtype=dtype, device=w.device)
+    _call("bevf_deconv_pack_" + _sfx(out), src, _p(out, dtype), Cin, Cout, s)
+    return out
+
+
+def deconv_nhwc(x: torch.Tensor, wp: torch.Tensor, scale, shift, y: torch.Tensor, *, N: int, H: int, W: int, Cin: int, x_cs: int,
+                Cout: int, y_cs: int, s: int, relu: bool) -> None:
+    """y [N][sH][sW][y_cs] (Cout channels per pixel written; y may start inside a wider map) = the kernel = stride = s transposed
+    convolution of x [N][H][W][x_cs] with the packed filter `wp` (deconv_pack), then scale / shift (fp32 [Cout] or None) and ReLU.
+    x, wp and y share one storage dtype (fp32 or bf16)."""
+    dt = x.dtype
+    es = 2 if dt == BF16 else 4
+    deconv_check_dims(N, H, W, x_cs, y_cs, s, es)
+    _need("deconv", x=(x, _strided(N * H * W, Cin, x_cs)), wp=(wp, deconv_pack_elems(Cin, Cout, s, dt)),
+          y=(y, _strided(N * H * W * s * s, Cout, y_cs)), scale=(scale, Cout), shift=(shift, Cout))
+    d = DeconvDesc(_p(x, dt), _pc(wp, dt), _pc(scale), _pc(shift), _p(y, dt), N, H, W, Cin, x_cs, Cout, y_cs, s, int(relu))
+    _call("bevf_deconv_nhwc_" + _sfx(x), C.addressof(d))

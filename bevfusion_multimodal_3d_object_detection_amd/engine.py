@@ -1397,6 +1397,107 @@ class IoUHeadEngine(_Engine):
         return out
 
 
+# ---- BEV backbone + FPN neck (bev_backbone.BEVBackbone) ------------------------------------------------------
+
+@dataclass
+class PackedDeconv:
+    w: torch.Tensor          # the packed filter of csrc/deconv.hip (L.deconv_pack)
+    scale: torch.Tensor
+    shift: torch.Tensor
+    cin: int
+    cout: int
+    s: int
+
+
+def _pad_cin(cin: int, dtype) -> int:
+    """Channel stride of an activation the bf16 implicit-GEMM kernel may read: its K step is 64 channels."""
+    return cin if dtype == torch.float32 else -(-cin // 64) * 64
+
+
+class BackboneEngine(_Engine):
+    """Eval mode: every stage's conv3x3 + folded BN + ReLU as a PackedConv (so every conv mode is honoured), every level's
+    kernel = stride transposed convolution + folded BN + ReLU as one csrc/deconv.hip launch that stores into the level's channel
+    slice of the NHWC concat buffer (a stride-1 level is a 1x1 convolution with the transposed weight, stored the same way).
+    fp32 or bf16 storage.  bf16 maps whose channel count is no multiple of 64 are held at a channel stride rounded up to one, the
+    padding zero and the filters zero-padded alike: the bf16 convolution kernels step through 64 channels at a time."""
+
+    def pack(self) -> None:
+        m, dt = self.module, self.dtype
+        self.stages: List[List[PackedConv]] = []
+        self.ups = []
+        for block, deblock in zip(m.backbone.blocks, m.neck.deblocks):
+            mods = list(block)
+            self.stages.append([self._pack_conv(mods[i], mods[i + 1], dt) for i in range(0, len(mods), 3)])
+            dc, bn = deblock[0], deblock[1]
+            w = dc.weight.detach()
+            cin, cout, s = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+            scale, shift = _bn_fold(None, bn, cout, w.device)
+            if s == 1:
+                w1 = torch.zeros(cout, _pad_cin(cin, dt), dtype=w.dtype, device=w.device)
+                w1[:, :cin] = w[:, :, 0, 0].t()
+                self.ups.append(_finish_pack(w1.view(-1), scale, shift, w1.shape[1], cout, 1, 1, 0, True))
+            else:
+                self.ups.append(PackedDeconv(L.deconv_pack(w.float(), dt), scale, shift, cin, cout, s))
+
+    @staticmethod
+    def _pack_conv(conv, bn, dt) -> PackedConv:
+        w = conv.weight.detach()
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        cp = _pad_cin(cin, dt)
+        if cp == cin:
+            return pack_conv(conv, bn, True)
+        scale, shift = _bn_fold(conv.bias, bn, cout, w.device)
+        wp = torch.zeros(cout, 3, 3, cp, dtype=w.dtype, device=w.device)
+        wp[..., :cin] = w.permute(0, 2, 3, 1)
+        return _finish_pack(wp.view(-1), scale, shift, cp, cout, 3, conv.stride[0], conv.padding[0], True)
+
+    def _map(self, name: str, rows: int, Cc: int) -> Tuple[torch.Tensor, int]:
+        """Activation buffer of `rows` pixels of Cc channels -> (buffer, channel stride); zero-filled when (re)made, so that the
+        padding channels of a bf16 map read as zeros for ever (the layers write the first Cc channels only)."""
+        cs = _pad_cin(Cc, self.dtype)
+        key = (rows, cs)
+        if getattr(self, "_map_keys", None) is None:
+            self._map_keys = {}
+        t = self.buf(name, rows * cs)
+        if self._map_keys.get(name) != (key, t.data_ptr()):
+            if cs != Cc:
+                t.zero_()
+            self._map_keys[name] = (key, t.data_ptr())
+        return t, cs
+
+    def run(self, x: torch.Tensor, B: int, H: int, W: int) -> torch.Tensor:
+        """x: the flat NHWC map [B][H][W][in_channels] in the storage dtype -> the flat NHWC concat [B][H][W][out_channels]."""
+        self.ensure_packed()
+        m, dt = self.module, self.dtype
+        Cin, Ct = m.in_channels, m.out_channels
+        if x.dtype != dt or x.numel() < B * H * W * Cin:
+            raise L.BevfError(f"BEVBackbone: expected a {dt} NHWC map of {B} x {H} x {W} x {Cin} elements, got {x.dtype} x {x.numel()}")
+        es = x.element_size()
+        cur, cs, h, w = x, Cin, H, W
+        if _pad_cin(Cin, dt) != Cin:                       # bf16, in_channels % 64 == 32: the one layout copy of this engine
+            cur, cs = self._map("bb_in", B * H * W, Cin)
+            cur[:B * H * W * cs].view(-1, cs)[:, :Cin].copy_(x[:B * H * W * Cin].view(-1, Cin))
+        out = self.buf("bb_concat", B * H * W * Ct)
+        off = 0
+        for i, (stage, up) in enumerate(zip(self.stages, self.ups)):
+            for j, pc in enumerate(stage):
+                ho, wo = (h + 2 - 3) // pc.stride + 1, (w + 2 - 3) // pc.stride + 1
+                y, ycs = self._map(f"bb_{i}_{j % 2}" if j else f"bb_{i}_in", B * ho * wo, pc.cout)
+                _run_conv(pc, cur, y, B, h, w, x_cs=cs, y_cs=ycs)
+                cur, cs, h, w = y, ycs, ho, wo
+            dst = out[off:]
+            if isinstance(up, PackedConv):
+                _run_conv(up, cur, dst, B, h, w, x_cs=cs, y_cs=Ct)
+            else:
+                M = B * h * w
+                with _span("deconv_" + L._sfx(x), flops=2.0 * M * up.s * up.s * up.cout * up.cin,
+                           nbytes=float(es) * M * (up.cin + up.s * up.s * up.cout)):
+                    L.deconv_nhwc(cur, up.w, up.scale, up.shift, dst, N=B, H=h, W=w, Cin=up.cin, x_cs=cs, Cout=up.cout, y_cs=Ct,
+                                  s=up.s, relu=True)
+            off += up.cout
+        return out
+
+
 # ---- layout helpers at the API surface ----------------------------------------------------------------------
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:

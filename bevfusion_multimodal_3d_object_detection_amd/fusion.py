@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from . import engine as E
 from . import camera_rig as CR
+from . import bev_backbone as BB
 from . import iou_head as IH
 from . import seg_head as SH
 from . import temporal as T
@@ -379,7 +380,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
                  camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None, seg_head=None,
-                 iou_head=None):
+                 iou_head=None, bev_backbone=None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -439,8 +440,19 @@ class FlexibleMultiModal3DDetector(nn.Module):
             self.fusion = FlexibleLateFusion()
         else:
             raise ValueError(f"Unknown fusion type: {self.fusion_type}")
+        # opt-in decoder between the fuser and every head: bev_backbone=True / dict, or model.bev_backbone.enable;
+        # adds the keys bev_backbone.{backbone.blocks,neck.deblocks}.* and widens the heads' first convolutions, nothing else
+        self.bev_backbone = None
+        head_channels = self.fusion.bev_channels
+        bb = BB.bev_backbone_settings(bev_backbone, config)
+        if bb is not None:
+            if self.fusion_type != "bev":
+                raise E.L.BevfError("bev_backbone needs the 'bev' fusion")
+            self.bev_backbone = BB.BEVBackbone(in_channels=self.fusion.bev_channels, **bb)
+            self.bev_backbone.check_grid(self.fusion.bev_h, self.fusion.bev_w)
+            head_channels = self.bev_backbone.out_channels
         if self.detection_head_type == "centernet":
-            self.det_head = CenterNetHead(in_channels=self.fusion.bev_channels, num_classes=num_classes, config=config)
+            self.det_head = CenterNetHead(in_channels=head_channels, num_classes=num_classes, config=config)
         else:
             self.det_head = MLPDetectionHead()
         # opt-in second task on the fused map: seg_head=True / dict, or model.seg_head.enable; adds the keys
@@ -448,14 +460,14 @@ class FlexibleMultiModal3DDetector(nn.Module):
         self.seg_head = None
         seg = SH.seg_head_settings(seg_head, config)
         if seg is not None:
-            self.seg_head = SH.BEVSegmentationHead(in_channels=self.fusion.bev_channels, pc_range=self.fusion.pc_range,
+            self.seg_head = SH.BEVSegmentationHead(in_channels=head_channels, pc_range=self.fusion.pc_range,
                                                    bev_h=self.fusion.bev_h, bev_w=self.fusion.bev_w, **seg)
         # opt-in IoU-aware head on the fused map: iou_head=True / dict, or model.iou_head.enable; adds the keys
         # iou_head.branch.{0,2}.{weight,bias} and the 'iou' output, nothing else
         self.iou_head = None
         iou = IH.iou_head_settings(iou_head, config)
         if iou is not None:
-            self.iou_head = IH.IoUHead(in_channels=self.fusion.bev_channels, config=config, **iou)
+            self.iou_head = IH.IoUHead(in_channels=head_channels, config=config, **iou)
 
     def camera_calib_tensor(self, camera_imgs, camera_calib):
         """`camera_calib=` of forward checked against the camera input (FlexibleBEVFusion.camera_calib_tensor); None without
@@ -563,16 +575,19 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        if history is None and self.seg_head is None and self.iou_head is None:
+        if history is None and self.seg_head is None and self.iou_head is None and self.bev_backbone is None:
             fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
             return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
         fus = self.fusion
         fused, B = fus.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None, history)
-        out = self.det_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
+        feat = fused                                                    # what the heads read: the decoder's concat when there is one
+        if self.bev_backbone is not None:
+            feat = self.bev_backbone.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
+        out = self.det_head.forward_nhwc(feat, B, fus.bev_h, fus.bev_w)
         if self.seg_head is not None:                                   # the fused map's second consumer
-            out["seg"] = self.seg_head.forward_nhwc(fused, B)
+            out["seg"] = self.seg_head.forward_nhwc(feat, B)
         if self.iou_head is not None:                                   # and the IoU-aware head
-            out["iou"] = self.iou_head.forward_nhwc(fused, B, fus.bev_h, fus.bev_w)
+            out["iou"] = self.iou_head.forward_nhwc(feat, B, fus.bev_h, fus.bev_w)
         if history is not None:
             out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
         return out
@@ -682,7 +697,8 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
                     detection_head: Optional[str] = None, num_classes: Optional[int] = None,
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
                     lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
-                    temporal: Optional[bool] = None, seg_head=None, iou_head=None, **kwargs) -> FlexibleMultiModal3DDetector:
+                    temporal: Optional[bool] = None, seg_head=None, iou_head=None, bev_backbone=None,
+                    **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
@@ -693,7 +709,11 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
     seg_head: True, or a dict of {num_classes | classes, output_range, output_size, hidden_channels}, adds the BEV map-segmentation
     head (seg_head.BEVSegmentationHead) on the fused map and the 'seg' output (None: the config's model.seg_head.enable, else off).
     iou_head: True, or a dict of {head_conv}, adds the IoU-aware head (iou_head.IoUHead) on the fused map and the 'iou' output
-    (None: the config's model.iou_head.enable, else off)."""
+    (None: the config's model.iou_head.enable, else off).
+    bev_backbone: True, or a dict of bev_backbone.BEVBackbone's settings, puts the multi-scale BEV backbone + FPN neck between the
+    fuser and every head (None: the config's model.bev_backbone.enable, else off)."""
+    if bev_backbone is not None:
+        kwargs["bev_backbone"] = bev_backbone
     if iou_head is not None:
         kwargs["iou_head"] = iou_head
     if temporal is not None:

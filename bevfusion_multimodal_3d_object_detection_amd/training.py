@@ -1579,6 +1579,97 @@ class IoUHeadTape:
         return dx
 
 
+class DeconvBNLayer:
+    """ConvTranspose2d(kernel = stride = s, no bias) -> train-mode BN -> ReLU, written into a channel slice of a wider NHWC map
+    (the FPN neck's concat).  Forward: the raw transposed convolution (csrc/deconv.hip; s = 1: a 1x1 convolution
+    with the transposed weight), BatchNorm over the N*sH*sW rows, then a copy into the slice -- bn_apply has one channel stride
+    for its input and output, and the raw rows are kept for the backward.  Backward: the slice of the concat's gradient copied out,
+    BatchNorm backward, dx = conv(dy, W, k = s, stride s, pad 0) on the forward convolution kernel, dW = that convolution's weight
+    gradient with x and dy swapped."""
+
+    def __init__(self, deconv, bn):
+        self.deconv, self.bn = deconv, bn
+        w = deconv.weight
+        self.cin, self.cout, self.s = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+
+    def forward(self, x, N, H, W, concat, off: int, ctot: int):
+        w, s, cin, cout = self.deconv.weight.detach(), self.s, self.cin, self.cout
+        self.x, self.N, self.H, self.W, self.off, self.ctot = x, N, H, W, off, ctot
+        Mo = N * H * W * s * s
+        if s == 1:
+            raw, _, _ = conv_raw(x, w[:, :, 0, 0].t().contiguous().view(-1), None, N, H, W, cin, cout, 1, 1, 0)
+        else:
+            raw = _new(Mo * cout, x.device)
+            with E._span("deconv_f32", flops=2.0 * Mo * cout * cin, nbytes=4.0 * (N * H * W * cin + Mo * cout)):
+                L.deconv_nhwc(x, L.deconv_pack(w), None, None, raw, N=N, H=H, W=W, Cin=cin, x_cs=cin, Cout=cout, y_cs=cout, s=s,
+                              relu=False)
+        y, self.bns = bn_train_forward(raw, self.bn, Mo, cout, relu=True)
+        concat[:Mo * ctot].view(Mo, ctot)[:, off:off + cout].copy_(y[:Mo * cout].view(Mo, cout))
+        return Mo
+
+    def backward(self, dconcat, sink: GradSink):
+        """dconcat: the gradient of the whole concat [N*sH*sW][ctot] -> the gradient of this layer's input."""
+        s, cin, cout, N, H, W = self.s, self.cin, self.cout, self.N, self.H, self.W
+        Mo = N * H * W * s * s
+        dy = _new(Mo * cout, dconcat.device)
+        dy[:Mo * cout].view(Mo, cout).copy_(dconcat[:Mo * self.ctot].view(Mo, self.ctot)[:, self.off:self.off + cout])
+        dxraw, dgamma, dbeta = bn_train_backward(dy, self.bns, self.bn, relu=True)
+        sink.add(self.bn.weight, dgamma)
+        sink.add(self.bn.bias, dbeta)
+        w = self.deconv.weight
+        if s == 1:
+            dw = conv_wgrad(self.x, dxraw, N, H, W, cin, cout, 1, 1, 0)                          # [cout][1][1][cin]
+            sink.add(w, dw.reshape(cout, cin).t().reshape(w.shape))
+            return conv_dgrad(dxraw, w.detach().permute(1, 0, 2, 3), N, H, W, cin, cout, 1, 1, 0)
+        # the forward k = s, stride s, pad 0 convolution of dy [N][sH][sW][cout] with the same weights, as OHWI [cin][s][s][cout]
+        dw = conv_wgrad(dxraw, self.x, N, s * H, s * W, cout, cin, s, s, 0)                      # [cin][s][s][cout]
+        sink.add(w, dw.permute(0, 3, 1, 2).reshape(w.shape))
+        dx, _, _ = conv_raw(dxraw, w.detach().permute(0, 2, 3, 1).contiguous().view(-1), None, N, s * H, s * W, cout, cin, s, s, 0)
+        return dx
+
+
+class BackboneTape:
+    """bev_backbone.BEVBackbone on an NHWC map [B*H*W*Cin]: per level the stage's ConvBNLayers, then its DeconvBNLayer into the
+    concat [B*H*W*out_channels].  A stage output has two consumers, the next stage and its own deblock: the backward sums the two
+    gradients (add_) before it walks the stage."""
+
+    def __init__(self, mod):
+        self.mod = mod
+
+    def forward(self, x, B, H, W):
+        m = self.mod
+        self.B, self.H, self.W = B, H, W
+        ct = m.out_channels
+        concat = _new(B * H * W * ct, x.device)
+        self.stages, self.ups, self.sizes = [], [], []
+        cur, h, w, off = x, H, W, 0
+        for block, deblock in zip(m.backbone.blocks, m.neck.deblocks):
+            mods = list(block)
+            layers = [ConvBNLayer(mods[i], mods[i + 1], True) for i in range(0, len(mods), 3)]
+            for layer in layers:
+                cur, h, w = layer.forward(cur, B, h, w)
+            up = DeconvBNLayer(deblock[0], deblock[1])
+            up.forward(cur, B, h, w, concat, off, ct)
+            off += up.cout
+            self.stages.append(layers)
+            self.ups.append(up)
+            self.sizes.append(B * h * w * layers[-1].cout)
+        return concat
+
+    def backward(self, dconcat, sink: GradSink, need_dx=True):
+        """dconcat [B*H*W*out_channels] -> the gradient of the input map (None with need_dx=False)."""
+        d_next = None
+        for i in reversed(range(len(self.stages))):
+            d = self.ups[i].backward(dconcat, sink)
+            if d_next is not None:
+                add_(d, d_next, self.sizes[i])
+            layers = self.stages[i]
+            for j in reversed(range(len(layers))):
+                d, _ = layers[j].backward(d, sink, need_dx=need_dx or i > 0 or j > 0)
+            d_next = d
+        return d_next
+
+
 # ---- the detector ------------------------------------------------------------------------------------------------------------------
 
 class DetectorTape:
@@ -1630,6 +1721,10 @@ class DetectorTape:
             fused = self.fusion.forward(cam_feat, cam_geom, lid_feat, rad_feat, B, self.camera_calib if has_cam else None,
                                         self.depth_sup, self.history)
             self.bev = (fused, B)                 # the 'bev' output is copied from it (detector_train_forward)
+        self.bb = None
+        if getattr(m, "bev_backbone", None) is not None:   # the decoder between the fuser and every head; the
+            self.bb = BackboneTape(m.bev_backbone)         # 'bev' output above stays the fuser's map
+            fused = self.bb.forward(fused, B, self.fusion.H, self.fusion.W)
         self.head = HeadTape(m.det_head)
         outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
         if self.depth_sup is not None:
@@ -1648,20 +1743,22 @@ class DetectorTape:
     def backward(self, douts: List[torch.Tensor], sink: GradSink) -> list:
         if self.depth_sup is not None:
             self.fusion.branches[0].depth_grad = douts[5]
-        if self.seg is None and self.iou is None:
+        if self.seg is None and self.iou is None and self.bb is None:
             dfused, pre_f2 = self.head.backward(douts[:5], sink, fuse_next=self.fusion.f2)
         else:
             # several consumers of `fused`: the head's fused BatchNorm-backward partials would cover its own share only, so the head
             # returns a plain data gradient, the seg head's and the IoU head's are added, and f2 runs its own BatchNorm backward
             # over the sum
             dfused, pre_f2 = self.head.backward(douts[:5], sink)
-            nf = self.fusion.B * self.fusion.H * self.fusion.W * self.fusion.cout
+            nf = self.fusion.B * self.fusion.H * self.fusion.W * (self.fusion.cout if self.bb is None else self.bb.mod.out_channels)
             d_iou = douts[-1] if self.iou is not None else None
             d_seg = None if self.seg is None else (douts[-2] if self.iou is not None else douts[-1])
             if d_seg is not None:
                 add_(dfused, self.seg.backward(d_seg, sink), nf)
             if d_iou is not None:
                 add_(dfused, self.iou.backward(d_iou, sink), nf)
+            if self.bb is not None:                     # the heads' producer is the neck's concat: through the decoder to the fuser
+                dfused = self.bb.backward(dfused, sink)
 
         def camera(dfeat):
             sink.ready()              # head, fusion, radar, LiDAR (the 164 MB dense layer): reduce under the camera trunk
@@ -1996,6 +2093,22 @@ def seg_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+
+
+def bev_backbone_train_forward(mod, x: torch.Tensor) -> torch.Tensor:
+    """BEVBackbone.forward under train-mode BatchNorm -> (B, out_channels, H, W), with gradients for the parameters and for the
+    BEV map `x` (B, C, H, W)."""
+    B, Cin, H, W = x.shape
+    tape = BackboneTape(mod)
+
+    def fwd(x):
+        return (E.to_nchw(tape.forward(_nhwc(x.detach()), B, H, W), B, mod.out_channels, H, W),)
+
+    def bwd(douts, sink):
+        return [E.to_nchw(tape.backward(_nhwc(douts[0]), sink), B, Cin, H, W)]
+
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(mod))
+    return out
 
 
 def iou_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:

@@ -1154,6 +1154,38 @@ int bevf_track_step_f32(const float* boxes, const float* velocities, const float
                         int32_t* det_slot, int32_t* overflow, int B, int N, int T, int C, int max_age, float birth_score,
                         int class_aware, void* stream);
 
+/* ==========================================================================================
+ * BEV backbone + FPN neck: transposed convolution with kernel = stride (csrc/deconv.hip).
+ * ========================================================================================== */
+
+/* nn.ConvTranspose2d(Cin, Cout, kernel_size = s, stride = s, bias = False) (+ folded BatchNorm)(+ ReLU) on NHWC maps:
+ *     y[n][s*h + i][s*w + j][co] = act( (sum_ci x[n][h][w][ci] * W[ci][co][i][j]) * scale[co] + shift[co] )
+ * One launch: a GEMM over the N*H*W input pixels whose epilogue scatters each pixel's s*s channel runs to its s*s output pixels (no
+ * intermediate, no shuffle pass).  fp32: v_mfma_f32_32x32x2_f32, exact fp32 products, fp32 accumulate.  bf16: x / y / packed weights
+ * in bf16, v_mfma_f32_32x32x16_bf16, fp32 accumulate, one rounding at the store; scale / shift stay fp32.  `y` may point into a
+ * channel slice of a wider map (y_cs = that map's channel count): only the Cout channels of the slice are written.
+ * `w`: the packed filter made by bevf_deconv_pack_f32 / _bf16 from the module's fp32 (Cin, Cout, s, s) tensor, once per weight
+ * version (bevf_deconv_pack_elems(Cin, Cout, s, bf16) elements of the storage type).
+ * Supported (anything else: BEVF_ERR_UNSUPPORTED with a message, nothing launched): s in {2, 4}; Cin % 32 == 0; Cout % 32 == 0;
+ * x_cs >= Cin, y_cs >= Cout, both multiples of 4 (fp32) / 8 (bf16); x, w, y 16-byte aligned; N*H*W*x_cs and N*sH*sW*y_cs below
+ * 2^31 elements and below 2 GiB (32-bit byte offsets).  s = 1 is a 1x1 convolution: bevf_conv2d_nhwc_* with the transposed weight.
+ * Stream-ordered, no allocation, no atomics, bit-equal run to run, graph-capturable.
+ * (A tagged struct, unlike the descriptors above: it is passed as an opaque pointer by the bindings.) */
+typedef struct bevf_deconv_desc {
+  const void* x;       /* [N][H][W][x_cs], first Cin channels of each pixel are read */
+  const void* w;       /* packed filter */
+  const float* scale;  /* [Cout] or NULL (1) */
+  const float* shift;  /* [Cout] or NULL (0) */
+  void* y;             /* [N][s*H][s*W][y_cs], Cout channels of each pixel are written */
+  int32_t N, H, W, Cin, x_cs, Cout, y_cs, s;
+  int32_t relu;        /* 0: none, 1: ReLU */
+} bevf_deconv_desc;
+size_t bevf_deconv_pack_elems(int Cin, int Cout, int s, int bf16);
+int bevf_deconv_pack_f32(const float* w, float* out, int Cin, int Cout, int s, void* stream);
+int bevf_deconv_pack_bf16(const float* w, void* out, int Cin, int Cout, int s, void* stream);
+int bevf_deconv_nhwc_f32(const bevf_deconv_desc* d, void* stream);
+int bevf_deconv_nhwc_bf16(const bevf_deconv_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 // and a planar vector (velocity, heading): vx' = fmaf(m[1], vy, m[0] * vx), vy' = fmaf(m[5], vy, m[4] * vx).
 // A frame whose 12 floats are exactly the identity is copied, not multiplied (block-uniform branch): its output has the input's bits.
 #include "common.h"
+#include "point_compact.h"
 
 #pragma clang fp contract(off)
 
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void resize_crop_u8(const unsigned char* __res
                                                        const int* __restrict__ bh_, const int* __restrict__ kh_, int ksh,
                                                        const int* __restrict__ bv_, const int* __restrict__ kv_, int ksv, int tilesX) {
   __shared__ unsigned char hbuf[RMAX][CT_][4];
-  __shared__ unsigned int wsum[4];
+  __shared__ unsigned int gsum[4];
   const int tid = threadIdx.x, img = blockIdx.z;
   const int tx = blockIdx.x, ty = blockIdx.y;
   (void)tilesX;
@@ -158,9 +159,9 @@ __global__ __launch_bounds__(256) void resize_crop_u8(const unsigned char* __res
     gray += (unsigned int)((19595 * R + 38470 * G + 7471 * B + 32768) >> 16);   // Pillow's RGB -> L
   }
   for (int o = 32; o > 0; o >>= 1) gray += __shfl_xor(gray, o);                  // <= 1024 * 255 per workgroup
-  if ((tid & 63) == 0) wsum[tid >> 6] = gray;
+  if ((tid & 63) == 0) gsum[tid >> 6] = gray;
   __syncthreads();
-  if (tid == 0) atomicAdd(gray_sum + img, (unsigned long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]));
+  if (tid == 0) atomicAdd(gray_sum + img, (unsigned long long)(gsum[0] + gsum[1] + gsum[2] + gsum[3]));
 }
 
 // ---- photometric jitter, flip, normalise -------------------------------------------------------------------------------------------
@@ -262,67 +263,37 @@ __device__ __forceinline__ void affine_planar(const Affine& a, float& vx, float&
   vx = nx, vy = ny;
 }
 
-constexpr int LFT = 1024;
-struct Range6 {
-  float x0, y0, z0, x1, y1, z1;
-};
+// The compaction's stages are point_compact.h's; here are the keep rule and the store.
 __device__ __forceinline__ bool paf_keep(const float* __restrict__ pts, int i, int n, int C, const Affine& a, const Range6& r, float& px,
                                          float& py, float& pz) {
   if (i >= n) return false;
   px = pts[(size_t)i * C], py = pts[(size_t)i * C + 1], pz = pts[(size_t)i * C + 2];
   affine_point(a, px, py, pz);
-  return px > r.x0 && px < r.x1 && py > r.y0 && py < r.y1 && pz > r.z0 && pz < r.z1;
-}
-__device__ __forceinline__ int frame_points(const int* __restrict__ n_in, int b, int N) {
-  const int n = n_in ? n_in[b] : N;
-  return n < 0 ? 0 : (n > N ? N : n);                                // never past the frame's N rows
+  return in_range(r, px, py, pz);
 }
 // grid (tiles, B); tcount [B][tiles]
-__global__ __launch_bounds__(LFT) void paf_count(const float* __restrict__ pts, const int* __restrict__ n_in, const float* __restrict__ mat,
-                                                 int* __restrict__ tcount, int N, int C, Range6 rg) {
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+__global__ __launch_bounds__(PC_TILE) void paf_count(const float* __restrict__ pts, const int* __restrict__ n_in,
+                                                     const float* __restrict__ mat, int* __restrict__ tcount, int N, int C, Range6 rg) {
+  const int b = blockIdx.y;
   const Affine a = load_affine(mat, b);
   float px, py, pz;
-  const unsigned long long bal =
-      __ballot(paf_keep(pts + (size_t)b * N * C, blockIdx.x * LFT + tid, frame_points(n_in, b, N), C, a, rg, px, py, pz));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  if (tid == 0) {
-    int t = 0;
-    for (int w = 0; w < 16; ++w) t += wsum[w];
-    tcount[(size_t)b * gridDim.x + blockIdx.x] = t;
-  }
+  tile_count(paf_keep(pts + (size_t)b * N * C, blockIdx.x * PC_TILE + threadIdx.x, frame_rows(n_in, b, N), C, a, rg, px, py, pz),
+             tcount + (size_t)b * gridDim.x + blockIdx.x);
 }
 // work [B][N][C]: the frame's survivors, transformed, in point order; count [B]
-__global__ __launch_bounds__(LFT) void paf_compact(const float* __restrict__ pts, const int* __restrict__ n_in,
-                                                   const float* __restrict__ mat, float* __restrict__ work,
-                                                   const int* __restrict__ tcount, int* __restrict__ count, int N, int C, int vc0, int vc1,
-                                                   Range6 rg) {
-  __shared__ int wsum[16], wpre[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t = blockIdx.x, b = blockIdx.y;
+__global__ __launch_bounds__(PC_TILE) void paf_compact(const float* __restrict__ pts, const int* __restrict__ n_in,
+                                                       const float* __restrict__ mat, float* __restrict__ work,
+                                                       const int* __restrict__ tcount, int* __restrict__ count, int N, int C, int vc0,
+                                                       int vc1, Range6 rg) {
+  const int t = blockIdx.x, b = blockIdx.y, i = t * PC_TILE + threadIdx.x;
   const Affine a = load_affine(mat, b);
   const float* const fp = pts + (size_t)b * N * C;
-  const int* const tc = tcount + (size_t)b * gridDim.x;
-  int part = 0;
-  for (int j = tid; j < t; j += LFT) part += tc[j];
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-  if (lane == 0) wpre[wave] = part;
-  const int i = t * LFT + tid;
   float px = 0.f, py = 0.f, pz = 0.f;
-  const bool keep = paf_keep(fp, i, frame_points(n_in, b, N), C, a, rg, px, py, pz);
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, woff = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    off += wpre[w];
-    if (w < wave) woff += wsum[w];
-    tot += wsum[w];
-  }
-  if (keep) {                                                        // off + woff + before < n <= N: inside the frame's work rows
-    float* dst = work + ((size_t)b * N + (off + woff + before)) * C;
+  const bool keep = paf_keep(fp, i, frame_rows(n_in, b, N), C, a, rg, px, py, pz);
+  const int start = tiles_before(tcount + (size_t)b * gridDim.x, t);
+  const TileRank r = tile_rank(keep, start);
+  if (keep) {                                                        // r.row < n <= N: inside the frame's work rows
+    float* dst = work + ((size_t)b * N + r.row) * C;
     dst[0] = px, dst[1] = py, dst[2] = pz;
     for (int c = 3; c < C; ++c) dst[c] = fp[(size_t)i * C + c];
     if (vc0 >= 0) {
@@ -331,20 +302,7 @@ __global__ __launch_bounds__(LFT) void paf_compact(const float* __restrict__ pts
       dst[vc0] = vx, dst[vc1] = vy;
     }
   }
-  if (tid == 0 && t == (int)gridDim.x - 1) count[b] = off + tot;
-}
-// grid (blocks, B): out [B][max_points][C] = the first max_points survivors, then zeros
-__global__ __launch_bounds__(256) void paf_output(const float* __restrict__ work, float* __restrict__ out, const int* __restrict__ count,
-                                                  int N, int C, int max_points) {
-  const int b = blockIdx.y;
-  const int total = count[b];
-  const long long n = (long long)max_points * C;
-  const float* const w = work + (size_t)b * N * C;
-  float* const o = out + (size_t)b * n;
-  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-    const int r = (int)(e / C);
-    o[e] = r < total ? w[e] : 0.f;                                   // r < total <= N: inside the frame's work rows
-  }
+  if (threadIdx.x == 0 && t == (int)gridDim.x - 1) count[b] = start + r.total;
 }
 
 // in place: points [B][N][C]; noise [B][N][3] (or null) scaled by noise_std onto channels 0-2 after the transform
@@ -440,7 +398,7 @@ extern "C" int bevf_jitter_flip_normalize_u8(const unsigned char* x, float* out,
 
 extern "C" size_t bevf_points_affine_work_floats(int B, int N, int C) {
   if (B <= 0 || N < 0 || C <= 0) return 0;
-  return (size_t)B * ((size_t)N * C + (size_t)((N + LFT - 1) / LFT)) + 64;
+  return (size_t)B * ((size_t)N * C + (size_t)point_tiles(N)) + 64;
 }
 
 extern "C" int bevf_points_affine_filter_pad_f32(const float* points, const int32_t* n_in, const float* mat12, float* out, int32_t* count,
@@ -451,18 +409,18 @@ extern "C" int bevf_points_affine_filter_pad_f32(const float* points, const int3
   BEVF_REQUIRE((vel_c0 < 0 && vel_c1 < 0) || (vel_c0 >= 3 && vel_c1 >= 3 && vel_c0 < C && vel_c1 < C && vel_c0 != vel_c1),
                "points_affine_filter_pad: velocity channels must be two distinct channels in [3, C) or both negative");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles = (N + LFT - 1) / LFT;
+  const int tiles = point_tiles(N);
   int* const tcount = reinterpret_cast<int*>(work + (size_t)B * N * C);
-  const Range6 rg = {pc_range6[0], pc_range6[1], pc_range6[2], pc_range6[3], pc_range6[4], pc_range6[5]};
+  const Range6 rg = range6(pc_range6);
   if (tiles > 0) {
-    hipLaunchKernelGGL(paf_count, dim3(tiles, B), dim3(LFT), 0, st, points, n_in, mat12, tcount, N, C, rg);
-    hipLaunchKernelGGL(paf_compact, dim3(tiles, B), dim3(LFT), 0, st, points, n_in, mat12, work, tcount, count, N, C, vel_c0, vel_c1, rg);
+    hipLaunchKernelGGL(paf_count, dim3(tiles, B), dim3(PC_TILE), 0, st, points, n_in, mat12, tcount, N, C, rg);
+    hipLaunchKernelGGL(paf_compact, dim3(tiles, B), dim3(PC_TILE), 0, st, points, n_in, mat12, work, tcount, count, N, C, vel_c0, vel_c1, rg);
   } else {
     (void)hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)B, st);
   }
   const long long n = (long long)max_points * C;
-  hipLaunchKernelGGL(paf_output, dim3((unsigned)((n + 255) / 256 < 512 ? (n + 255) / 256 : 512), B), dim3(256), 0, st, work, out, count, N, C,
-                     max_points);
+  hipLaunchKernelGGL(compact_output<false>, dim3((unsigned)((n + 255) / 256 < 512 ? (n + 255) / 256 : 512), B), dim3(256), 0, st,
+                     (const float*)work, out, (const int*)count, (const long long*)nullptr, N, C, max_points);
   return bevf_check_launch("bevf_points_affine_filter_pad_f32");
 }
 

@@ -27,10 +27,11 @@
 // paste_accept: one workgroup per frame.  All (candidate, GT row) pairs in parallel, then wave 0 walks the candidates in order: an
 //   accepted candidate k is broadcast and the lanes of the later candidates test themselves against it.  Also the exclusive prefix of the
 //   accepted objects' point counts, and the output GT rows.
-// paste_count / paste_compact: the order-preserving compaction of augment.hip's paf_count / paf_compact, with "inside an accepted
-//   pasted box" as the drop rule, written straight into the output.  paste_append: the accepted objects' points (bank row + centre, one
+// paste_count / paste_compact: the order-preserving compaction of point_compact.h with "inside an accepted pasted box" as the drop
+//   rule, written straight into the output.  paste_append: the accepted objects' points (bank row + centre, one
 //   fp32 addition per coordinate) behind the survivors, zeros behind those, and the count.
 #include "common.h"
+#include "point_compact.h"
 
 #pragma clang fp contract(off)
 
@@ -39,7 +40,6 @@ namespace {
 constexpr int PIB_T = 256;    // points per workgroup of points_in_boxes
 constexpr int PIB_CHUNK = 64; // boxes staged per round
 constexpr int KC_MAX = 64;    // candidates per frame (one wave)
-constexpr int PT = 1024;      // points per workgroup of the compaction
 
 struct Box8 {
   float cx, cy, cz, c, s, hl, hw, hh;
@@ -62,10 +62,6 @@ __device__ __forceinline__ bool inside_box(const Box8& q, float px, float py, fl
   const float lx = fmaf(dy, q.s, dx * q.c);
   const float ly = fmaf(dy, q.c, -(dx * q.s));
   return fabsf(lx) <= q.hl && fabsf(ly) <= q.hw && fabsf(dz) <= q.hh;
-}
-__device__ __forceinline__ int frame_rows(const int* __restrict__ n_in, int b, int N) {
-  const int n = n_in ? n_in[b] : N;
-  return n < 0 ? 0 : (n > N ? N : n);                                // never past the frame's N rows
 }
 
 // grid (ceil(N / 256), B).  mask [B][M] (or null): rows < 0 are ignored.  idx [B][N].
@@ -228,57 +224,36 @@ __device__ __forceinline__ bool paste_keep(const float* __restrict__ fp, int i, 
   return true;
 }
 // grid (tiles, B); tcount [B][tiles]
-__global__ __launch_bounds__(PT) void paste_count(const float* __restrict__ pts, const int* __restrict__ n_in,
-                                                  const float* __restrict__ bank_boxes, const int* __restrict__ cand,
-                                                  const int* __restrict__ accepted, int* __restrict__ tcount, int N, int C, int K, int bcol,
-                                                  int Kc) {
+__global__ __launch_bounds__(PC_TILE) void paste_count(const float* __restrict__ pts, const int* __restrict__ n_in,
+                                                       const float* __restrict__ bank_boxes, const int* __restrict__ cand,
+                                                       const int* __restrict__ accepted, int* __restrict__ tcount, int N, int C, int K,
+                                                       int bcol, int Kc) {
   __shared__ Box8 sb[KC_MAX];
-  __shared__ int nb_lds, wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+  __shared__ int nb_lds;
+  const int b = blockIdx.y;
   const int nb = stage_accepted(sb, &nb_lds, bank_boxes, cand, accepted, b, K, bcol, Kc);
-  const unsigned long long bal = __ballot(paste_keep(pts + (size_t)b * N * C, blockIdx.x * PT + tid, frame_rows(n_in, b, N), C, sb, nb));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  if (tid == 0) {
-    int t = 0;
-    for (int w = 0; w < 16; ++w) t += wsum[w];
-    tcount[(size_t)b * gridDim.x + blockIdx.x] = t;
-  }
+  tile_count(paste_keep(pts + (size_t)b * N * C, blockIdx.x * PC_TILE + threadIdx.x, frame_rows(n_in, b, N), C, sb, nb),
+             tcount + (size_t)b * gridDim.x + blockIdx.x);
 }
 // out [B][capacity][C]: survivor number r goes to row r when r < capacity; kept [B] = all survivors
-__global__ __launch_bounds__(PT) void paste_compact(const float* __restrict__ pts, const int* __restrict__ n_in,
-                                                    const float* __restrict__ bank_boxes, const int* __restrict__ cand,
-                                                    const int* __restrict__ accepted, const int* __restrict__ tcount,
-                                                    float* __restrict__ out, int* __restrict__ kept, int N, int C, int K, int bcol, int Kc,
-                                                    int capacity) {
+__global__ __launch_bounds__(PC_TILE) void paste_compact(const float* __restrict__ pts, const int* __restrict__ n_in,
+                                                         const float* __restrict__ bank_boxes, const int* __restrict__ cand,
+                                                         const int* __restrict__ accepted, const int* __restrict__ tcount,
+                                                         float* __restrict__ out, int* __restrict__ kept, int N, int C, int K, int bcol,
+                                                         int Kc, int capacity) {
   __shared__ Box8 sb[KC_MAX];
-  __shared__ int nb_lds, wsum[16], wpre[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t = blockIdx.x, b = blockIdx.y;
+  __shared__ int nb_lds;
+  const int t = blockIdx.x, b = blockIdx.y, i = t * PC_TILE + threadIdx.x;
   const int nb = stage_accepted(sb, &nb_lds, bank_boxes, cand, accepted, b, K, bcol, Kc);
   const float* const fp = pts + (size_t)b * N * C;
-  const int* const tc = tcount + (size_t)b * gridDim.x;
-  int part = 0;
-  for (int j = tid; j < t; j += PT) part += tc[j];
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-  if (lane == 0) wpre[wave] = part;
-  const int i = t * PT + tid;
   const bool keep = paste_keep(fp, i, frame_rows(n_in, b, N), C, sb, nb);
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, woff = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    off += wpre[w];
-    if (w < wave) woff += wsum[w];
-    tot += wsum[w];
-  }
-  const int r = off + woff + before;
-  if (keep && r < capacity) {                                        // i < N and r < capacity: inside both frames' rows
-    float* const dst = out + ((size_t)b * capacity + r) * C;
+  const int start = tiles_before(tcount + (size_t)b * gridDim.x, t);
+  const TileRank r = tile_rank(keep, start);
+  if (keep && r.row < capacity) {                                    // i < N and r.row < capacity: inside both frames' rows
+    float* const dst = out + ((size_t)b * capacity + r.row) * C;
     for (int c = 0; c < C; ++c) dst[c] = fp[(size_t)i * C + c];
   }
-  if (tid == 0 && t == (int)gridDim.x - 1) kept[b] = off + tot;
+  if (threadIdx.x == 0 && t == (int)gridDim.x - 1) kept[b] = start + r.total;
 }
 // grid (blocks, B): rows [kept, kept + total) of out = the accepted objects' points, rows behind them zeros; count [B]
 __global__ __launch_bounds__(256) void paste_append(const float* __restrict__ bank_points, const int* __restrict__ obj_ptr,
@@ -350,7 +325,7 @@ extern "C" int bevf_paste_accept_f32(const float* gt_boxes, const int64_t* gt_la
 
 extern "C" size_t bevf_paste_points_work_ints(int B, int N) {
   if (B <= 0 || N < 0) return 0;
-  return (size_t)B * ((size_t)((N + PT - 1) / PT) + 1);
+  return (size_t)B * ((size_t)point_tiles(N) + 1);
 }
 
 extern "C" int bevf_paste_points_f32(const float* points, const int32_t* n_in, const float* bank_points, const int32_t* obj_ptr,
@@ -362,12 +337,12 @@ extern "C" int bevf_paste_points_f32(const float* points, const int32_t* n_in, c
   BEVF_REQUIRE(B > 0 && B < 65536 && N >= 0 && C >= 3 && K > 0 && Kc > 0 && Kc <= KC_MAX && capacity > 0 && (bank_ncol == 7 || bank_ncol == 9),
                "paste_points: need B > 0, N >= 0, C >= 3, K > 0, 0 < Kc <= 64, capacity > 0, 7 or 9 bank columns");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles = (N + PT - 1) / PT;
+  const int tiles = point_tiles(N);
   int* const tcount = work;
   int* const kept = work + (size_t)B * tiles;
   if (tiles > 0) {
-    hipLaunchKernelGGL(paste_count, dim3(tiles, B), dim3(PT), 0, st, points, n_in, bank_boxes, cand, accepted, tcount, N, C, K, bank_ncol, Kc);
-    hipLaunchKernelGGL(paste_compact, dim3(tiles, B), dim3(PT), 0, st, points, n_in, bank_boxes, cand, accepted, tcount, out, kept, N, C, K,
+    hipLaunchKernelGGL(paste_count, dim3(tiles, B), dim3(PC_TILE), 0, st, points, n_in, bank_boxes, cand, accepted, tcount, N, C, K, bank_ncol, Kc);
+    hipLaunchKernelGGL(paste_compact, dim3(tiles, B), dim3(PC_TILE), 0, st, points, n_in, bank_boxes, cand, accepted, tcount, out, kept, N, C, K,
                        bank_ncol, Kc, capacity);
   } else {
     (void)hipMemsetAsync(kept, 0, sizeof(int32_t) * (size_t)B, st);

@@ -8,6 +8,7 @@
 // lidar_filter_pad: range filter with strict inequalities, order-preserving compaction (wave ballot + block scan),
 //   zero padding / index gather to exactly max_points rows.
 #include "common.h"
+#include "point_compact.h"
 
 namespace {
 
@@ -122,69 +123,25 @@ __global__ __launch_bounds__(256) void resize_normalize_u8_tiled(const unsigned 
 // Three small launches over many workgroups (round 3: the one-workgroup sweep took 190 us for 120 k points): a tile of 1024 points counts its
 // survivors; every tile adds the counts in front of it (<= a few hundred integers), compacts its survivors in point order into `work` and
 // the last one leaves the total; the output rows (survivors then zeros, or the caller's random choice among them) are an elementwise pass.
-constexpr int LFT = 1024;
-__device__ __forceinline__ bool lfp_keep(const float* __restrict__ pts, int i, int N, int C, float x0, float y0, float z0, float x1,
-                                         float y1, float z1) {
+// The stages are point_compact.h's; here are the keep rule and the store.
+__device__ __forceinline__ bool lfp_keep(const float* __restrict__ pts, int i, int N, int C, const Range6& r) {
   if (i >= N) return false;
-  const float px = pts[(size_t)i * C], py = pts[(size_t)i * C + 1], pz = pts[(size_t)i * C + 2];
-  return px > x0 && px < x1 && py > y0 && py < y1 && pz > z0 && pz < z1;         // NaN fails every test, like numpy
+  return in_range(r, pts[(size_t)i * C], pts[(size_t)i * C + 1], pts[(size_t)i * C + 2]);
 }
-__global__ __launch_bounds__(LFT) void lfp_count(const float* __restrict__ pts, int* __restrict__ tcount, int N, int C, float x0, float y0,
-                                                 float z0, float x1, float y1, float z1) {
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long bal = __ballot(lfp_keep(pts, blockIdx.x * LFT + tid, N, C, x0, y0, z0, x1, y1, z1));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  if (tid == 0) {
-    int t = 0;
-    for (int w = 0; w < 16; ++w) t += wsum[w];
-    tcount[blockIdx.x] = t;
-  }
+__global__ __launch_bounds__(PC_TILE) void lfp_count(const float* __restrict__ pts, int* __restrict__ tcount, int N, int C, Range6 rg) {
+  tile_count(lfp_keep(pts, blockIdx.x * PC_TILE + threadIdx.x, N, C, rg), tcount + blockIdx.x);
 }
-__global__ __launch_bounds__(LFT) void lfp_compact(const float* __restrict__ pts, float* __restrict__ work, const int* __restrict__ tcount,
-                                                   int* __restrict__ count, int N, int C, float x0, float y0, float z0, float x1,
-                                                   float y1, float z1) {
-  __shared__ int wsum[16], wpre[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t = blockIdx.x;
-  int part = 0;                                                      // survivors in the tiles in front of this one
-  for (int j = tid; j < t; j += LFT) part += tcount[j];
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-  if (lane == 0) wpre[wave] = part;
-  const int i = t * LFT + tid;
-  const bool keep = lfp_keep(pts, i, N, C, x0, y0, z0, x1, y1, z1);
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, woff = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    off += wpre[w];
-    if (w < wave) woff += wsum[w];
-    tot += wsum[w];
-  }
+__global__ __launch_bounds__(PC_TILE) void lfp_compact(const float* __restrict__ pts, float* __restrict__ work, const int* __restrict__ tcount,
+                                                       int* __restrict__ count, int N, int C, Range6 rg) {
+  const int t = blockIdx.x, i = t * PC_TILE + threadIdx.x;
+  const bool keep = lfp_keep(pts, i, N, C, rg);
+  const int start = tiles_before(tcount, t);
+  const TileRank r = tile_rank(keep, start);
   if (keep) {
-    float* dst = work + (size_t)(off + woff + before) * C;
+    float* dst = work + (size_t)r.row * C;
     for (int c = 0; c < C; ++c) dst[c] = pts[(size_t)i * C + c];
   }
-  if (tid == 0 && t == (int)gridDim.x - 1) *count = off + tot;
-}
-__global__ __launch_bounds__(256) void lfp_output(const float* __restrict__ work, float* __restrict__ out, const int* __restrict__ count,
-                                                  const long long* __restrict__ choice, int C, int max_points) {
-  const int total = *count;
-  const bool gather = choice != nullptr && total >= max_points;
-  const long long n = (long long)max_points * C;
-  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-    const int r = (int)(e / C), c = (int)(e - (long long)r * C);
-    float v = 0.f;
-    if (gather) {
-      const long long s = choice[r];
-      if (s >= 0 && s < total) v = work[(size_t)s * C + c];
-    } else if (r < total) {
-      v = work[(size_t)r * C + c];
-    }
-    out[e] = v;
-  }
+  if (threadIdx.x == 0 && t == (int)gridDim.x - 1) *count = start + r.total;
 }
 
 }  // namespace
@@ -220,17 +177,17 @@ extern "C" int bevf_lidar_filter_pad_f32(const float* points, float* out, int32_
   BEVF_REQUIRE((points || N == 0) && out && count && work && pc_range6, "lidar_filter_pad: null pointer");
   BEVF_REQUIRE(N >= 0 && C >= 3 && max_points > 0, "lidar_filter_pad: need N >= 0, C >= 3, max_points > 0");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles = (N + LFT - 1) / LFT;
+  const int tiles = point_tiles(N);
   int* const tcount = reinterpret_cast<int*>(work + (size_t)N * C);   // the tile counts live behind the compacted rows
-  const float x0 = pc_range6[0], y0 = pc_range6[1], z0 = pc_range6[2], x1 = pc_range6[3], y1 = pc_range6[4], z1 = pc_range6[5];
+  const Range6 rg = range6(pc_range6);
   if (tiles > 0) {
-    hipLaunchKernelGGL(lfp_count, dim3(tiles), dim3(LFT), 0, st, points, tcount, N, C, x0, y0, z0, x1, y1, z1);
-    hipLaunchKernelGGL(lfp_compact, dim3(tiles), dim3(LFT), 0, st, points, work, tcount, count, N, C, x0, y0, z0, x1, y1, z1);
+    hipLaunchKernelGGL(lfp_count, dim3(tiles), dim3(PC_TILE), 0, st, points, tcount, N, C, rg);
+    hipLaunchKernelGGL(lfp_compact, dim3(tiles), dim3(PC_TILE), 0, st, points, work, tcount, count, N, C, rg);
   } else {
     (void)hipMemsetAsync(count, 0, sizeof(int32_t), st);
   }
   const long long n = (long long)max_points * C;
-  hipLaunchKernelGGL(lfp_output, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st, work, out, count,
-                     reinterpret_cast<const long long*>(choice), C, max_points);
+  hipLaunchKernelGGL(compact_output<true>, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st, (const float*)work,
+                     out, (const int*)count, reinterpret_cast<const long long*>(choice), N, C, max_points);
   return bevf_check_launch("bevf_lidar_filter_pad_f32");
 }

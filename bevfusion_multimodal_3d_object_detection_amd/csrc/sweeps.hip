@@ -12,17 +12,13 @@
 //   x' = (float)(((m[0] * (double)x + m[1] * (double)y) + m[2] * (double)z) + m[3])        (rows 1 and 2 alike)
 // in exactly this order with contraction off for the file: the numpy restatement (tests/sweeps_ref.py) reproduces it bit for bit.
 #include "common.h"
+#include "point_compact.h"
 #include "scan_counts.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int MST = 1024;                                            // rows per tile = threads per workgroup
-
-struct Range6 {
-  float x0, y0, z0, x1, y1, z1;
-};
 struct Rigid {
   double m[12];
 };
@@ -31,10 +27,6 @@ __device__ __forceinline__ Rigid load_rigid(const double* __restrict__ mat, size
 #pragma unroll
   for (int i = 0; i < 12; ++i) t.m[i] = mat[16 * sweep + i];
   return t;
-}
-__device__ __forceinline__ int sweep_rows(const int* __restrict__ counts, size_t sweep, int N) {
-  const int n = counts[sweep];
-  return n < 0 ? 0 : (n > N ? N : n);                                // never past the sweep's N rows
 }
 // pts: the sweep's rows.  close_r <= 0 (or NaN) switches the close-point test off; a NaN coordinate fails the range test.
 // V4: C == 4 and 16-byte aligned rows (chosen on the host): the row is one 16-byte load and w is its channel 3.
@@ -54,37 +46,29 @@ __device__ __forceinline__ bool msw_keep(const float* __restrict__ pts, int i, i
   px = (float)(((t.m[0] * dx + t.m[1] * dy) + t.m[2] * dz) + t.m[3]);
   py = (float)(((t.m[4] * dx + t.m[5] * dy) + t.m[6] * dz) + t.m[7]);
   pz = (float)(((t.m[8] * dx + t.m[9] * dy) + t.m[10] * dz) + t.m[11]);
-  return px > r.x0 && px < r.x1 && py > r.y0 && py < r.y1 && pz > r.z0 && pz < r.z1;
+  return in_range(r, px, py, pz);
 }
 
 // grid (tiles, S, B); tcount [B][S * tiles]
 template <bool V4>
-__global__ __launch_bounds__(MST) void msw_count(const float* __restrict__ pts, const int* __restrict__ counts, const double* __restrict__ mat,
-                                                 int* __restrict__ tcount, int N, int C, float close_r, Range6 rg) {
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(PC_TILE) void msw_count(const float* __restrict__ pts, const int* __restrict__ counts,
+                                                     const double* __restrict__ mat, int* __restrict__ tcount, int N, int C, float close_r,
+                                                     Range6 rg) {
   const size_t sweep = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
   const Rigid t = load_rigid(mat, sweep);
   float px, py, pz, w;
-  const unsigned long long bal =
-      __ballot(msw_keep<V4>(pts + sweep * N * C, blockIdx.x * MST + tid, sweep_rows(counts, sweep, N), C, t, close_r, rg, px, py, pz, w));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  if (tid == 0) {
-    int s = 0;
-    for (int w = 0; w < 16; ++w) s += wsum[w];
-    tcount[sweep * gridDim.x + blockIdx.x] = s;
-  }
+  tile_count(msw_keep<V4>(pts + sweep * N * C, blockIdx.x * PC_TILE + threadIdx.x, frame_rows(counts, sweep, N), C, t, close_r, rg, px, py,
+                          pz, w),
+             tcount + sweep * gridDim.x + blockIdx.x);
 }
 
 // grid (tiles, S, B); rp [B][S * tiles + 1] from scan_counts; out [B][max_points][C + 1]; count [B]; sweep_count [B][S]
 template <bool V4>
-__global__ __launch_bounds__(MST) void msw_write(const float* __restrict__ pts, const int* __restrict__ counts, const double* __restrict__ mat,
-                                                 const float* __restrict__ lag, const int* __restrict__ rp, float* __restrict__ out,
-                                                 int* __restrict__ count, int* __restrict__ sweep_count, int N, int C, int max_points,
-                                                 float close_r, Range6 rg) {
-  __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(PC_TILE) void msw_write(const float* __restrict__ pts, const int* __restrict__ counts,
+                                                     const double* __restrict__ mat, const float* __restrict__ lag,
+                                                     const int* __restrict__ rp, float* __restrict__ out, int* __restrict__ count,
+                                                     int* __restrict__ sweep_count, int N, int C, int max_points, float close_r, Range6 rg) {
+  const int tid = threadIdx.x;
   const int tile = blockIdx.x, tiles = gridDim.x, s = blockIdx.y, S = gridDim.y, b = blockIdx.z;
   const size_t sweep = (size_t)b * S + s;
   const int* const frp = rp + (size_t)b * ((size_t)S * tiles + 1);
@@ -96,16 +80,10 @@ __global__ __launch_bounds__(MST) void msw_write(const float* __restrict__ pts, 
   if (start >= max_points) return;                                   // the same in every thread: a truncated tile reads no point
   const Rigid t = load_rigid(mat, sweep);
   const float* const sp = pts + sweep * N * C;
-  const int i = tile * MST + tid;
+  const int i = tile * PC_TILE + tid;
   float px = 0.f, py = 0.f, pz = 0.f, w = 0.f;
-  const bool keep = msw_keep<V4>(sp, i, sweep_rows(counts, sweep, N), C, t, close_r, rg, px, py, pz, w);
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  const int row = start + woff + before;
+  const bool keep = msw_keep<V4>(sp, i, frame_rows(counts, sweep, N), C, t, close_r, rg, px, py, pz, w);
+  const int row = tile_rank(keep, start).row;
   if (keep && row < max_points) {                                    // row < max_points: inside the frame's rows of out
     float* const dst = out + ((size_t)b * max_points + row) * (C + 1);
     dst[0] = px, dst[1] = py, dst[2] = pz;
@@ -189,13 +167,11 @@ __global__ __launch_bounds__(256) void sweep_pose_chain(const double* __restrict
   for (int i = 0; i < 16; ++i) o[i] = t.a[i];
 }
 
-inline int merge_tiles(int N) { return (N + MST - 1) / MST; }
-
 }  // namespace
 
 extern "C" size_t bevf_sweeps_merge_work_bytes(int B, int S, int N) {
   if (B <= 0 || S <= 0 || N < 0) return 0;
-  const size_t per_frame = (size_t)S * merge_tiles(N);
+  const size_t per_frame = (size_t)S * point_tiles(N);
   return sizeof(int32_t) * (size_t)B * (2 * per_frame + 1);         // tcount [B][S * tiles], then rp [B][S * tiles + 1]
 }
 
@@ -208,16 +184,16 @@ extern "C" int bevf_sweeps_merge_f32(const float* points, const int32_t* counts,
                "sweeps_merge: need 0 < B, S < 65536, N >= 0, 3 <= C <= 8, max_points > 0");
   BEVF_REQUIRE((long long)S * N < (1ll << 31) && (long long)B * S < (1ll << 31), "sweeps_merge: S * N and B * S must stay below 2^31");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int tiles = merge_tiles(N);
+  const int tiles = point_tiles(N);
   int* const tcount = static_cast<int*>(work);
   int* const rp = tcount + (size_t)B * S * tiles;
-  const Range6 rg = {pc_range6[0], pc_range6[1], pc_range6[2], pc_range6[3], pc_range6[4], pc_range6[5]};
+  const Range6 rg = range6(pc_range6);
   if (tiles > 0) {
     bevf_dispatch_bool(C == 4 && bevf_aligned16(points), [&](auto v4) {   // a sweep's rows start at a multiple of N * 16 bytes
       constexpr bool V4 = decltype(v4)::value;
-      hipLaunchKernelGGL(msw_count<V4>, dim3(tiles, S, B), dim3(MST), 0, st, points, counts, sweep_to_key, tcount, N, C, close_radius, rg);
+      hipLaunchKernelGGL(msw_count<V4>, dim3(tiles, S, B), dim3(PC_TILE), 0, st, points, counts, sweep_to_key, tcount, N, C, close_radius, rg);
       hipLaunchKernelGGL(scan_counts, dim3(B), dim3(1024), 0, st, (const int32_t*)tcount, S * tiles, rp);
-      hipLaunchKernelGGL(msw_write<V4>, dim3(tiles, S, B), dim3(MST), 0, st, points, counts, sweep_to_key, time_lag, (const int*)rp, out,
+      hipLaunchKernelGGL(msw_write<V4>, dim3(tiles, S, B), dim3(PC_TILE), 0, st, points, counts, sweep_to_key, time_lag, (const int*)rp, out,
                          count, sweep_count, N, C, max_points, close_radius, rg);
       return 0;
     });

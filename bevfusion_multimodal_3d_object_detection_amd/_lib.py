@@ -308,6 +308,15 @@ SIGNATURES = {
     "bevf_deconv_pack_bf16": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_void_p]),
     "bevf_deconv_nhwc_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bevf_deconv_nhwc_bf16": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # ---- CenterPoint second stage: RoI BEV-point gather, targets, loss, refine ----
+    "bevf_roi_bev_points_table_words": (C.c_size_t, [C.c_int] * 2),
+    "bevf_roi_bev_points_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_double] * 4 + [C.c_void_p]),
+    "bevf_roi_bev_points_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_double] * 4 + [C.c_void_p]),
+    "bevf_roi_bev_points_bwd_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
+    "bevf_roi_targets_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "bevf_roi_loss_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_float] * 2 + [C.c_void_p]),
+    "bevf_roi_loss_bwd_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 2 + [C.c_float] * 2 + [C.c_void_p]),
+    "bevf_roi_refine_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
 }
 
 
@@ -2127,3 +2136,139 @@ def deconv_nhwc(x: torch.Tensor, wp: torch.Tensor, scale, shift, y: torch.Tensor
           y=(y, _strided(N * H * W * s * s, Cout, y_cs)), scale=(scale, Cout), shift=(shift, Cout))
     d = DeconvDesc(_p(x, dt), _pc(wp, dt), _pc(scale), _pc(shift), _p(y, dt), N, H, W, Cin, x_cs, Cout, y_cs, s, int(relu))
     _call("bevf_deconv_nhwc_" + _sfx(x), C.addressof(d))
+
+
+# ---- CenterPoint second stage: RoI BEV-point gather, targets, loss, refine (csrc/roi_points.hip, csrc/roi_head.hip) ------------------
+
+ROI_MAX_K = 4096                                 # bevf_roi_refine_f32 stages a frame's scores in LDS (the tracker's limit on N)
+
+
+def _roi_want(what: str, name: str, t, dtype, shape) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise BevfError(f"{what}: {name} must be a {dtype} {tuple(shape)} tensor, got {got}")
+
+
+def _roi_boxes(what: str, boxes, count):
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3 or boxes.shape[2] != 7 or boxes.shape[0] == 0 or boxes.shape[1] == 0:
+        got = tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__
+        raise BevfError(f"{what}: boxes must be a (B,K,7) tensor with B, K > 0, got {got}")
+    B, K = int(boxes.shape[0]), int(boxes.shape[1])
+    _roi_want(what, "boxes", boxes, torch.float32, (B, K, 7))
+    _roi_want(what, "count", count, I32, (B,))
+    return B, K
+
+
+def _roi_range(what: str, bev_range):
+    r = tuple(float(v) for v in bev_range)
+    if len(r) != 4 or r[2] == r[0] or r[3] == r[1]:
+        raise BevfError(f"{what}: bev_range is (x_min, y_min, x_max, y_max) with a non-empty extent, got {tuple(bev_range)}")
+    return r
+
+
+def roi_bev_points_table_words(B: int, K: int) -> int:
+    return int(lib().bevf_roi_bev_points_table_words(B, K))
+
+
+def roi_bev_points(x, boxes, count, feat, table, H: int, W: int, Cc: int, x_cs: int, bev_range) -> None:
+    """feat [B*K][5*Cc] (x's dtype) = the NHWC map x [B][H][W] (Cc channels at stride x_cs) sampled bilinearly at the centre and the
+    four face centres of every RoI (bevf_roi_bev_points_*; the rules: include/bevf.h).  boxes (B,K,7) fp32, count int32 (B,);
+    bev_range = (x_min, y_min, x_max, y_max) of the map.  table: None, or int32 [B*K*5*6] for roi_bev_points_bwd."""
+    B, K = _roi_boxes("roi_bev_points", boxes, count)
+    r = _roi_range("roi_bev_points", bev_range)
+    if x.dtype != feat.dtype:
+        raise BevfError(f"roi_bev_points: x is {x.dtype}, feat is {feat.dtype}")
+    if x_cs < Cc or Cc <= 0 or H <= 0 or W <= 0:
+        raise BevfError(f"roi_bev_points: bad map shape (H={H} W={W} C={Cc} stride={x_cs})")
+    _need("roi_bev_points", x=(x, _strided(B * H * W, Cc, x_cs)), feat=(feat, B * K * 5 * Cc),
+          table=(table, roi_bev_points_table_words(B, K)))
+    if x.untyped_storage().data_ptr() == feat.untyped_storage().data_ptr():
+        raise BevfError("roi_bev_points: x and feat share storage")
+    _call("bevf_roi_bev_points_" + _sfx(x), _p(x, x.dtype), _pc(boxes), _pc(count, I32), _pc(feat, x.dtype), _pc(table, I32), B, K,
+          H, W, Cc, x_cs, *r)
+
+
+def roi_bev_points_bwd(dfeat, table, count, dx, B: int, K: int, H: int, W: int, Cc: int) -> None:
+    """dx [B][H][W][Cc] = the transpose of roi_bev_points applied to dfeat [B*K][5*Cc], through the forward's sample table: a
+    deterministic pull, every element written (bevf_roi_bev_points_bwd_f32, fp32)."""
+    _roi_want("roi_bev_points_bwd", "count", count, I32, (B,))
+    if min(B, K, H, W, Cc) <= 0:
+        raise BevfError(f"roi_bev_points_bwd: bad shape (B={B} K={K} H={H} W={W} C={Cc})")
+    _need("roi_bev_points_bwd", dfeat=(dfeat, B * K * 5 * Cc), table=(table, roi_bev_points_table_words(B, K)), dx=(dx, B * H * W * Cc))
+    _call("bevf_roi_bev_points_bwd_f32", _pc(dfeat), _pc(table, I32), _pc(count, I32), _pc(dx), B, K, H, W, Cc)
+
+
+def roi_targets(boxes, count, roi_labels, gt, gt_labels, use_bev: bool, match_labels: bool, reg_fg_thresh: float) -> dict:
+    """The RoI targets (bevf_roi_targets_f32; the rules: include/bevf.h) of RoIs (B,K,7) / count int32 (B,) against the padded
+    ground truth gt (B,M,7) fp32 / gt_labels int32 (B,M) (-1 = padding; M may be 0).  roi_labels int64 (B,K) with match_labels.
+    Returns {'iou', 'cls_target' (B,K), 'gt_index' int32 (B,K), 'reg_mask' uint8 (B,K), 'reg_target' (B,K,7), 'count'}."""
+    B, K = _roi_boxes("roi_targets", boxes, count)
+    if not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 7:
+        got = tuple(gt.shape) if isinstance(gt, torch.Tensor) else type(gt).__name__
+        raise BevfError(f"roi_targets: gt must be a ({B},M,7) tensor, got {got}")
+    M = int(gt.shape[1])
+    _roi_want("roi_targets", "gt", gt, torch.float32, (B, M, 7))
+    _roi_want("roi_targets", "gt_labels", gt_labels, I32, (B, M))
+    if match_labels:
+        _roi_want("roi_targets", "roi_labels", roi_labels, torch.int64, (B, K))
+    dev = boxes.device
+    out = dict(iou=torch.empty(B, K, device=dev), gt_index=torch.empty(B, K, dtype=I32, device=dev),
+               cls_target=torch.empty(B, K, device=dev), reg_mask=torch.empty(B, K, dtype=torch.uint8, device=dev),
+               reg_target=torch.empty(B, K, 7, device=dev), count=count)
+    _call("bevf_roi_targets_f32", _pc(boxes), _pc(count, I32), _pc(roi_labels, torch.int64) if match_labels else None,
+          _pc(gt) if M else None, _pc(gt_labels, I32) if M else None, _pc(out["iou"]), _pc(out["gt_index"], I32),
+          _pc(out["cls_target"]), _pc(out["reg_mask"], torch.uint8), _pc(out["reg_target"]), B, K, M, int(bool(use_bev)),
+          int(bool(match_labels)), float(reg_fg_thresh))
+    return out
+
+
+def _roi_loss_args(what: str, pred, tgt: dict):
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or pred.shape[2] != 8 or pred.shape[0] == 0 or pred.shape[1] == 0:
+        got = tuple(pred.shape) if isinstance(pred, torch.Tensor) else type(pred).__name__
+        raise BevfError(f"{what}: pred must be a (B,K,8) tensor (the logit, then seven residuals), got {got}")
+    B, K = int(pred.shape[0]), int(pred.shape[1])
+    _roi_want(what, "pred", pred, torch.float32, (B, K, 8))
+    missing = [k for k in ("count", "cls_target", "reg_mask", "reg_target") if k not in tgt]
+    if missing:
+        raise BevfError(f"{what}: targets lack {missing} (build them with roi_refine.roi_targets)")
+    _roi_want(what, "targets['count']", tgt["count"], I32, (B,))
+    _roi_want(what, "targets['cls_target']", tgt["cls_target"], torch.float32, (B, K))
+    _roi_want(what, "targets['reg_mask']", tgt["reg_mask"], torch.uint8, (B, K))
+    _roi_want(what, "targets['reg_target']", tgt["reg_target"], torch.float32, (B, K, 7))
+    return B, K, (_pc(pred), _pc(tgt["count"], I32), _pc(tgt["cls_target"]), _pc(tgt["reg_mask"], torch.uint8), _pc(tgt["reg_target"]))
+
+
+def roi_loss(pred, tgt: dict, w_cls: float, w_reg: float) -> torch.Tensor:
+    """(3,) device tensor: total, cls_loss, reg_loss (bevf_roi_loss_f32)."""
+    B, K, ptrs = _roi_loss_args("roi_loss", pred, tgt)
+    out = torch.empty(3, device=pred.device)
+    _call("bevf_roi_loss_f32", *ptrs, _pc(out), B, K, float(w_cls), float(w_reg))
+    return out
+
+
+def roi_loss_bwd(pred, tgt: dict, w_cls: float, w_reg: float, dpred) -> None:
+    """dpred (B,K,8) = d total / d pred, every element written (bevf_roi_loss_bwd_f32)."""
+    B, K, ptrs = _roi_loss_args("roi_loss_bwd", pred, tgt)
+    _roi_want("roi_loss_bwd", "dpred", dpred, torch.float32, (B, K, 8))
+    _call("bevf_roi_loss_bwd_f32", *ptrs, _pc(dpred), B, K, float(w_cls), float(w_reg))
+
+
+def roi_refine(boxes, scores, labels, velocities, count, pred, score_thresh: float) -> dict:
+    """The refine step (bevf_roi_refine_f32; the rules: include/bevf.h) -> the padded records {'boxes', 'velocities', 'scores',
+    'labels', 'count'}, compacted and in descending final score.  velocities may be None (then the result has none)."""
+    B, K = _roi_boxes("roi_refine", boxes, count)
+    if K > ROI_MAX_K:
+        raise BevfError(f"roi_refine: K={K} exceeds the kernel's {ROI_MAX_K} RoIs per frame")
+    _roi_want("roi_refine", "scores", scores, torch.float32, (B, K))
+    _roi_want("roi_refine", "labels", labels, torch.int64, (B, K))
+    _roi_want("roi_refine", "pred", pred, torch.float32, (B, K, 8))
+    if velocities is not None:
+        _roi_want("roi_refine", "velocities", velocities, torch.float32, (B, K, 2))
+    dev = boxes.device
+    out = dict(boxes=torch.empty(B, K, 7, device=dev), velocities=torch.empty(B, K, 2, device=dev) if velocities is not None else None,
+               scores=torch.empty(B, K, device=dev), labels=torch.empty(B, K, dtype=torch.int64, device=dev),
+               count=torch.empty(B, dtype=I32, device=dev))
+    _call("bevf_roi_refine_f32", _pc(boxes), _pc(scores), _pc(labels, torch.int64), _pc(velocities), _pc(count, I32), _pc(pred),
+          _pc(out["boxes"]), _pc(out["scores"]), _pc(out["labels"], torch.int64), _pc(out["velocities"]), _pc(out["count"], I32), B, K,
+          float(score_thresh))
+    return out

@@ -8,6 +8,8 @@
 namespace {
 
 constexpr int NWG = 256;                 // workgroups of the reduction kernels = partial rows
+constexpr int BN_SLAB = 128;             // channels the BatchNorm reductions take at a time
+constexpr int BN_MAX_C = 1024;
 
 __device__ __forceinline__ bool slot_active(const int32_t* __restrict__ count, int cap, long long row, int& b) {
   b = (int)(row / cap);
@@ -77,14 +79,16 @@ __global__ __launch_bounds__(256) void sp_canvas_bwd(const float* __restrict__ d
 // takes slots g * lanes + rl, + NWG * lanes, ... of every frame in frame order; the row lanes are then added in lane order.
 //   MODE 0  (sum y, sum y^2): the batch statistics
 //   MODE 1  (sum g, sum g x_hat) with g = da through the recomputed ReLU mask: the BatchNorm backward's two sums
+// One slab of Cs <= 128 channels starting at channel cb of rows that are Cr channels wide (Cs = Cr, cb = 0 up to 128 channels).
 template <int MODE>
-__global__ __launch_bounds__(256) void sp_bn_sums(const float* __restrict__ y, const float* __restrict__ da,
-                                                  const int32_t* __restrict__ count, int B, int cap, int C,
-                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                  double* __restrict__ part) {
-  __shared__ double red[256 * 2];
+__device__ __forceinline__ void sp_bn_sums_slab(const float* __restrict__ y, const float* __restrict__ da,
+                                                const int32_t* __restrict__ count, int B, int cap, int Cr, int cb, int C,
+                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                double* __restrict__ part, double* red) {
   const int tid = threadIdx.x, lanes = 256 / C, c = tid % C, rl = tid / C;
+  y += cb, part += (size_t)cb * 2;
+  if (MODE == 1) da += cb, mean += cb, invstd += cb, gamma = gamma ? gamma + cb : gamma, beta = beta ? beta + cb : beta;
   double s1 = 0.0, s2 = 0.0;
   if (rl < lanes) {
     float mu = 0.f, is = 1.f, fa = 1.f, fb = 0.f;
@@ -97,7 +101,7 @@ __global__ __launch_bounds__(256) void sp_bn_sums(const float* __restrict__ y, c
     for (int b = 0; b < B; ++b) {
       const int n = count[b] < cap ? count[b] : cap;
       for (int v = blockIdx.x * lanes + rl; v < n; v += NWG * lanes) {
-        const size_t o = ((size_t)b * cap + v) * C + c;
+        const size_t o = ((size_t)b * cap + v) * Cr + c;
         const float yv = y[o];
         if (MODE == 0) {
           s1 += (double)yv;
@@ -119,8 +123,22 @@ __global__ __launch_bounds__(256) void sp_bn_sums(const float* __restrict__ y, c
       t1 += red[(l * C + tid) * 2];
       t2 += red[(l * C + tid) * 2 + 1];
     }
-    part[((size_t)blockIdx.x * C + tid) * 2] = t1;
-    part[((size_t)blockIdx.x * C + tid) * 2 + 1] = t2;
+    part[((size_t)blockIdx.x * Cr + tid) * 2] = t1;
+    part[((size_t)blockIdx.x * Cr + tid) * 2 + 1] = t2;
+  }
+}
+
+// Rows wider than 128 channels (the RoI head's MLP) go slab by slab; up to 128 it is the one slab it always was.
+template <int MODE>
+__global__ __launch_bounds__(256) void sp_bn_sums(const float* __restrict__ y, const float* __restrict__ da,
+                                                  const int32_t* __restrict__ count, int B, int cap, int C,
+                                                  const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  double* __restrict__ part) {
+  __shared__ double red[256 * 2];
+  for (int cb = 0; cb < C; cb += BN_SLAB) {
+    if (cb) __syncthreads();   // (red is reused)
+    sp_bn_sums_slab<MODE>(y, da, count, B, cap, C, cb, C - cb < BN_SLAB ? C - cb : BN_SLAB, mean, invstd, gamma, beta, part, red);
   }
 }
 
@@ -130,12 +148,11 @@ __global__ __launch_bounds__(128) void sp_bn_stats_finish(const double* __restri
                                                           int C, float eps, float momentum, float* rmean, float* rvar, long long* nbt,
                                                           float* __restrict__ mean, float* __restrict__ invstd,
                                                           int32_t* __restrict__ nrows_out) {
-  const int c = threadIdx.x;
   long long N = 0;
   for (int b = 0; b < B; ++b) N += count[b] < cap ? count[b] : cap;
   const long long nb_old = nbt ? *nbt : 0;
   __syncthreads();
-  if (c < C) {
+  for (int c = threadIdx.x; c < C; c += BN_SLAB) {
     double s1 = 0.0, s2 = 0.0;
     for (int g = 0; g < NWG; ++g) {
       s1 += part[((size_t)g * C + c) * 2];
@@ -153,7 +170,7 @@ __global__ __launch_bounds__(128) void sp_bn_stats_finish(const double* __restri
       rvar[c] = (float)((1.0 - mo) * (double)rvar[c] + mo * var * (double)N / (double)(N - 1));
     }
   }
-  if (c == 0) {
+  if (threadIdx.x == 0) {
     if (nbt && N > 1) *nbt = nb_old + 1;
     if (nrows_out) *nrows_out = (int32_t)(N < 0x7fffffff ? N : 0x7fffffff);
   }
@@ -179,20 +196,20 @@ __global__ __launch_bounds__(256) void sp_bn_apply(const float* __restrict__ y, 
 __global__ __launch_bounds__(128) void sp_bn_bwd_finish(const double* __restrict__ part, const int32_t* __restrict__ count, int B, int cap,
                                                         int C, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                         float* __restrict__ sd, float* __restrict__ sx) {
-  const int c = threadIdx.x;
   long long N = 0;
   for (int b = 0; b < B; ++b) N += count[b] < cap ? count[b] : cap;
-  if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int g = 0; g < NWG; ++g) {
-    s1 += part[((size_t)g * C + c) * 2];
-    s2 += part[((size_t)g * C + c) * 2 + 1];
+  for (int c = threadIdx.x; c < C; c += BN_SLAB) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int g = 0; g < NWG; ++g) {
+      s1 += part[((size_t)g * C + c) * 2];
+      s2 += part[((size_t)g * C + c) * 2 + 1];
+    }
+    const double inv = N > 0 ? 1.0 / (double)N : 0.0;
+    dbeta[c] = (float)s1;
+    dgamma[c] = (float)s2;
+    sd[c] = (float)(s1 * inv);
+    sx[c] = (float)(s2 * inv);
   }
-  const double inv = N > 0 ? 1.0 / (double)N : 0.0;
-  dbeta[c] = (float)s1;
-  dgamma[c] = (float)s2;
-  sd[c] = (float)(s1 * inv);
-  sx[c] = (float)(s2 * inv);
 }
 
 // dy = gamma invstd (g - sd - x_hat sx) (bn_dx), or gamma invstd g when the statistics are frozen
@@ -219,9 +236,9 @@ __global__ __launch_bounds__(256) void sp_bn_bwd_apply(const float* __restrict__
   *reinterpret_cast<f32x4*>(dy + (size_t)row * C + c) = o;
 }
 
-int rows_check(const char* who, int B, int cap, int C) {
+int rows_check(const char* who, int B, int cap, int C, int max_c = 128) {
   BEVF_REQUIRE(B > 0 && cap > 0, "%s: empty shape", who);
-  BEVF_REQUIRE(C > 0 && C <= 128 && C % 32 == 0, "%s: C=%d must be a multiple of 32 up to 128", who, C);
+  BEVF_REQUIRE(C > 0 && C <= max_c && C % 32 == 0, "%s: C=%d must be a multiple of 32 up to %d", who, C, max_c);
   BEVF_REQUIRE((long long)B * cap * C < (1ll << 31), "%s: B * capacity * C does not fit int32", who);
   return BEVF_OK;
 }
@@ -275,7 +292,7 @@ extern "C" size_t bevf_sparse_bn_work_bytes(int C) { return (size_t)NWG * C * 2 
 extern "C" int bevf_sparse_bn_stats_f32(const float* y, const int32_t* count, int B, int cap, int C, float eps, float momentum,
                                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean,
                                         float* invstd, int32_t* nrows, void* work, void* stream) {
-  if (int rc = rows_check("sparse_bn_stats", B, cap, C)) return rc;
+  if (int rc = rows_check("sparse_bn_stats", B, cap, C, BN_MAX_C)) return rc;
   BEVF_REQUIRE(y && count && mean && invstd && work, "sparse_bn_stats: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* part = aligned_part(work);
@@ -288,7 +305,7 @@ extern "C" int bevf_sparse_bn_stats_f32(const float* y, const int32_t* count, in
 
 extern "C" int bevf_sparse_bn_apply_f32(const float* y, const int32_t* count, int B, int cap, int C, const float* mean, const float* invstd,
                                         const float* gamma, const float* beta, float* a, void* stream) {
-  if (int rc = rows_check("sparse_bn_apply", B, cap, C)) return rc;
+  if (int rc = rows_check("sparse_bn_apply", B, cap, C, BN_MAX_C)) return rc;
   BEVF_REQUIRE(y && count && mean && invstd && a, "sparse_bn_apply: null pointer");
   BEVF_REQUIRE(bevf_aligned16(y) && bevf_aligned16(a), "sparse_bn_apply: y / a must be 16-byte aligned");
   hipLaunchKernelGGL(sp_bn_apply, dim3(blocks_for((long long)B * cap * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), y, count,
@@ -299,7 +316,7 @@ extern "C" int bevf_sparse_bn_apply_f32(const float* y, const int32_t* count, in
 extern "C" int bevf_sparse_bn_backward_f32(const float* y, const float* da, const int32_t* count, int B, int cap, int C, const float* mean,
                                            const float* invstd, const float* gamma, const float* beta, int frozen, float* dy,
                                            float* dgamma, float* dbeta, float* sums, void* work, void* stream) {
-  if (int rc = rows_check("sparse_bn_backward", B, cap, C)) return rc;
+  if (int rc = rows_check("sparse_bn_backward", B, cap, C, BN_MAX_C)) return rc;
   BEVF_REQUIRE(y && da && count && mean && invstd && dy && dgamma && dbeta && sums && work, "sparse_bn_backward: null pointer");
   BEVF_REQUIRE(bevf_aligned16(y) && bevf_aligned16(da) && bevf_aligned16(dy), "sparse_bn_backward: y / da / dy must be 16-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -1397,6 +1397,65 @@ class IoUHeadEngine(_Engine):
         return out
 
 
+# ---- CenterPoint second stage (roi_head.RoIHead) -----------------------------------------------------------------
+
+class RoIHeadEngine(_Engine):
+    """Eval mode: the five-point gather, then three launches of the 1x1 convolution kernel over the (1, B*K, 1, .) row image --
+    the two shared layers with BatchNorm folded and ReLU, and cls_out / reg_out as one 8-channel layer (zero rows up to
+    depth_net_width).  fp32 or bf16 storage; pred comes out fp32.  Widths that are no multiple of the kernel's K granule (32
+    channels fp32, 64 bf16) are padded with zero weights (the gathered rows are then copied into a padded buffer); at the default
+    widths (5 * 256 -> 256 -> 256) nothing is padded."""
+
+    def pack(self) -> None:
+        m = self.module
+        g = 64 if self.dtype == torch.bfloat16 else 32
+        pad = lambda n: -(-n // g) * g
+        self.C5, F = 5 * m.in_channels, m.fc
+        self.C5p, self.Fp = pad(self.C5), pad(F)
+        fc = m.shared_fc
+
+        def layer(w, scale, shift, cinp, coutp, relu):
+            cout, cin = w.shape
+            wp = torch.nn.functional.pad(w.detach(), (0, cinp - cin, 0, coutp - cout)).contiguous().view(-1)
+            scale = torch.nn.functional.pad(scale, (0, coutp - cout), value=1.0).contiguous()
+            shift = torch.nn.functional.pad(shift, (0, coutp - cout)).contiguous()
+            return _finish_pack(wp, scale, shift, cinp, coutp, 1, 1, 0, relu, split_ok=relu, wino_ok=False)
+
+        self.c1 = layer(fc[0].weight, *_bn_fold(None, fc[1], F, self.device), self.C5p, self.Fp, True)
+        self.c2 = layer(fc[3].weight, *_bn_fold(None, fc[4], F, self.device), self.Fp, self.Fp, True)
+        w3 = torch.cat([m.cls_out.weight, m.reg_out.weight], 0)
+        b3 = torch.cat([m.cls_out.bias, m.reg_out.bias], 0)
+        self.Op = depth_net_width(8)                     # (the width the convolution kernels take for any narrow output)
+        self.c3 = layer(w3, *_bn_fold(b3, None, 8, self.device), self.Fp, self.Op, False)
+
+    def run(self, bev_nhwc: torch.Tensor, boxes: torch.Tensor, count: torch.Tensor, B: int, K: int, H: int, W: int,
+            bev_range) -> torch.Tensor:
+        """bev_nhwc: the flat NHWC map [B][H][W][in_channels] in the storage dtype; boxes (B, K, 7), count int32 (B,) -> pred
+        (B, K, 8) fp32, owned by the caller."""
+        self.ensure_packed()
+        Cc, R = self.module.in_channels, B * K
+        if bev_nhwc.dtype != self.dtype or bev_nhwc.numel() < B * H * W * Cc:
+            raise L.BevfError(f"RoIHead: expected a {self.dtype} NHWC map of {B} x {H} x {W} x {Cc} elements, got {bev_nhwc.dtype} x "
+                              f"{bev_nhwc.numel()}")
+        feat = self.buf("roi_feat", R * self.C5)
+        with _span("roi_bev_points", nbytes=float(feat.element_size()) * R * self.C5 * 5):
+            L.roi_bev_points(bev_nhwc, boxes, count, feat, None, H, W, Cc, Cc, bev_range)
+        if self.C5p != self.C5:
+            x0 = self.buf("roi_feat_pad", R * self.C5p)
+            v = x0[:R * self.C5p].view(R, self.C5p)
+            v[:, self.C5:].zero_()
+            v[:, :self.C5].copy_(feat[:R * self.C5].view(R, self.C5))
+        else:
+            x0 = feat
+        a1 = self.buf("roi_fc1", R * self.Fp)
+        _run_conv(self.c1, x0, a1, 1, R, 1)
+        a2 = self.buf("roi_fc2", R * self.Fp)
+        _run_conv(self.c2, a1, a2, 1, R, 1)
+        cols = self.buf("roi_pred", R * self.Op)
+        _run_conv(self.c3, a2, cols, 1, R, 1)
+        return cols[:R * self.Op].view(R, self.Op)[:, :8].float().contiguous().view(B, K, 8)
+
+
 # ---- BEV backbone + FPN neck (bev_backbone.BEVBackbone; DESIGN.md 3.2n) ------------------------------------------------------
 
 @dataclass

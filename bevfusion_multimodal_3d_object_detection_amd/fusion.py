@@ -19,6 +19,7 @@ from . import engine as E
 from . import camera_rig as CR
 from . import bev_backbone as BB
 from . import iou_head as IH
+from . import roi_head as RH
 from . import seg_head as SH
 from . import temporal as T
 from .encoders import (MultiRadarEncoder, PillarLiDAREncoder, PointNetLiDAREncoder, ResNetCameraEncoder, SparseLiDAREncoder,  # noqa: F401
@@ -380,7 +381,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                  bev_h: Optional[int] = None, bev_w: Optional[int] = None, config: Optional[Dict] = None,
                  config_path: Optional[str] = None, lidar_encoder_type: Optional[str] = None,
                  camera_view_transform: Optional[str] = None, temporal: Optional[bool] = None, seg_head=None,
-                 iou_head=None, bev_backbone=None):
+                 iou_head=None, bev_backbone=None, roi_head=None):
         super().__init__()
         config = _cfg(config, config_path)
         # LiDAR branch: 'PointPillars' / 'pillars' (any case) from the keyword, else model.lidar_encoder.type -> the pillar
@@ -468,6 +469,14 @@ class FlexibleMultiModal3DDetector(nn.Module):
         iou = IH.iou_head_settings(iou_head, config)
         if iou is not None:
             self.iou_head = IH.IoUHead(in_channels=head_channels, config=config, **iou)
+        # opt-in second stage: roi_head=True / dict, or model.roi_head.enable; adds the keys roi_head.{shared_fc,
+        # cls_out,reg_out}.* and the 'feat' output (the map the heads read), nothing else
+        self.roi_head = None
+        roi = RH.roi_head_settings(roi_head, config)
+        if roi is not None:
+            if self.fusion_type != "bev":
+                raise E.L.BevfError("roi_head needs the 'bev' fusion")
+            self.roi_head = RH.RoIHead(in_channels=head_channels, pc_range=self.fusion.pc_range, config=config, **roi)
 
     def camera_calib_tensor(self, camera_imgs, camera_calib):
         """`camera_calib=` of forward checked against the camera input (FlexibleBEVFusion.camera_calib_tensor); None without
@@ -516,6 +525,9 @@ class FlexibleMultiModal3DDetector(nn.Module):
         (B, num_classes, Ho, Wo) in fp32 of seg_head.BEVSegmentationHead on the fused map.
         A model built with iou_head= returns 'iou' as well, in eval and train mode: the (B, 1, H, W) fp32 map of
         iou_head.IoUHead, 2 * IoU - 1 of the box regressed at each cell (iou_aware.IoUAwareLoss, the decode's iou_rectify=).
+        A model built with roi_head= returns 'feat' as well, in eval and train mode: an owned (B, C, H, W)
+        channels-last copy of the map the heads read (the neck's concat with a bev_backbone, else the fused map), detached in train
+        mode -- the input of roi_head.RoIHead and of `refine`.
         camera_calib (camera_view_transform='project' or 'frustum'): per-frame camera calibration -- a sequence of B
         camera_rig.CameraRig, or the float64 (B, ncam, 4, 4) tensor of camera_rig.calib_matrices (host or device); None = the
         fusion's rig for every frame.
@@ -575,7 +587,7 @@ class FlexibleMultiModal3DDetector(nn.Module):
                 lid = self.lidar_encoder._forward_eval(lidar_points)
         if self.use_radar and radar_points is not None:
             rad = self.radar_encoder._forward_eval(radar_points)
-        if history is None and self.seg_head is None and self.iou_head is None and self.bev_backbone is None:
+        if history is None and self.seg_head is None and self.iou_head is None and self.bev_backbone is None and self.roi_head is None:
             fused, B = self.fusion.forward_nhwc(cam, geom, lid, rad, camera_calib if cam is not None else None)
             return self.det_head.forward_nhwc(fused, B, self.fusion.bev_h, self.fusion.bev_w)
         fus = self.fusion
@@ -590,7 +602,24 @@ class FlexibleMultiModal3DDetector(nn.Module):
             out["iou"] = self.iou_head.forward_nhwc(feat, B, fus.bev_h, fus.bev_w)
         if history is not None:
             out["bev"] = T.own_bev(fused, B, fus.bev_h, fus.bev_w, fus.bev_channels)   # (the engine reuses its buffer: an owned copy)
+        if self.roi_head is not None:                                   # the second stage's input, owned like 'bev'
+            out["feat"] = T.own_bev(feat, B, fus.bev_h, fus.bev_w, self.roi_head.in_channels)
         return out
+
+    def refine(self, out: Dict[str, torch.Tensor], *, refine_score_thresh: float = 0.0, **decode_keywords) -> Dict[str, torch.Tensor]:
+        """The second stage on the forward's outputs (a model built with roi_head=):
+        centernet_target.decode_padded(out, **decode_keywords) -> roi_head(out['feat'], rois) -> roi_refine.refine_padded(rois,
+        head_out, refine_score_thresh) -> the final padded records, with nothing read back.  (score_thresh among the decode keywords
+        is the first stage's threshold.)"""
+        if self.roi_head is None:
+            raise E.L.BevfError("refine needs a detector built with roi_head=True")
+        if "feat" not in out:
+            raise E.L.BevfError("refine: the outputs lack 'feat' (pass the dict the forward of this model returned)")
+        from .centernet_target import decode_padded
+        from .roi_refine import refine_padded
+        with torch.no_grad():
+            rois = decode_padded(out, **decode_keywords)
+            return refine_padded(rois, self.roi_head(out["feat"], rois), refine_score_thresh)
 
     def get_config_str(self) -> str:
         return f"{self.fusion.get_config_str()}_{self.fusion_type}_{self.detection_head_type}"
@@ -698,7 +727,7 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
                     config: Optional[Dict] = None, config_path: Optional[str] = None,
                     lidar_encoder_type: Optional[str] = None, camera_view_transform: Optional[str] = None,
                     temporal: Optional[bool] = None, seg_head=None, iou_head=None, bev_backbone=None,
-                    **kwargs) -> FlexibleMultiModal3DDetector:
+                    roi_head=None, **kwargs) -> FlexibleMultiModal3DDetector:
     """ref src/fusion.py:1148-1221.  modality_config: 'camera_only' | 'camera+lidar' | ... | 'all'; the
     flags are substring tests on the lower-cased, space-stripped string (ref :1197-1202).
     lidar_encoder_type: 'PointPillars' selects the pillar LiDAR branch (None: the config's model.lidar_encoder.type).
@@ -711,7 +740,11 @@ def create_detector(modality_config: Optional[str] = None, fusion_type: Optional
     iou_head: True, or a dict of {head_conv}, adds the IoU-aware head (iou_head.IoUHead) on the fused map and the 'iou' output
     (None: the config's model.iou_head.enable, else off).
     bev_backbone: True, or a dict of bev_backbone.BEVBackbone's settings, puts the multi-scale BEV backbone + FPN neck between the
-    fuser and every head (None: the config's model.bev_backbone.enable, else off)."""
+    fuser and every head (None: the config's model.bev_backbone.enable, else off).
+    roi_head: True, or a dict of {fc}, adds CenterPoint's second stage (roi_head.RoIHead) on the map the heads read, the 'feat'
+    output and `model.refine` (None: the config's model.roi_head.enable, else off)."""
+    if roi_head is not None:
+        kwargs["roi_head"] = roi_head
     if bev_backbone is not None:
         kwargs["bev_backbone"] = bev_backbone
     if iou_head is not None:

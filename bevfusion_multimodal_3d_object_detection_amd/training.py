@@ -1579,6 +1579,137 @@ class IoUHeadTape:
         return dx
 
 
+def _pad_cols(t, rows: int, c: int, cp: int):
+    """[rows][c] -> [rows][cp] with zero columns appended (the convolution kernels' 32-channel granule); t itself when c == cp."""
+    if c == cp:
+        return t
+    out = torch.zeros(rows * cp, device=t.device)
+    out.view(rows, cp)[:, :c] = t[:rows * c].view(rows, c)
+    return out
+
+
+def _pad_vec(v, n: int, np_: int, value: float):
+    v = torch.full((n,), value, device=v.device) if v is None else v.detach().float()
+    return torch.nn.functional.pad(v, (0, np_ - n), value=value).contiguous()
+
+
+class RoIRowLayer:
+    """One `Linear(no bias) -> BatchNorm1d -> ReLU` of RoIHead.shared_fc over the [B * K] RoI rows: the 1x1 convolution kernel on the
+    row image, then the row BatchNorm with the device-side count (L.sparse_bn_*, cap = K), so rows past count[b] enter neither the
+    statistics nor the gradients.  Widths are padded to the kernels' 32-channel granule with zero weights (gamma 1, beta 0 there: the
+    padding columns stay exactly zero forwards and backwards); at the default widths (5 * 256 -> 256 -> 256) nothing is padded."""
+
+    def __init__(self, lin, bn, cin: int, cinp: int, cout: int, coutp: int):
+        self.lin, self.bn, self.cin, self.cinp, self.cout, self.coutp = lin, bn, cin, cinp, cout, coutp
+        w = lin.weight.detach().float()
+        self.wp = torch.nn.functional.pad(w, (0, cinp - cin, 0, coutp - cout)).contiguous()          # [coutp][cinp]
+
+    def forward(self, x, count, B: int, K: int):
+        bn, dev, F, Fp, R = self.bn, x.device, self.cout, self.coutp, B * K
+        self.x, self.count, self.B, self.K = x, count, B, K
+        self.y, _, _ = conv_raw(x, self.wp.view(-1), None, R, 1, 1, self.cinp, Fp, 1, 1, 0)
+        self.gamma, self.beta = _pad_vec(bn.weight, F, Fp, 1.0), _pad_vec(bn.bias, F, Fp, 0.0)
+        self.frozen = bn_is_frozen(bn)
+        if self.frozen:
+            self.mean = _pad_vec(bn.running_mean, F, Fp, 0.0)
+            self.invstd = _pad_vec(torch.rsqrt(bn.running_var.detach().float() + bn.eps), F, Fp, 1.0)
+        else:
+            self.mean, self.invstd = _new(Fp, dev), _new(Fp, dev)
+            work = torch.empty(L.sparse_bn_work_bytes(Fp), dtype=torch.uint8, device=dev)
+            track = bn.track_running_stats and bn.running_mean is not None
+            rm = rv = None
+            if track:                                                        # (padded widths: the buffers go through padded copies)
+                rm, rv = (bn.running_mean, bn.running_var) if F == Fp else (_pad_vec(bn.running_mean, F, Fp, 0.0),
+                                                                            _pad_vec(bn.running_var, F, Fp, 1.0))
+            with E._span("sparse_bn_stats"):
+                L.sparse_bn_stats(self.y, count, B, K, Fp, bn.eps, -1.0 if bn.momentum is None else bn.momentum, rm, rv,
+                                  bn.num_batches_tracked if track else None, self.mean, self.invstd, None, work)
+            if track:
+                if F != Fp:
+                    bn.running_mean.copy_(rm[:F])
+                    bn.running_var.copy_(rv[:F])
+                for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):   # written through raw pointers
+                    if t is not None:
+                        torch.autograd.graph.increment_version(t)
+        a = torch.zeros(R * Fp, device=dev)                                  # rows past the count stay zero
+        with E._span("sparse_bn_apply"):
+            L.sparse_bn_apply(self.y, count, B, K, Fp, self.mean, self.invstd, self.gamma, self.beta, a)
+        return a
+
+    def backward(self, da, sink: GradSink, need_dx: bool):
+        bn, dev, F, Fp, B, K = self.bn, da.device, self.cout, self.coutp, self.B, self.K
+        R = B * K
+        dy, dgamma, dbeta, sums = torch.zeros(R * Fp, device=dev), _new(Fp, dev), _new(Fp, dev), _new(2 * Fp, dev)
+        work = torch.empty(L.sparse_bn_work_bytes(Fp), dtype=torch.uint8, device=dev)
+        with E._span("sparse_bn_backward"):
+            L.sparse_bn_backward(self.y, da, self.count, B, K, Fp, self.mean, self.invstd, self.gamma, self.beta, self.frozen, dy,
+                                 dgamma, dbeta, sums, work)
+        sink.add(bn.weight, dgamma[:F])
+        sink.add(bn.bias, dbeta[:F])
+        dw = conv_wgrad(self.x, dy, R, 1, 1, self.cinp, Fp, 1, 1, 0).reshape(Fp, self.cinp)
+        sink.add(self.lin.weight, dw[:F, :self.cin])
+        if not need_dx:
+            return None
+        return conv_dgrad(dy, self.wp.view(Fp, self.cinp, 1, 1), R, 1, 1, self.cinp, Fp, 1, 1, 0)
+
+
+class RoIHeadTape:
+    """RoIHead (roi_head.py) on an NHWC map [B*H*W*C] and padded RoIs: the five-point gather (keeping its sample
+    table), two RoIRowLayer, and cls_out / reg_out as one 8-column layer padded to engine.depth_net_width -> pred (B, K, 8).  The
+    backward ends in the gather's pull kernel when the map wants a gradient."""
+
+    def __init__(self, head):
+        self.head = head
+
+    def forward(self, x, boxes, count, B: int, K: int, H: int, W: int, bev_range):
+        h, dev = self.head, x.device
+        Cc, F, R = h.in_channels, h.fc, B * K
+        p32 = lambda n: (n + 31) // 32 * 32
+        C5, self.Op = 5 * Cc, E.depth_net_width(8)
+        C5p, Fp = p32(C5), p32(F)
+        self.geom = (B, K, H, W, Cc, C5, C5p, F, Fp)
+        self.count = count
+        feat = _new(R * C5, dev)
+        self.table = torch.empty(L.roi_bev_points_table_words(B, K), dtype=torch.int32, device=dev)
+        with E._span("roi_bev_points"):
+            L.roi_bev_points(x, boxes, count, feat, self.table, H, W, Cc, Cc, bev_range)
+        fc = h.shared_fc
+        self.l1 = RoIRowLayer(fc[0], fc[1], C5, C5p, F, Fp)
+        self.l2 = RoIRowLayer(fc[3], fc[4], F, Fp, F, Fp)
+        a1 = self.l1.forward(_pad_cols(feat, R, C5, C5p), count, B, K)
+        self.a2 = self.l2.forward(a1, count, B, K)
+        w3 = torch.cat([h.cls_out.weight.detach(), h.reg_out.weight.detach()], 0).float()
+        b3 = torch.cat([h.cls_out.bias.detach(), h.reg_out.bias.detach()], 0).float()
+        self.w3p = torch.nn.functional.pad(w3, (0, Fp - F, 0, self.Op - 8)).contiguous()               # [Op][Fp]
+        cols, _, _ = conv_raw(self.a2, self.w3p.view(-1), torch.nn.functional.pad(b3, (0, self.Op - 8)).contiguous(), R, 1, 1, Fp,
+                              self.Op, 1, 1, 0)
+        return cols[:R * self.Op].view(R, self.Op)[:, :8].reshape(B, K, 8)
+
+    def backward(self, dpred, sink: GradSink, need_dx: bool):
+        """dpred (B, K, 8) -> the gradient of the input NHWC map (None unless need_dx)."""
+        h, dev = self.head, dpred.device
+        B, K, H, W, Cc, C5, C5p, F, Fp = self.geom
+        R, Op = B * K, self.Op
+        dcols = torch.zeros(R * Op, device=dev)                                 # the padding columns carry no gradient
+        dcols.view(R, Op)[:, :8] = dpred.reshape(R, 8).float()
+        db = colsum(dcols, R, Op)
+        sink.add(h.cls_out.bias, db[:1])
+        sink.add(h.reg_out.bias, db[1:8])
+        dw3 = conv_wgrad(self.a2, dcols, R, 1, 1, Fp, Op, 1, 1, 0).reshape(Op, Fp)
+        sink.add(h.cls_out.weight, dw3[:1, :F])
+        sink.add(h.reg_out.weight, dw3[1:8, :F])
+        da2 = conv_dgrad(dcols, self.w3p.view(Op, Fp, 1, 1), R, 1, 1, Fp, Op, 1, 1, 0)
+        da1 = self.l2.backward(da2, sink, True)
+        dx0 = self.l1.backward(da1, sink, need_dx)
+        if not need_dx:
+            return None
+        dfeat = dx0 if C5 == C5p else dx0[:R * C5p].view(R, C5p)[:, :C5].contiguous().view(-1)
+        dx = _new(B * H * W * Cc, dev)
+        with E._span("roi_bev_points_bwd"):
+            L.roi_bev_points_bwd(dfeat, self.table, self.count, dx, B, K, H, W, Cc)
+        return dx
+
+
 class DeconvBNLayer:
     """ConvTranspose2d(kernel = stride = s, no bias) -> train-mode BN -> ReLU, written into a channel slice of a wider NHWC map
     (the FPN neck's concat).  Forward: the raw transposed convolution (csrc/deconv.hip; s = 1: a 1x1 convolution
@@ -1725,6 +1856,7 @@ class DetectorTape:
         if getattr(m, "bev_backbone", None) is not None:   # the decoder between the fuser and every head; the
             self.bb = BackboneTape(m.bev_backbone)         # 'bev' output above stays the fuser's map
             fused = self.bb.forward(fused, B, self.fusion.H, self.fusion.W)
+        self.feat = (fused, B)                    # the map the heads read: the 'feat' output of a model with a RoI head is copied from it
         self.head = HeadTape(m.det_head)
         outs = self.head.forward(fused, B, self.fusion.H, self.fusion.W)
         if self.depth_sup is not None:
@@ -1863,6 +1995,10 @@ def detector_train_forward(model, imgs, pts, radars, camera_calib=None, depth_su
         from .temporal import own_bev
         fus = model.fusion
         res["bev"] = own_bev(tape.bev[0], tape.bev[1], fus.bev_h, fus.bev_w, fus.bev_channels)
+    if getattr(model, "roi_head", None) is not None:                      # the second stage trains on a constant map
+        from .temporal import own_bev
+        fus = model.fusion
+        res["feat"] = own_bev(tape.feat[0], tape.feat[1], fus.bev_h, fus.bev_w, model.roi_head.in_channels)
     return res
 
 
@@ -2122,6 +2258,25 @@ def iou_head_train_forward(head, x: torch.Tensor) -> torch.Tensor:
 
     def bwd(douts, sink):
         return [E.to_nchw(tape.backward(douts[0], sink), B, Cin, H, W)]
+
+    (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
+    return out
+
+
+def roi_head_train_forward(head, x: torch.Tensor, boxes: torch.Tensor, count: torch.Tensor, bev_range) -> torch.Tensor:
+    """RoIHead.forward under train-mode BatchNorm -> pred (B, K, 8), with gradients for the parameters and, when it asks for one, for
+    the BEV map `x` (B, C, H, W).  The RoIs are constants of the step."""
+    B, Cin, H, W = x.shape
+    K = boxes.shape[1]
+    tape = RoIHeadTape(head)
+    need_dx = x.requires_grad
+
+    def fwd(x):
+        return (tape.forward(_nhwc(x.detach()), boxes, count, B, K, H, W, bev_range),)
+
+    def bwd(douts, sink):
+        dx = tape.backward(douts[0], sink, need_dx)
+        return [E.to_nchw(dx, B, Cin, H, W) if dx is not None else None]
 
     (out,) = _TapeFn.apply("module", fwd, bwd, None, 1, x, *_trainable(head))
     return out

@@ -480,7 +480,9 @@ int bevf_sparse_canvas_bwd_f32(const float* dcanvas, const int32_t* cell, const 
  * eps), the running buffers as nn.BatchNorm1d moves them (momentum < 0 = cumulative average; untouched below two rows),
  * nrows[0] = the active rows (optional).  apply: a = relu(batchnorm(y)).  backward: g = da through the recomputed ReLU mask,
  * dgamma = sum g x_hat, dbeta = sum g, dy = gamma invstd (g - mean(g) - x_hat mean(g x_hat)), or gamma invstd g when frozen
- * (mean / invstd then are the running statistics).  sums: 2 C floats of scratch.  work: bevf_sparse_bn_work_bytes(C).     */
+ * (mean / invstd then are the running statistics).  sums: 2 C floats of scratch.  work: bevf_sparse_bn_work_bytes(C).
+ * These three take C up to 1024 (a multiple of 32; the reductions go in slabs of 128 channels, so up to 128 nothing differs from
+ * a single slab): the RoI head's MLP rows run through them with cap = K.                                   */
 size_t bevf_sparse_bn_work_bytes(int C);
 int bevf_sparse_bn_stats_f32(const float* y, const int32_t* count, int B, int cap, int C, float eps, float momentum,
                              float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean,
@@ -1185,6 +1187,70 @@ int bevf_deconv_pack_f32(const float* w, float* out, int Cin, int Cout, int s, v
 int bevf_deconv_pack_bf16(const float* w, void* out, int Cin, int Cout, int s, void* stream);
 int bevf_deconv_nhwc_f32(const bevf_deconv_desc* d, void* stream);
 int bevf_deconv_nhwc_bf16(const bevf_deconv_desc* d, void* stream);
+
+/* ==========================================================================================
+ * CenterPoint second stage: RoI BEV-point head (csrc/roi_points.hip, csrc/roi_head.hip).
+ * ========================================================================================== */
+
+/* Conventions of all entry points below.  RoIs are the decode's padded records: boxes [B][K][7] = (x, y, z, w, l, h, yaw) with l along
+ * the heading, count int32 [B] clamped to [0, K]; rows past the count are never read.  The map is flat NHWC [B][H][W] rows of C
+ * channels at channel stride x_cs, covering [x_min, x_max) x [y_min, y_max): cells of vx = (x_max - x_min) / W by
+ * vy = (y_max - y_min) / H, a cell's feature at the cell centre, so a world point (px, py) samples at column
+ * u = (px - x_min) / vx - 0.5, row v = (py - y_min) / vy - 0.5.  Everything is stream-ordered, allocates nothing, uses no atomics, is
+ * bit-equal run to run, reads nothing back and is graph-capturable.
+ *
+ * bevf_roi_bev_points_*: feat [B * K][5 * C] in the map's storage type, row (b, k); point p occupies channels [p C, (p + 1) C).  The
+ * points, in order: the centre, centre +- (l / 2)(cos yaw, sin yaw) (front, back), centre +- (w / 2)(-sin yaw, cos yaw) (left, right),
+ * in fp64 from the fp32 box.  A sample = the corner (i0, j0) = (floor v, floor u) and the four weights (1 - fi)(1 - fj), (1 - fi) fj,
+ * fi (1 - fj), fi fj (fp64 products, each rounded once to fp32) of the corners (i0, j0), (i0, j0 + 1), (i0 + 1, j0), (i0 + 1, j0 + 1);
+ * a channel = w0 v0, then fma with corners 1, 2, 3 in fp32 (bevf_bev_warp_* / bevf_bev_grid_resample_*'s order), rounded once to the
+ * storage type.  A corner outside the map contributes zero; a row with k >= count[b], a non-finite point and a point with u or v
+ * outside (-1, W) / (-1, H) are written as zeros.  table (optional, for the backward): int32 [B * K * 5][6] = i0, j0 and the bits
+ * of the four weights (all zero for a zero row); bevf_roi_bev_points_table_words(B, K) words.  fp32 moves channel quads when
+ * C % 4 == 0 (x_cs % 4 == 0, 16-byte aligned buffers), bf16 eight or four channels when C % 8 == 0 / C % 4 == 0; anything else scalar.
+ * B * K * 5 * max(C, 6), B * H * W * x_cs below 2^31.                                                                               */
+size_t bevf_roi_bev_points_table_words(int B, int K);
+int bevf_roi_bev_points_f32(const float* x, const float* boxes, const int32_t* count, float* feat, int32_t* table, int B, int K,
+                            int H, int W, int C, int x_cs, double x_min, double y_min, double x_max, double y_max, void* stream);
+int bevf_roi_bev_points_bf16(const void* x, const float* boxes, const int32_t* count, void* feat, int32_t* table, int B, int K,
+                             int H, int W, int C, int x_cs, double x_min, double y_min, double x_max, double y_max, void* stream);
+/* The gradient of the map: dx [B][H][W][C] (dense) = sum over the frame's samples s = k * 5 + p < 5 count[b], in ascending s, of
+ * w(s -> cell) * dfeat[b * K * 5 + s][:] (dfeat [B * K][5 * C] dense), by fma from 0.  A pull: one wave per map cell scans the frame's
+ * table rows 64 at a time.  Cells no sample touches are exact zeros; every cell is written.                                      */
+int bevf_roi_bev_points_bwd_f32(const float* dfeat, const int32_t* table, const int32_t* count, float* dx, int B, int K, int H,
+                                int W, int C, void* stream);
+/* RoI targets against the padded ground truth gt [B][M][7], gt_labels int32 [B][M] (< 0 = padding; M = 0: both may be NULL).  A GT is
+ * a candidate of RoI (b, k) when its label is >= 0 and, with match_labels, equals roi_labels[b][k] (int64 [B][K], else may be NULL).
+ * Per RoI with k < count[b]:  iou = the best IoU(roi, gt) over the candidates (box_geom.h's rotated 3-D IoU, or the BEV IoU when
+ * use_bev), gt_index = the lowest index among equal best values; no candidate: gt_index = -1, iou = 0.
+ *   cls_target = clamp(2 iou - 0.5, 0, 1);  reg_mask = iou >= reg_fg_thresh and all six sizes > 0;
+ *   reg_target[7] (zeros where reg_mask is 0), with d = gt - roi, c = cos yaw, s = sin yaw, diag = sqrt(l^2 + w^2) of the RoI:
+ *     ((c dx + s dy) / diag, (c dy - s dx) / diag, dz / h, log(w_g / w), log(l_g / l), log(h_g / h), dyaw),
+ *     dyaw = yaw_g - yaw wrapped into [-pi, pi), then folded into [-pi / 2, pi / 2] by -+ pi (opposite headings are the same box).
+ * Rows past the count: zeros with gt_index -1.  iou, cls_target [B][K]; gt_index int32 [B][K]; reg_mask uint8 [B][K]; reg_target
+ * [B][K][7].  One wave per RoI.                                                                                                  */
+int bevf_roi_targets_f32(const float* rois, const int32_t* count, const int64_t* roi_labels, const float* gt, const int32_t* gt_labels,
+                         float* iou, int32_t* gt_index, float* cls_target, uint8_t* reg_mask, float* reg_target, int B, int K, int M,
+                         int use_bev, int match_labels, float reg_fg_thresh, void* stream);
+/* The head's output pred [B * K][8] = the logit, then seven residuals.  Over the rows with k < count[b] (n_valid of them, n_fg with
+ * reg_mask set):  cls_loss = sum (max(x, 0) - x t + log1p(exp(-|x|))) / (n_valid + 1e-4), reg_loss = sum over reg_mask of
+ * sum_7 |res - reg_target| / (n_fg + 1e-4);  out[3] = w_cls cls_loss + w_reg reg_loss, cls_loss, reg_loss.  One workgroup, sums in
+ * fp64 in a fixed order.  bwd: dpred [B * K][8] = d out[0] / d pred, exact zeros on rows past the count.                          */
+int bevf_roi_loss_f32(const float* pred, const int32_t* count, const float* cls_target, const uint8_t* reg_mask,
+                      const float* reg_target, float* out, int B, int K, float w_cls, float w_reg, void* stream);
+int bevf_roi_loss_bwd_f32(const float* pred, const int32_t* count, const float* cls_target, const uint8_t* reg_mask,
+                          const float* reg_target, float* dpred, int B, int K, float w_cls, float w_reg, void* stream);
+/* The refine step: the inverse of the encoding above applied to every RoI with the residual t = pred[1 .. 7],
+ *   x' = x + (c t0 - s t1) diag, y' = y + (s t0 + c t1) diag, z' = z + t2 h, (w', l', h') = (w exp t3, l exp t4, h exp t5),
+ *   yaw' = yaw + t6 (not wrapped);  score' = sqrt(score * sigmoid(pred[0]));  labels (int64) and velocities ([B][K][2], optional:
+ *   both pointers NULL) carried through.
+ * A row is dropped when k >= count[b], when score' is not finite or when score' < score_thresh.  The frame's kept rows are written
+ * compacted and in descending score', ties by ascending RoI index -- what bevf_nms_boxes_f32 and bevf_track_step_f32 expect of their
+ * input -- out_count[b] = their number, the rows behind them zeros.  One workgroup per frame, ranks by counting over the scores in
+ * LDS.  K <= 4096, B <= 65535; the outputs must not alias the inputs.                                                             */
+int bevf_roi_refine_f32(const float* rois, const float* scores, const int64_t* labels, const float* velocities, const int32_t* count,
+                        const float* pred, float* out_boxes, float* out_scores, int64_t* out_labels, float* out_velocities,
+                        int32_t* out_count, int B, int K, float score_thresh, void* stream);
 
 #ifdef __cplusplus
 }
